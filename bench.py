@@ -11,6 +11,11 @@ iterations each (eps = 0, x0 = 0, b = A x_true), bracketed by a barrier and a de
 every solve's set-up (r = b - A x, r0 = p = r, one dot) and status read-back.  Rank 0 prints ONE JSON line.  N > 1: rows are range-partitioned across the ranks (strong scaling, the matrix is
 the same 10M-row matrix), see sparse_matrix_math_amd/distributed.py.
 
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, roofline of the timed region).  --full
+adds every other measurement: the CSR leg with the STREAM family forced (roofline_csr, spmv_gbps), the second handle's set-up time, the
+extras legs (unless --no-extras), the Matrix Market leg and the CPU baseline (--cpu-seconds).  --dump-outputs DIR writes what the
+timed path returned in its last step (the solution x of the last solve, its residual norm, status and iteration count) as .npy files.
+
 roofline: the dominant kernel is the SpMV; `achieved` = algorithmic bytes of one SpMV launch
 (B_spmv = nnz*(s+4) + (rows+1)*4 + cols*s + rows*s; the fused-dot launches also read one or two more
 vectors, which are NOT counted) divided by the average launch duration measured with HIP events inside the timed region.
@@ -43,18 +48,47 @@ def parse_args():
     ap.add_argument("--max-offset", type=int, default=1 << 20)
     ap.add_argument("--diag-shift", type=float, default=1.0, help="A[i][i] = shift + sum|offdiag| (SURVEY.md section 8d: 1.0)")
     ap.add_argument("--iters-per-solve", type=int, default=20, help="BiCGStab iterations per solver call inside the timed region")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-baseline budget; 0 disables it")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-baseline budget (--full); 0 disables it")
     ap.add_argument("--spmv-family", type=int, default=0)
     ap.add_argument("--spmv-lanes", type=int, default=0)
     ap.add_argument("--autotune", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra (non-headline) PATTERN-family measurement")
-    ap.add_argument("--mtx", default=None, help="extras leg (BASELINE config 5): a Matrix Market file read by the drop-in header's direct-to-CSR loader and "
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra (non-headline) SpMV / solver legs")
+    ap.add_argument("--mtx", default=None, help="--full's extras leg (BASELINE config 5): a Matrix Market file read by the drop-in header's direct-to-CSR loader and "
                     "solved with BiCGStab + none / Jacobi / BLOCK_ILU0 / ILU0 (tests/cpp/mtx_bicgstab); default: ./atmosmodd.mtx when it exists, else a "
                     "generated 1.26 M-row general file with varying coefficients")
     ap.add_argument("--dist", action="store_true", help="take the row-partitioned multi-GPU code path even with one rank")
     ap.add_argument("--dist-driver", choices=["native", "python"], default="native",
                     help="N > 1: the loop behind the C ABI (csrc/smm_dist.hip, RCCL) or the Python driver over torch.distributed")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every non-headline measurement: the STREAM-forced CSR leg, the second handle's set-up, the extras legs, "
+                         "the Matrix Market leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (x, resnorm, status and iterations of the last solve) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # x is written whole up to this size, else a fixed seeded sample of its entries (all files < 64 MB)
+
+
+def dump_outputs(outdir, x, status, iterations, resnorm, seed):
+    """the arrays a caller of smm_hip_bicgstab_dev receives from the timed path's last solve: x, and status / iterations / resnorm as
+    float64 scalars.  x larger than DUMP_BUDGET_BYTES is sampled at the same sorted, seeded positions on every run (x_index.npy holds them)."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    x = x.detach().cpu().numpy()
+    if x.nbytes > DUMP_BUDGET_BYTES:
+        k = DUMP_BUDGET_BYTES // (x.itemsize + 8)  # the sampled entries and their float64 positions share the budget
+        idx = np.sort(np.random.default_rng(seed).choice(x.size, k, replace=False))
+        np.save(os.path.join(outdir, "x_index.npy"), idx.astype(np.float64))
+        x = x[idx]
+    np.save(os.path.join(outdir, "x.npy"), x)
+    np.save(os.path.join(outdir, "resnorm.npy"), np.array([resnorm], dtype=np.float64))
+    np.save(os.path.join(outdir, "status.npy"), np.array([status], dtype=np.float64))
+    np.save(os.path.join(outdir, "iterations.npy"), np.array([iterations], dtype=np.float64))
 
 
 def spmv_bytes(rows, cols, nnz, s):
@@ -601,6 +635,8 @@ def main():
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     use_dist = world > 1 or args.dist
+    if use_dist and args.dump_outputs:
+        raise SystemExit("--dump-outputs: the row-partitioned path keeps x split over the ranks; run the one-GPU path (--gpus 1, no --dist)")
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29513")
@@ -623,7 +659,7 @@ def main():
         from sparse_matrix_math_amd import distributed as dsm
 
         result = dsm.bench_bicgstab(args, rank, world, dev, np_dtype, t_dtype)
-        if rank == 0 and args.cpu_seconds > 0:
+        if rank == 0 and args.full and args.cpu_seconds > 0:
             # the CPU baseline belongs to the WORKLOAD, not to the partition: rank 0 builds the whole matrix once more on its GPU, hands it
             # to the host and times the bounded sample exactly as the one-GPU run does (the other ranks wait in the all-reduce below)
             nnz = host.gen_banded_nnz(n, args.band_k, args.seed, args.max_offset)
@@ -661,17 +697,19 @@ def main():
         torch.cuda.synchronize()
         first_spmv_ms = (time.perf_counter() - t0) * 1e3
         family, lanes = A.get_kernel()  # what AUTO settled on (SMM_SPMV_PATTERN when the matrix passed the verification)
-        # the same on a SECOND handle over the same arrays: the per-matrix set-up alone (analysis, verification of every entry, tile table),
-        # with whatever the process pays once (code objects, allocator warm-up) already paid by the first
-        A2 = smm.CSRMatrix.from_device(n, n, d_start, d_pos, d_val, np_dtype)
-        y2 = torch.empty(n, dtype=t_dtype, device=dev)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        A2.spmv_dev(0, None, x_true, y2, stream)
-        torch.cuda.synchronize()
-        second_handle_first_spmv_ms = (time.perf_counter() - t0) * 1e3
-        A2.close()
-        del A2, y2
+        second_handle_first_spmv_ms = None
+        if args.full:
+            # the same on a SECOND handle over the same arrays: the per-matrix set-up alone (analysis, verification of every entry, tile table),
+            # with whatever the process pays once (code objects, allocator warm-up) already paid by the first
+            A2 = smm.CSRMatrix.from_device(n, n, d_start, d_pos, d_val, np_dtype)
+            y2 = torch.empty(n, dtype=t_dtype, device=dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            A2.spmv_dev(0, None, x_true, y2, stream)
+            torch.cuda.synchronize()
+            second_handle_first_spmv_ms = (time.perf_counter() - t0) * 1e3
+            A2.close()
+            del A2, y2
         x = torch.zeros(n, dtype=t_dtype, device=dev)
         torch.cuda.synchronize()
 
@@ -688,23 +726,24 @@ def main():
                 if iters != it or not np.isfinite(resnorm) or resnorm <= 0:
                     raise SystemExit(f"BiCGStab ran {iters} of {it} iterations (resnorm {resnorm}): the timed region is invalid")
                 done += iters
-                last = (status, resnorm)
+                last = (status, resnorm, iters)
             return done, last
 
         def timed_leg():
-            """W untimed + K timed iterations with the matrix's current kernel: (iterations, seconds, summed SpMV ms, SpMV launches, resnorm)"""
+            """W untimed + K timed iterations with the matrix's current kernel: (iterations, seconds, summed SpMV ms, SpMV launches,
+            (status, resnorm, iterations) of the last solve)"""
             if args.warmup > 0:
                 run(args.warmup)
             host.profile_enable(True)
             host.profile_read(reset=True)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            iters, (_status, resnorm) = run(args.steps)
+            iters, last = run(args.steps)
             torch.cuda.synchronize()
             elapsed = time.perf_counter() - t0
             spmv_ms, spmv_launches = host.profile_read(reset=True)
             host.profile_enable(False)
-            return iters, elapsed, spmv_ms, spmv_launches, resnorm
+            return iters, elapsed, spmv_ms, spmv_launches, last
 
         def roofline_of(kernel, nbytes, spmv_ms, spmv_launches, where):
             """the roofline object of one timed leg: the bytes ONE launch of `kernel` moves by its own layout (smm_hip_csr_kernel_desc) over
@@ -723,19 +762,24 @@ def main():
         # THE timed region: the library as a user gets it (AUTO).  value, ms_per_step and roofline all describe THIS leg: roofline is its
         # dominant kernel priced with the bytes that kernel's own data layout moves -- never with another layout's
         kernel, kernel_bytes = A.kernel_desc()
-        iters, elapsed, spmv_ms, spmv_launches, resnorm = timed_leg()
+        iters, elapsed, spmv_ms, spmv_launches, (status, resnorm, last_iters) = timed_leg()
         err = float(((x - x_true).abs() / x_true).max())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, x, int(status), last_iters, float(resnorm), args.seed)
         b_spmv = spmv_bytes(n, n, nnz, s_bytes)
         chosen_by = "autotune" if args.autotune else "forced" if (args.spmv_family or args.spmv_lanes) else "auto"
         result = {"elapsed": elapsed, "iters": iters, "nnz": nnz, "resnorm": float(resnorm), "max_rel_err_vs_x_true": err,
                   "spmv_kernel": {"family": family, "lanes_per_row": lanes, "kernel": kernel, "chosen_by": chosen_by, "first_spmv_ms": first_spmv_ms,
-                                  "second_handle_first_spmv_ms": second_handle_first_spmv_ms, "pattern_encoding": A.pattern_info()[0]}}
+                                  "pattern_encoding": A.pattern_info()[0]}}
+        if second_handle_first_spmv_ms is not None:
+            result["spmv_kernel"]["second_handle_first_spmv_ms"] = second_handle_first_spmv_ms
         result["roofline"] = roofline_of(kernel, kernel_bytes, spmv_ms, spmv_launches, "the timed region")
         if family == 3:
             result["roofline"]["note"] = ("PATTERN family chosen by AUTO on the first SpMV: positions[] replaced by one verified 64-bit mask per row "
                                           "(bit-identical to STREAM at equal lanes); bytes = values + masks + start + x + out, NOT the CSR formula")
-            # The metric names "CSR SpMV GB/s (% HBM peak)": that contract -- the reference's CSR layout on the kernel that streams it
-            #  -- is measured in a leg of its own with the STREAM family forced: same matrix, same K iterations
+        # The metric names "CSR SpMV GB/s (% HBM peak)": that contract -- the reference's CSR layout on the kernel that streams it
+        #  -- is measured in a leg of its own with the STREAM family forced: same matrix, same K iterations (--full)
+        if family == 3 and args.full:
             A.set_kernel(2, 0)
             s_kernel, s_bytes_launch = A.kernel_desc()
             s_iters, s_elapsed, s_ms, s_launches, _s_res = timed_leg()
@@ -744,16 +788,16 @@ def main():
                        max_rel_err_vs_x_true=float(((x - x_true).abs() / x_true).max()))
             A.set_kernel(0, 0)  # back to AUTO's choice
             result["roofline_csr"] = csr
-        else:
+        elif family != 3:
             result["roofline_csr"] = dict(result["roofline"], value=iters / elapsed, value_unit="iterations/s", ms_per_step=elapsed / iters * 1e3)
-        assert result["roofline_csr"]["algorithmic_bytes_per_launch"] == b_spmv or result["roofline_csr"]["kernel"] == "spmvVectorKernel"
-        if not args.no_extras:
+        assert "roofline_csr" not in result or result["roofline_csr"]["algorithmic_bytes_per_launch"] == b_spmv or result["roofline_csr"]["kernel"] == "spmvVectorKernel"
+        if args.full and not args.no_extras:
             result.setdefault("extras", {}).update(extra_spmv_legs(args, smm, host, torch, np, dev, stream))
         mtx = args.mtx or (os.path.join(ROOT, "atmosmodd.mtx") if os.path.exists(os.path.join(ROOT, "atmosmodd.mtx")) else None)
-        if mtx or not args.no_extras:
+        if args.full and (mtx or not args.no_extras):
             torch.cuda.empty_cache()
-            result.setdefault("extras", {})["mtx_bicgstab"] = mtx_leg(mtx)  # config 5 on a file, every run
-        if args.cpu_seconds > 0:
+            result.setdefault("extras", {})["mtx_bicgstab"] = mtx_leg(mtx)  # config 5 on a file, every --full run
+        if args.full and args.cpu_seconds > 0:
             result["cpu_baseline"] = cpu_baseline(args, np_dtype, d_start.cpu().numpy(), d_pos.cpu().numpy(), d_val.cpu().numpy(),
                                                   b.cpu().numpy(), args.cpu_seconds)
 

@@ -66,15 +66,6 @@ def oracle_fma():
 
 
 @pytest.fixture(scope="session")
-def reference():
-    from oracle.oracle import Reference
-
-    if not Reference.available():
-        pytest.skip("oracle/_ref/libsmm_ref.so not built (the reference is only mounted in the build container)")
-    return Reference()
-
-
-@pytest.fixture(scope="session")
 def smm():
     """the product package, initialised on device 0 -- gpu tests only"""
     import sparse_matrix_math_amd as smm

@@ -38,3 +38,36 @@ def test_kernel_hash_ignores_comments_and_white_space(tmp_path, monkeypatch):
     assert bench.spmv_kernel_source_sha() == before
     (fake / "smm_device.h").write_text((fake / "smm_device.h").read_text(encoding="utf-8") + "int changed;\n", encoding="utf-8")
     assert bench.spmv_kernel_source_sha() != before
+
+
+def test_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """--dump-outputs: x whole while it fits, the scalars as float64"""
+    import numpy as np
+    import torch
+
+    x = torch.arange(1000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path), x, 0, 20, 1.5e-3, 0x5EED)
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(got) == ["iterations", "resnorm", "status", "x"]
+    np.testing.assert_array_equal(got["x"], x.numpy())
+    assert got["x"].dtype == np.float32
+    assert got["iterations"].tolist() == [20.0] and got["status"].tolist() == [0.0] and got["resnorm"].tolist() == [1.5e-3]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+
+
+def test_dump_outputs_samples_a_large_x_at_fixed_positions(tmp_path, monkeypatch):
+    """an x over the budget is written at the same seeded positions on every run, and the positions beside it"""
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 800)
+    x = torch.rand(1000, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), x, 0, 20, 1.0, 7)
+    idx = np.load(tmp_path / "a" / "x_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 800 // 16 and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "b" / "x_index.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "x.npy"), x.numpy()[idx.astype(np.int64)])
+    npy_headers = 4 * 128
+    assert os.path.getsize(tmp_path / "a" / "x.npy") + os.path.getsize(tmp_path / "a" / "x_index.npy") <= 800 + 2 * 128
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= 800 + npy_headers + 3 * 136

@@ -844,7 +844,7 @@ def test_bench_self_launch_rehearsal(ranks):
     env = dict(os.environ, SMM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--rows", "600000", "--max-offset", "65536", "--steps", "20",
-           "--warmup", "10", "--iters-per-solve", "10", "--cpu-seconds", "2"]
+           "--warmup", "10", "--iters-per-solve", "10", "--cpu-seconds", "2", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

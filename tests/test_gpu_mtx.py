@@ -57,7 +57,7 @@ def test_mtx_general_file_bicgstab_preconditioned(tmp_path, oracle):
 
 @pytest.mark.gpu
 def test_mtx_varying_coefficients_all_kinds_from_one_load(tmp_path, oracle):
-    """what bench.py's extras.mtx_bicgstab runs on every line, at 24^3: the convection-diffusion matrix with SPATIALLY VARYING coefficients
+    """what bench.py's extras.mtx_bicgstab runs on every --full line, at 24^3: the convection-diffusion matrix with SPATIALLY VARYING coefficients
     (every diagonal varies, so the PATTERN family must keep reading values[]: MASKS, never CONST) written as a shuffled `general` file,
     loaded ONCE by SMM::loadMatrix and solved with none / Jacobi / ILU0 / BLOCK_ILU0; x of the last kind against the oracle"""
     from write_mtx import write_mtx

@@ -1,11 +1,12 @@
 """CPU tests of the oracle's block preconditioners (oracle/smm_oracle_impl.inc, smm_oracle_block_*): pinned against the committed outputs
 of the real reference for the construction that defines them (tests/golden/reference_outputs_v3.npz, oracle/gen_golden_v3.py: the
-reference's SGSPreconditioner of the block-diagonal part of A, plugged into the reference's BiCGStab template) and, in the build
-container, against the real reference live.  BLOCK_ILU0 has no reference behaviour (like ILU0): it is checked against the global
+reference's SGSPreconditioner of the block-diagonal part of A, plugged into the reference's BiCGStab template; tests/golden/
+reference_outputs_v4_<dtype>.npz, oracle/gen_golden_v4.py: the same on more block shapes and on level-cut matrices).  BLOCK_ILU0 has no reference behaviour (like ILU0): it is checked against the global
 textbook ILU0 on the block-diagonal matrix and by (L U)_ij = A_ij inside every block."""
 import numpy as np
 import pytest
 
+from oracle import gen_golden_v4
 from oracle.gen_golden_v3 import bounds_sets, matrices, rhs_of
 from oracle.oracle import PRECOND_BLOCK_ILU0, PRECOND_BLOCK_SGS, PRECOND_ILU0, PRECOND_SGS, block_diagonal_part
 from sparse_matrix_math_amd import generators as gen
@@ -39,23 +40,18 @@ def test_block_sgs_matches_committed_reference_outputs(oracle, golden_v3, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_block_sgs_is_reference_sgs_of_block_diagonal(oracle, reference, dtype):
-    """live, in the build container: the real reference on the block-diagonal part"""
-    csr = gen.convdiff3d(9, 0.3, dtype=dtype)
-    rows = len(csr[0]) - 1
-    rhs = rhs_of(rows, dtype)
-    b = gen.row_sums(csr[0], csr[2])
-    for bounds in (np.array([0, rows]), np.append(np.arange(0, rows, 50), rows), np.array([0, 3, 4, 400, rows])):
-        bounds = bounds.astype(np.int32)
-        bd, _ = block_diagonal_part(csr, bounds)
-        with reference.csr(csr) as a, reference.csr(bd) as m:
-            err, x_ref = reference.sgs_apply(m, rhs)
-            assert err == 0
-            np.testing.assert_array_equal(oracle.block_sgs_apply(csr, bounds, rhs)[1], x_ref)
-            st_ref, xs_ref = reference.bicgstab_sgs_of(a, m, b, np.zeros(rows, dtype=dtype), 7, dtype(1e-30))
-            st, xs, it, _ = oracle.bicgstab_block(csr, b, np.zeros(rows, dtype=dtype), 7, dtype(1e-30), PRECOND_BLOCK_SGS, bounds)
-            assert st == st_ref
-            np.testing.assert_array_equal(xs, xs_ref)
+def test_block_sgs_is_reference_sgs_of_block_diagonal(oracle, dtype):
+    """the real reference on the block-diagonal part, as it computed it (tests/golden/reference_outputs_v4_<dtype>.npz, oracle/gen_golden_v4.py)"""
+    g = np.load(gen_golden_v4.golden_path(dtype))
+    csr, rhs, b = gen_golden_v4.block_matrix(dtype)
+    rows = len(b)
+    for bname, bounds in gen_golden_v4.block_bounds_sets(rows).items():
+        t = f"block_sgs/{bname}"
+        assert int(g[f"{t}/apply/err"]) == 0
+        np.testing.assert_array_equal(oracle.block_sgs_apply(csr, bounds, rhs)[1], g[f"{t}/apply/x"], err_msg=t)
+        st, xs, it, _ = oracle.bicgstab_block(csr, b, np.zeros(rows, dtype=dtype), 7, dtype(1e-30), PRECOND_BLOCK_SGS, bounds)
+        assert st == int(g[f"{t}/bicgstab/7/status"])
+        np.testing.assert_array_equal(xs, g[f"{t}/bicgstab/7/x"], err_msg=t)
 
 
 def slow_level_cut(csr, bounds, cap):
@@ -106,24 +102,21 @@ def test_level_cut_rule(oracle):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_level_cut_block_sgs_is_reference_sgs_of_the_cut_matrix(oracle, reference, dtype):
-    """live, in the build container: block SGS with a level cut = the real reference's SGS of the matrix the cut leaves, apply and
-    inside the reference's BiCGStab template"""
-    csr = gen.convdiff3d(9, 0.3, dtype=dtype)
-    rows = len(csr[0]) - 1
-    rhs = rhs_of(rows, dtype)
-    b = gen.row_sums(csr[0], csr[2])
-    bounds = np.append(np.arange(0, rows, 200), rows).astype(np.int32)
-    for cap in (2, 4, 16):
+def test_level_cut_block_sgs_is_reference_sgs_of_the_cut_matrix(oracle, dtype):
+    """block SGS with a level cut = the real reference's SGS of the matrix the cut leaves, apply and inside the reference's BiCGStab
+    template, as the reference computed them (tests/golden/reference_outputs_v4_<dtype>.npz, oracle/gen_golden_v4.py)"""
+    g = np.load(gen_golden_v4.golden_path(dtype))
+    csr, rhs, b = gen_golden_v4.block_matrix(dtype)
+    rows = len(b)
+    bounds = gen_golden_v4.level_cut_bounds(rows)
+    for cap in gen_golden_v4.LEVEL_CUT_CAPS:
+        t = f"level_cut/{cap}"
         mcsr = oracle.level_cut_matrix(csr, bounds, cap)[0]
-        with reference.csr(csr) as a, reference.csr(mcsr) as m:
-            err, x_ref = reference.sgs_apply(m, rhs)
-            assert err == 0
-            np.testing.assert_array_equal(oracle.block_sgs_apply(mcsr, bounds, rhs)[1], x_ref)
-            st_ref, xs_ref = reference.bicgstab_sgs_of(a, m, b, np.zeros(rows, dtype=dtype), 7, dtype(1e-30))
-            st, xs, it, _ = oracle.bicgstab_block_of(csr, mcsr, b, np.zeros(rows, dtype=dtype), 7, dtype(1e-30), PRECOND_BLOCK_SGS, bounds)
-            assert st == st_ref
-            np.testing.assert_array_equal(xs, xs_ref)
+        assert int(g[f"{t}/apply/err"]) == 0
+        np.testing.assert_array_equal(oracle.block_sgs_apply(mcsr, bounds, rhs)[1], g[f"{t}/apply/x"], err_msg=t)
+        st, xs, it, _ = oracle.bicgstab_block_of(csr, mcsr, b, np.zeros(rows, dtype=dtype), 7, dtype(1e-30), PRECOND_BLOCK_SGS, bounds)
+        assert st == int(g[f"{t}/bicgstab/7/status"])
+        np.testing.assert_array_equal(xs, g[f"{t}/bicgstab/7/x"], err_msg=t)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

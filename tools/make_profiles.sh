@@ -9,8 +9,8 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/profiles_$ROUND
 mkdir -p $OUT
 cd $ROOT
-timeout -k 10 500 python bench.py > $OUT/bench_stdout.json 2> $OUT/bench_stderr.txt || { echo "bench failed"; tail -5 $OUT/bench_stderr.txt; exit 1; }
-( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof -- python3 $ROOT/bench.py --cpu-seconds 0 > $OUT/bench_under_rocprof_stdout.json 2> /dev/null ) || { echo "rocprofv3 run failed"; exit 1; }
+timeout -k 10 500 python bench.py --full > $OUT/bench_stdout.json 2> $OUT/bench_stderr.txt || { echo "bench failed"; tail -5 $OUT/bench_stderr.txt; exit 1; }
+( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof -- python3 $ROOT/bench.py --full --cpu-seconds 0 > $OUT/bench_under_rocprof_stdout.json 2> /dev/null ) || { echo "rocprofv3 run failed"; exit 1; }
 cp $(ls $OUT/rocprof/*/*_kernel_stats.csv | head -1) $OUT/bench_kernel_stats.csv
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof_block -- python3 $ROOT/tools/block_precond_timing.py --skip-global --block-rows 0 > $OUT/block_under_rocprof.txt 2> /dev/null ) || { echo "rocprofv3 block run failed"; exit 1; }
 cp $(ls $OUT/rocprof_block/*/*_kernel_stats.csv | head -1) $OUT/block_kernel_stats.csv

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $ROOT
 timeout -k 10 1000 python -m pytest tests/ -x -q -m gpu > $OUT/gpu_suite.txt 2>&1
 echo "suite rc $?"; tail -12 $OUT/gpu_suite.txt | cut -c1-400
-timeout -k 10 400 python bench.py > $OUT/bench_stdout.json 2> $OUT/bench_stderr.txt
+timeout -k 10 400 python bench.py --full > $OUT/bench_stdout.json 2> $OUT/bench_stderr.txt
 echo "bench rc $?"
 python - <<'PY'
 import json, os

@@ -3,7 +3,7 @@ set -u
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r05; mkdir -p $OUT
 for nt in 0 1 0 1; do
-  SMM_HIP_NT_OUT=$nt timeout -k 10 300 python bench.py --cpu-seconds 0 > $OUT/bench_nt$nt.json 2>/dev/null
+  SMM_HIP_NT_OUT=$nt timeout -k 10 300 python bench.py --full --cpu-seconds 0 > $OUT/bench_nt$nt.json 2>/dev/null
   python - <<PY
 import json
 p = json.load(open("$OUT/bench_nt$nt.json"))

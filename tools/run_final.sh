@@ -11,7 +11,7 @@ echo "pytest exit $RC"
 [ $RC -ne 0 ] && exit $RC
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/final_smoke.log 2>&1
 echo "smoke exit $?"; tail -n 2 $OUT/final_smoke.log
-timeout -k 10 600 python bench.py > $OUT/final_bench.json 2> $OUT/final_bench.err
+timeout -k 10 600 python bench.py --full > $OUT/final_bench.json 2> $OUT/final_bench.err
 echo "bench exit $?"
 python - <<'PY'
 import json,os
