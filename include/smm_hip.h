@@ -140,7 +140,8 @@ int smm_hip_profile_read_waits(double* exposed_ms, long long* pairs, int reset);
  * to the device.  The host arrays stay owned by the caller. */
 int smm_hip_csr_create_f32(int rows, int cols, const int* start, const int* positions, const float* values, smm_hip_csr** out);
 int smm_hip_csr_create_f64(int rows, int cols, const int* start, const int* positions, const double* values, smm_hip_csr** out);
-/* Wraps arrays that already live in device memory (no copy; the caller keeps them alive and unchanged). */
+/* Wraps arrays that already live in device memory (no copy; the caller keeps them alive, and start[] / positions[] unchanged).  The
+ * values may change: through the edit calls below, or written by the caller followed by smm_hip_csr_values_changed_*. */
 int smm_hip_csr_create_dev_f32(int rows, int cols, const int* d_start, const int* d_positions, const float* d_values, smm_hip_csr** out);
 int smm_hip_csr_create_dev_f64(int rows, int cols, const int* d_start, const int* d_positions, const double* d_values, smm_hip_csr** out);
 int smm_hip_csr_destroy(smm_hip_csr* m);
@@ -181,6 +182,72 @@ int smm_hip_set_cg_fuse_p(int on);
 int smm_hip_csr_pattern_allow_const(smm_hip_csr* m, int allow);
 /* Times the candidate SpMV configurations on this matrix and keeps the fastest. */
 int smm_hip_csr_autotune(smm_hip_csr* m);
+
+/* ---- editing the VALUES of a matrix on the device (CSRMatrix<T>::operator*=, inplaceAdd / inplaceSubtract, zeroValues, updateEntry /
+ * addEntry: ref:1525-1604) -------------------------------------------------------------------------------------------------------
+ * The pattern (rows, cols, start[], positions[]) never changes; only values[nnz] does.  What the library derived from the pattern alone
+ * (tile tables, row masks, dictionary codes, the 2.5-D plan, the kernel choice) is kept: the first SpMV after an edit runs no analysis.
+ * What it derived from the values is kept coherent by the edit itself: a matrix in the constant-diagonal encoding (SMM_PATTERN_CONST)
+ * stays in it after scale, zero, and axpy of two such matrices (the k diagonal values are updated exactly, in stream order); any other edit re-verifies
+ * every entry with one device pass (the call then synchronises `stream`) and drops the matrix to SMM_PATTERN_MASKS when a diagonal no
+ * longer holds one value.  A matrix is never promoted back to CONST by an edit (same results either way; only speed differs).
+ *
+ * Cost: scale / zero move nnz * sizeof(T) once (read + write), axpy three times that; update_entries is one pass over the batch plus a
+ * sort of it; set_values is one copy of values[] (host link or HBM) -- positions[] / start[] are never uploaded again.
+ *
+ * Ordering: asynchronous on `stream` (NULL = the null stream) like the `_dev` calls, except where noted.  An edit is a device write
+ * like any other: do not edit a matrix while another thread runs a solve or SpMV on it, and order the streams yourself.  The host-pointer
+ * forms (update_entries, set_values, get_values) run on the library's stream and synchronise before returning.
+ * For a matrix created with smm_hip_csr_create_dev_* these calls WRITE THE CALLER'S d_values array.
+ *
+ * Preconditioners made from the matrix before an edit:
+ *   SGS     reads A's values at every apply: after an edit it applies the EDITED A (bit for bit an SGS created after the edit), as the
+ *           reference's SGSPreconditioner, which holds a reference to A (ref:1185).  Nothing of A's values is kept at create (the
+ *           diagonal is only checked there).
+ *   ILU0, IC0, JACOBI, BLOCK_ILU0, BLOCK_SGS  are snapshots taken at create (the reference's ilu0Val / ic0Val members): their factors
+ *           do not follow the edit -- create a new one to follow it.  The A v half of smm_hip_precond_apply_spmv always uses the
+ *           current A, in the encoding A is in at apply time.
+ * Distributed handles (smm_hip_dist_csr) cannot be edited. */
+#define SMM_UPDATE_SET 0 /* updateEntry (ref:1572-1580): values[k] = v */
+#define SMM_UPDATE_ADD 1 /* addEntry    (ref:1596-1604): values[k] = values[k] + v */
+/* operator*= (ref:1525-1531): values[k] = values[k] * alpha */
+int smm_hip_csr_scale_f32(smm_hip_csr* m, float alpha, smm_hip_stream stream);
+int smm_hip_csr_scale_f64(smm_hip_csr* m, double alpha, smm_hip_stream stream);
+/* values[k] = values[k] + alpha * other.values[k] (two roundings); alpha = 1 / -1 give the bits of inplaceAdd / inplaceSubtract
+ * (ref:1533-1549).  `other` must have the same dtype and pattern (rows, cols, nnz, start[], positions[]), else SMM_HIP_ERR_INVALID and
+ * nothing changes.  The first call for a pair of matrices compares the two patterns on the device (and synchronises `stream`); the verdict
+ * is kept in both handles, so later calls for the same pair compare nothing.  other may be m. */
+int smm_hip_csr_axpy_f32(smm_hip_csr* m, float alpha, const smm_hip_csr* other, smm_hip_stream stream);
+int smm_hip_csr_axpy_f64(smm_hip_csr* m, double alpha, const smm_hip_csr* other, smm_hip_stream stream);
+/* zeroValues (ref:1591-1594): every value +0 */
+int smm_hip_csr_zero_f32(smm_hip_csr* m, smm_hip_stream stream);
+int smm_hip_csr_zero_f64(smm_hip_csr* m, smm_hip_stream stream);
+/* A batch of n entries (rows[i], cols[i], values[i]) applied in ONE device pass, each found by a binary search of its row like
+ * getValueIndex (ref:1551-1570); mode SMM_UPDATE_SET or SMM_UPDATE_ADD.  The result is that of applying the entries one after another in
+ * the order given, bit for bit: duplicates of one entry are summed in order (ADD) or the last one wins (SET).  An entry that is not
+ * stored -- or whose row or column is out of range -- changes nothing and reports 0 in found[i] (found may be NULL; 1 = applied).
+ * Host form: host arrays, synchronous.  _dev form: device arrays (d_found device memory or NULL), asynchronous on `stream`. */
+int smm_hip_csr_update_entries_f32(smm_hip_csr* m, int n, const int* rows, const int* cols, const float* values, int mode, unsigned char* found);
+int smm_hip_csr_update_entries_f64(smm_hip_csr* m, int n, const int* rows, const int* cols, const double* values, int mode, unsigned char* found);
+int smm_hip_csr_update_entries_dev_f32(smm_hip_csr* m, int n, const int* d_rows, const int* d_cols, const float* d_values, int mode, unsigned char* d_found,
+                                       smm_hip_stream stream);
+int smm_hip_csr_update_entries_dev_f64(smm_hip_csr* m, int n, const int* d_rows, const int* d_cols, const double* d_values, int mode, unsigned char* d_found,
+                                       smm_hip_stream stream);
+/* Replace all nnz values: from host memory (synchronous) or device memory (asynchronous on `stream`).  Only values[] is copied. */
+int smm_hip_csr_set_values_f32(smm_hip_csr* m, const float* values);
+int smm_hip_csr_set_values_f64(smm_hip_csr* m, const double* values);
+int smm_hip_csr_set_values_dev_f32(smm_hip_csr* m, const float* d_values, smm_hip_stream stream);
+int smm_hip_csr_set_values_dev_f64(smm_hip_csr* m, const double* d_values, smm_hip_stream stream);
+/* Copy the nnz values to host memory (synchronous). */
+int smm_hip_csr_get_values_f32(const smm_hip_csr* m, float* values);
+int smm_hip_csr_get_values_f64(const smm_hip_csr* m, double* values);
+/* For matrices over caller-owned device arrays (smm_hip_csr_create_dev_*): the caller has written d_values itself (ordered before this
+ * call on `stream`) and announces it; the matrix re-derives its value-dependent state as after any other edit. */
+int smm_hip_csr_values_changed_f32(smm_hip_csr* m, smm_hip_stream stream);
+int smm_hip_csr_values_changed_f64(smm_hip_csr* m, smm_hip_stream stream);
+/* hasSameNonZeroPattern (ref:1366-1385): *same = 1 when rows, cols, nnz, start[] and positions[] are equal.  Synchronous; cached per pair
+ * like smm_hip_csr_axpy_*. */
+int smm_hip_csr_same_pattern(const smm_hip_csr* a, const smm_hip_csr* b, int* same);
 
 /* ---- SpMV: CSRMatrix<T>::rMult / rMultAdd / rMultSub (ref:1458-1515) -------------------------------------- */
 /* out[i] = op(lhs[i], sum_k values[k]*x[positions[k]]); empty rows give op(lhs[i],0) (ref:1479-1483);

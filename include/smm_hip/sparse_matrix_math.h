@@ -2,8 +2,9 @@
 // libsmm_hip.so (include/smm_hip.h).  A program written against vasil-pashov/sparse_matrix_math's
 // include/sparse_matrix_math.h ("ref" below) that only uses
 //
-//     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration /
-//     getPreconditioner), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
+//     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
+//     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
+//     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
 //     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::loadMatrix
 //
 // compiles against this header unchanged and runs those calls on an MI355X: same names, same argument order and meaning,
@@ -19,7 +20,8 @@
 //
 // Written from the documented behaviour of the reference; no reference source is reproduced here.
 // Additions the reference lacks: CSRMatrix::init(rows, cols, start, positions, values) (raw CSR arrays, ref can only be
-// filled through a std::map), JacobiPreconditioner, a working ILU0Preconditioner, Matrix Market `general` matrices.
+// filled through a std::map), JacobiPreconditioner, a working ILU0Preconditioner, Matrix Market `general` matrices, and value edits
+// made ON THE GPU once the matrix has a device mirror (the pattern and everything derived from it are kept: see "Editing the values").
 #pragma once
 
 #include <algorithm>
@@ -33,6 +35,7 @@
 #include <limits>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <sstream>
 #include <string>
 #include <type_traits>
@@ -64,6 +67,11 @@ struct Abi<float> {
 	}
 	static int bicgsym(const smm_hip_csr* a, float* b, float* x, int it, float eps, int* st) { return smm_hip_bicgsymmetric_f32(a, b, x, it, eps, st, nullptr); }
 	static int apply(const smm_hip_precond* M, const float* r, float* x) { return smm_hip_precond_apply_f32(M, r, x); }
+	static int scale(smm_hip_csr* m, float a) { return smm_hip_csr_scale_f32(m, a, nullptr); }
+	static int axpy(smm_hip_csr* m, float a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f32(m, a, o, nullptr); }
+	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f32(m, nullptr); }
+	static int update(smm_hip_csr* m, int n, const int* r, const int* c, const float* v) { return smm_hip_csr_update_entries_f32(m, n, r, c, v, SMM_UPDATE_SET, nullptr); }
+	static int getValues(const smm_hip_csr* m, float* v) { return smm_hip_csr_get_values_f32(m, v); }
 };
 template <>
 struct Abi<double> {
@@ -78,6 +86,11 @@ struct Abi<double> {
 	}
 	static int bicgsym(const smm_hip_csr* a, double* b, double* x, int it, double eps, int* st) { return smm_hip_bicgsymmetric_f64(a, b, x, it, eps, st, nullptr); }
 	static int apply(const smm_hip_precond* M, const double* r, double* x) { return smm_hip_precond_apply_f64(M, r, x); }
+	static int scale(smm_hip_csr* m, double a) { return smm_hip_csr_scale_f64(m, a, nullptr); }
+	static int axpy(smm_hip_csr* m, double a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f64(m, a, o, nullptr); }
+	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f64(m, nullptr); }
+	static int update(smm_hip_csr* m, int n, const int* r, const int* c, const double* v) { return smm_hip_csr_update_entries_f64(m, n, r, c, v, SMM_UPDATE_SET, nullptr); }
+	static int getValues(const smm_hip_csr* m, double* v) { return smm_hip_csr_get_values_f64(m, v); }
 };
 inline int& statusSlot() noexcept {
 	static thread_local int st = SMM_HIP_OK;
@@ -93,6 +106,12 @@ inline int note(int abi) noexcept {
 	}
 #endif
 	return abi;
+}
+// guards the host / device coherence of the matrices' values (CSRMatrix below): const members that refresh the host copy or flush
+// queued entries may run concurrently on one const matrix
+inline std::mutex& editMutex() noexcept {
+	static std::mutex mu;
+	return mu;
 }
 template <typename T>
 inline void fillNaN(T* p, int n) noexcept {
@@ -208,37 +227,77 @@ class CSRMatrix {
 public:
 	using value_type = T;
 
-	class ConstElement {
+	// Iterators (ref:722-1000): `*it` / `it->` give an element with getRow / getCol / getValue, and setValue for the non-const kinds.
+	// Iterator / ConstIterator walk all stored elements in row-major order (`for (const auto& el : m)`), RowIterator / ConstRowIterator
+	// the elements of one row (rowBegin(i) .. rowEnd(i)).  Getting an iterator brings the host copy of the values up to date; setValue
+	// writes it and, when the matrix has a device mirror, queues the entry for the mirror (see "Editing the values" below).
+	template <bool CONST, bool ROW>
+	class IteratorT;
+	template <bool CONST>
+	class Element {
 	public:
-		ConstElement(const CSRMatrix* m, int row, int idx) : m(m), row(row), idx(idx) {}
+		using Matrix = std::conditional_t<CONST, const CSRMatrix, CSRMatrix>;
+		Element(Matrix* m, int row, int idx) : m(m), row(row), idx(idx) {}
 		int getRow() const noexcept { return row; }
 		int getCol() const noexcept { return m->positions[idx]; }
 		T getValue() const noexcept { return m->values[idx]; }
+		template <bool C = CONST, typename = std::enable_if_t<!C>>
+		void setValue(const T v) noexcept {
+			m->setValueAt(row, idx, v);
+		}
 
 	private:
-		const CSRMatrix* m;
+		template <bool, bool>
+		friend class IteratorT;
+		Matrix* m;
 		int row, idx;
 	};
-	// forward iterator over all stored elements in row-major order (what the reference's tests use: `for (const auto& el : m)`)
-	class ConstIterator {
+	template <bool CONST, bool ROW>
+	class IteratorT {
 	public:
-		ConstIterator(const CSRMatrix* m, int row, int idx) : m(m), row(row), idx(idx) { skipEmpty(); }
-		ConstElement operator*() const { return ConstElement(m, row, idx); }
-		ConstIterator& operator++() {
-			++idx;
-			skipEmpty();
+		using Matrix = std::conditional_t<CONST, const CSRMatrix, CSRMatrix>;
+		using value_type = Element<CONST>;
+		using reference = std::conditional_t<CONST, const Element<CONST>&, Element<CONST>&>;
+		using pointer = std::conditional_t<CONST, const Element<CONST>*, Element<CONST>*>;
+		IteratorT(Matrix* m, int row, int idx) : e(m, row, idx) {
+			if (!ROW) skipEmpty();
+		}
+		template <bool C2, typename = std::enable_if_t<CONST || !C2>>
+		IteratorT(const IteratorT<C2, ROW>& o) : e(o.e.m, o.e.row, o.e.idx) {}
+		reference operator*() { return e; }
+		pointer operator->() { return &e; }
+		const Element<CONST>& operator*() const { return e; }
+		const Element<CONST>* operator->() const { return &e; }
+		IteratorT& operator++() {
+			++e.idx;
+			if (ROW) {
+				if (e.idx == e.m->start[e.row + 1]) ++e.row;
+			} else {
+				skipEmpty();
+			}
 			return *this;
 		}
-		bool operator!=(const ConstIterator& o) const { return idx != o.idx; }
-		bool operator==(const ConstIterator& o) const { return idx == o.idx; }
+		IteratorT operator++(int) {
+			IteratorT before = *this;
+			++*this;
+			return before;
+		}
+		bool operator!=(const IteratorT& o) const { return e.idx != o.e.idx || e.m != o.e.m; }
+		bool operator==(const IteratorT& o) const { return !(*this != o); }
 
 	private:
+		template <bool, bool>
+		friend class IteratorT;
 		void skipEmpty() {
-			while (row < m->denseRowCount && idx >= m->start[row + 1]) ++row;
+			while (e.row < e.m->denseRowCount && e.idx >= e.m->start[e.row + 1]) ++e.row;
 		}
-		const CSRMatrix* m;
-		int row, idx;
+		Element<CONST> e;
 	};
+	using ConstElement = Element<true>;
+	using Iterator = IteratorT<false, false>;
+	using ConstIterator = IteratorT<true, false>;
+	using RowIterator = IteratorT<false, true>;
+	using ConstRowIterator = IteratorT<true, true>;
 
 	// Every preconditioner wraps a device-side smm_hip_precond; `int apply(const T* rhs, T* x) const` as in ref:1173-1235.
 	class PreconditionerBase {
@@ -248,10 +307,12 @@ public:
 		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h) { o.h = nullptr; }
 		~PreconditionerBase() { smm_hip_precond_destroy(h); }
 		// non-zero on structural failure (missing / tiny diagonal, empty row, non-SPD pivot), like ref:1668-1693
+		// (every init / apply / handle goes through m->device(): entries queued by updateEntry / addEntry / setValue reach the matrix's
+		// mirror before the preconditioner is made or applied -- SGS reads A's values at every apply)
 		int init() const noexcept {
-			if (h) return 0;
 			const smm_hip_csr* dev = m->device();
 			if (!dev) return 1;
+			if (h) return 0;
 			return detail::note(smm_hip_precond_create(dev, kind, &h)) == SMM_HIP_OK ? 0 : 1;
 		}
 		int apply(const T* rhs, T* x) const noexcept {
@@ -321,7 +382,10 @@ public:
 		denseColCount = o.denseColCount;
 		firstActiveStart = o.firstActiveStart;
 		dev = o.dev;
+		hostStale = o.hostStale;
+		queued = std::move(o.queued);
 		o.dev = nullptr;
+		o.hostStale = false;
 		return *this;
 	}
 	~CSRMatrix() { release(); }
@@ -364,13 +428,81 @@ public:
 	int getNonZeroCount() const noexcept { return start ? start[denseRowCount] : 0; }
 	int getDenseRowCount() const noexcept { return denseRowCount; }
 	int getDenseColCount() const noexcept { return denseColCount; }
-	ConstIterator begin() const noexcept { return ConstIterator(this, 0, 0); }
-	ConstIterator end() const noexcept { return ConstIterator(this, denseRowCount, getNonZeroCount()); }
+	Iterator begin() noexcept {
+		refreshHost();
+		return Iterator(this, 0, 0);
+	}
+	Iterator end() noexcept { return Iterator(this, denseRowCount, getNonZeroCount()); }
+	ConstIterator begin() const noexcept { return cbegin(); }
+	ConstIterator end() const noexcept { return cend(); }
+	ConstIterator cbegin() const noexcept {
+		refreshHost();
+		return ConstIterator(this, 0, 0);
+	}
+	ConstIterator cend() const noexcept { return ConstIterator(this, denseRowCount, getNonZeroCount()); }
+	// ref:1428-1456: rowEnd(i) of an empty row is rowBegin(i)
+	RowIterator rowBegin(const int i) noexcept {
+		refreshHost();
+		return RowIterator(this, i, start[i]);
+	}
+	RowIterator rowEnd(const int i) noexcept { return start[i] == start[i + 1] ? rowBegin(i) : RowIterator(this, i + 1, start[i + 1]); }
+	ConstRowIterator rowBegin(const int i) const noexcept { return crowBegin(i); }
+	ConstRowIterator rowEnd(const int i) const noexcept { return crowEnd(i); }
+	ConstRowIterator crowBegin(const int i) const noexcept {
+		refreshHost();
+		return ConstRowIterator(this, i, start[i]);
+	}
+	ConstRowIterator crowEnd(const int i) const noexcept { return start[i] == start[i + 1] ? crowBegin(i) : ConstRowIterator(this, i + 1, start[i + 1]); }
 	T getValue(int row, int col) const noexcept {
-		const int* b = positions.get() + start[row];
-		const int* e = positions.get() + start[row + 1];
-		const int* it = std::lower_bound(b, e, col);
-		return it != e && *it == col ? values[it - positions.get()] : T(0);
+		const int k = indexOf(row, col);
+		if (k < 0) return T(0);
+		refreshHost();
+		return values[k];
+	}
+
+	// ---- Editing the values (ref:1366-1385, 1525-1604); the pattern never changes ----
+	// No device mirror yet: the edit is made on the host only, as in the reference (no GPU needed).  With a mirror (any hot-path call made
+	// one): operator*=, inplaceAdd / inplaceSubtract and zeroValues run on the GPU (libsmm_hip.so) and leave the host copy stale -- the next
+	// host read (getValue, iterators, rawValues, or inplaceAdd reading `other`) refreshes it with one device-to-host copy; updateEntry /
+	// addEntry / setValue write the host copy and queue the entry, and the queue goes to the GPU as ONE batched update before the next
+	// hot-path call (rMult*, the solvers, device(), a preconditioner's init / apply).  Preconditioners made before an edit: SGS applies
+	// the edited A, ILU0 / IC0 / JACOBI / BLOCK_* keep their factors (smm_hip.h).  Not while another thread uses the matrix.
+	bool hasSameNonZeroPattern(const CSRMatrix& other) const noexcept {
+		if (denseRowCount != other.denseRowCount || denseColCount != other.denseColCount) return false;
+		const int nnz = getNonZeroCount();
+		if (nnz != other.getNonZeroCount()) return false;
+		if (nnz == 0) return true;
+		return std::equal(start.get(), start.get() + denseRowCount + 1, other.start.get()) && std::equal(positions.get(), positions.get() + nnz, other.positions.get());
+	}
+	void operator*=(const T scalar) {
+		if (!flushedMirror()) {
+			const int nnz = getNonZeroCount();
+			for (int i = 0; i < nnz; ++i) values[i] *= scalar;
+			return;
+		}
+		deviceEdited(detail::Abi<T>::scale(dev, scalar));
+	}
+	void inplaceAdd(const CSRMatrix& other) { addScaled(other, T(1)); }
+	void inplaceSubtract(const CSRMatrix& other) { addScaled(other, T(-1)); }
+	bool updateEntry(const int row, const int col, const T newValue) {
+		const int k = indexOf(row, col);
+		if (k < 0) return false;
+		setValueAt(row, k, newValue);
+		return true;
+	}
+	bool addEntry(const int row, const int col, const T value) {
+		const int k = indexOf(row, col);
+		if (k < 0) return false;
+		refreshHost();
+		setValueAt(row, k, values[k] + value);
+		return true;
+	}
+	void zeroValues() {
+		if (!flushedMirror()) {
+			std::fill_n(values.get(), getNonZeroCount(), T(0));
+			return;
+		}
+		deviceEdited(detail::Abi<T>::zero(dev));
 	}
 
 	// ---- the hot path: out = op(lhs, A * mult) on the GPU (ref:1458-1515) ----
@@ -404,10 +536,14 @@ public:
 	}
 
 	// device mirror of the three arrays, created on first use; nullptr when there is no GPU
+	// (entries queued by updateEntry / addEntry / setValue are sent first, as one batched update)
 	const smm_hip_csr* device() const noexcept {
+		std::lock_guard<std::mutex> lock(detail::editMutex());
 		if (!dev && start) {
 			if (detail::note(detail::Abi<T>::create(denseRowCount, denseColCount, start.get(), positions.get(), values.get(), &dev)) != SMM_HIP_OK) dev = nullptr;
+			queued.clear();
 		}
+		if (dev && !queued.empty()) flushLocked();
 		return dev;
 	}
 	// Tuning only (results unchanged): SpMV kernel family and lanes per row for this matrix, e.g. SMM_SPMV_PATTERN for stencil /
@@ -418,10 +554,16 @@ public:
 	}
 	// call after editing values/positions in place through the raw accessors below
 	void invalidateDevice() noexcept {
+		refreshHost();  // (a device-side edit not yet copied back would be lost with the mirror)
 		smm_hip_csr_destroy(dev);
 		dev = nullptr;
+		hostStale = false;
+		queued.clear();
 	}
-	const T* rawValues() const noexcept { return values.get(); }
+	const T* rawValues() const noexcept {
+		refreshHost();
+		return values.get();
+	}
 	const int* rawPositions() const noexcept { return positions.get(); }
 	const int* rawStart() const noexcept { return start.get(); }
 
@@ -442,7 +584,69 @@ private:
 	void release() noexcept {
 		smm_hip_csr_destroy(dev);
 		dev = nullptr;
+		hostStale = false;
+		queued.clear();
 	}
+	int indexOf(int row, int col) const noexcept {  // ref:1551-1570 (out-of-range: not stored)
+		if (!start || row < 0 || row >= denseRowCount || col < 0 || col >= denseColCount) return -1;
+		const int* b = positions.get() + start[row];
+		const int* e = positions.get() + start[row + 1];
+		const int* it = std::lower_bound(b, e, col);
+		return it != e && *it == col ? static_cast<int>(it - positions.get()) : -1;
+	}
+	// the host copy after a device-side bulk edit: one device-to-host copy
+	void refreshHost() const noexcept {
+		std::lock_guard<std::mutex> lock(detail::editMutex());
+		if (!hostStale || !dev) return;
+		if (detail::note(detail::Abi<T>::getValues(dev, values.get())) == SMM_HIP_OK) hostStale = false;
+	}
+	void setValueAt(int row, int k, T v) {
+		refreshHost();
+		values[k] = v;
+		std::lock_guard<std::mutex> lock(detail::editMutex());
+		if (dev) queued.push_back({row, positions[k], v});
+	}
+	// the mirror, with every queued entry on it; false when there is none (the edit stays on the host)
+	bool flushedMirror() {
+		std::lock_guard<std::mutex> lock(detail::editMutex());
+		if (!dev) return false;
+		if (!queued.empty()) flushLocked();
+		return true;
+	}
+	void flushLocked() const noexcept {
+		std::vector<int> r(queued.size()), c(queued.size());
+		std::vector<T> v(queued.size());
+		for (size_t i = 0; i < queued.size(); ++i) {
+			r[i] = queued[i].row;
+			c[i] = queued[i].col;
+			v[i] = queued[i].value;
+		}
+		if (detail::note(detail::Abi<T>::update(dev, static_cast<int>(r.size()), r.data(), c.data(), v.data())) == SMM_HIP_OK) queued.clear();
+	}
+	void addScaled(const CSRMatrix& other, T alpha) {
+		if (flushedMirror()) {
+			const smm_hip_csr* o = other.device();  // (a failed mirror has noted its status; a matrix never initialised has none)
+			deviceEdited(o ? detail::Abi<T>::axpy(dev, alpha, o) : (other.start ? lastHipStatus() : SMM_HIP_ERR_INVALID));
+			return;
+		}
+		other.refreshHost();
+		const int nnz = getNonZeroCount();
+		for (int i = 0; i < nnz; ++i) values[i] = alpha == T(1) ? values[i] + other.values[i] : values[i] - other.values[i];
+	}
+	// after a device-side bulk edit: the host copy is stale once the edit has run (a failed call leaves the device values, and so the
+	// host copy, as they were; its status is in lastHipStatus())
+	void deviceEdited(int abi) {
+		if (detail::note(abi) != SMM_HIP_OK) return;
+		{
+			std::lock_guard<std::mutex> lock(detail::editMutex());
+			hostStale = true;
+		}
+		detail::note(smm_hip_stream_synchronize(nullptr));
+	}
+	struct Queued {
+		int row, col;
+		T value;
+	};
 	// the reference's layout (ref:1243-1259)
 	std::unique_ptr<T[]> values;
 	std::unique_ptr<int[]> positions;
@@ -451,6 +655,8 @@ private:
 	int denseColCount = 0;
 	int firstActiveStart = 0;
 	mutable smm_hip_csr* dev = nullptr;
+	mutable bool hostStale = false;      // a device-side bulk edit has not been copied back yet
+	mutable std::vector<Queued> queued;  // single-entry edits not yet sent to the mirror
 };
 
 // ---- solvers ---------------------------------------------------------------------------------------------------------------

@@ -72,6 +72,15 @@ _TYPED = {
     "smm_hip_dist_spmv_dev": (c_int, [_P, c_int, _P, _P, _P, _P]),
     "smm_hip_dist_bicgstab_dev": (c_int, [_P, _P, _P, c_int, "T", _P, _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_dist_cg_dev": (c_int, [_P, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_csr_scale": (c_int, [_P, "T", _P]),
+    "smm_hip_csr_axpy": (c_int, [_P, "T", _P, _P]),
+    "smm_hip_csr_zero": (c_int, [_P, _P]),
+    "smm_hip_csr_update_entries": (c_int, [_P, c_int, _P, _P, _P, c_int, _P]),
+    "smm_hip_csr_update_entries_dev": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, _P]),
+    "smm_hip_csr_set_values": (c_int, [_P, _P]),
+    "smm_hip_csr_set_values_dev": (c_int, [_P, _P, _P]),
+    "smm_hip_csr_get_values": (c_int, [_P, _P]),
+    "smm_hip_csr_values_changed": (c_int, [_P, _P]),
 }
 
 
@@ -99,6 +108,7 @@ _PLAIN = {
     "smm_hip_set_cg_lazy_x_min_bytes": (c_int, [c_longlong]),
     "smm_hip_set_cg_fuse_p": (c_int, [c_int]),
     "smm_hip_csr_pattern_allow_const": (c_int, [_P, c_int]),
+    "smm_hip_csr_same_pattern": (c_int, [_P, _P, POINTER(c_int)]),
     "smm_hip_precond_create": (c_int, [_P, c_int, POINTER(_P)]),
     "smm_hip_precond_create_block": (c_int, [_P, c_int, c_int, POINTER(_P)]),
     "smm_hip_precond_create_block_capped": (c_int, [_P, c_int, c_int, c_int, POINTER(_P)]),

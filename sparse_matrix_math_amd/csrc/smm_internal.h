@@ -197,6 +197,11 @@ struct smm_hip_csr {
 	// multiples of that) holds -- its fixed row tiles are staged whole, so their LDS is sized from this; -1: not counted yet (under tileMutex)
 	int split_tile_max[3] = {-1, -1, -1};
 	bool split_uneven = false;  // one contiguous eighth of the rows holds more than 1.5 x its share of the entries (counted with the above)
+	// values edited on the device (smm_csr_update.hip): a number of the handle's own for the pattern-comparison cache (0: none drawn yet) and
+	// the handles whose pattern was already compared with this one's (uid, same), under editMutex
+	std::atomic<unsigned long long> uid{0};
+	std::mutex editMutex;
+	std::vector<std::pair<unsigned long long, bool>> patternSeen;
 };
 
 struct smm_hip_precond {
@@ -296,6 +301,8 @@ int patternLanesFor(const smm_hip_csr* m);
 // the PATTERN kernel launchPat picks for `lanes` and the bytes one launch moves (smm_hip_csr_kernel_desc)
 const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes);
 void planMarch(smm_hip_csr* m);
+// values edited (smm_csr_update.hip): rewrite the single-launch BiCGStab's slot-major copy of the values (smm_resident_bicg.hip; asynchronous)
+int refreshResEll(smm_hip_csr* a, hipStream_t s);
 int marchBuildMasks32(smm_hip_csr* m, hipStream_t s);
 // Launch plumbing of the persistent SpMV kernels (per template instantiation: `slot` / `granted` are statics of the launcher).
 // occupancyCached: workgroups per CU of `kernel` at `lds` bytes of dynamic LDS, asked from the runtime once per LDS size -- the query costs

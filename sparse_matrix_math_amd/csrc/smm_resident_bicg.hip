@@ -514,6 +514,21 @@ void preloadBicgResidentUnit() {
 	(void)hipGetLastError();
 }
 
+// values edited (smm_csr_update.hip): the slot-major copy is rewritten in place, on the edit's stream
+int refreshResEll(smm_hip_csr* a, hipStream_t s) {
+	if (!a->d_res_ell || !a->d_pat_masks || a->rows <= 0) return SMM_HIP_OK;
+	const int n = a->rows, k = a->pat_k;
+	if (a->dtype == SMM_DTYPE_F32) {
+		ellFromMasksKernel<float><<<std::min(4096, (n + 255) / 256), 256, 0, s>>>(n, k, a->d_start, a->d_pat_masks, static_cast<const float*>(a->d_values),
+		                                                                         static_cast<float*>(a->d_res_ell));
+	} else {
+		ellFromMasksKernel<double><<<std::min(4096, (n + 255) / 256), 256, 0, s>>>(n, k, a->d_start, a->d_pat_masks, static_cast<const double*>(a->d_values),
+		                                                                          static_cast<double*>(a->d_res_ell));
+	}
+	SMM_HIP_TRY(hipGetLastError());
+	return SMM_HIP_OK;
+}
+
 template int bicgstabResidentTry<float>(const smm_hip_csr*, const float*, float*, int, float, const float*, hipStream_t, int*, int*, float*, bool*);
 template int bicgstabResidentTry<double>(const smm_hip_csr*, const double*, double*, int, double, const double*, hipStream_t, int*, int*, double*, bool*);
 

@@ -324,6 +324,88 @@ class CSRMatrix:
         """False: a matrix with constant diagonals keeps reading values[] (measurements); same bits either way"""
         check(_lib.load().smm_hip_csr_pattern_allow_const(self._h, 1 if allow else 0))
 
+    # ---- editing the values on the device (the pattern stays; smm_hip.h "editing the VALUES of a matrix") ----
+    # The reference's names (ref:1525-1604) return once the edit is done on the GPU; the batch / bulk forms below take an optional
+    # stream and are then only enqueued on it.  Preconditioners made before an edit: SGS follows it, the other kinds are snapshots.
+    def _edited(self, stream):
+        if stream is None:
+            synchronize(None)
+
+    def scale(self, alpha, stream=None):
+        check(_fn("smm_hip_csr_scale", self._suf)(self._h, float(alpha), _dptr(stream)))
+        self._edited(stream)
+
+    def axpy(self, alpha, other, stream=None):
+        """values += alpha * other.values (same pattern and dtype, else SmmHipError with SMM_HIP_ERR_INVALID and nothing changed)"""
+        check(_fn("smm_hip_csr_axpy", self._suf)(self._h, float(alpha), other._h, _dptr(stream)))
+        self._edited(stream)
+
+    def zero(self, stream=None):
+        check(_fn("smm_hip_csr_zero", self._suf)(self._h, _dptr(stream)))
+        self._edited(stream)
+
+    def __imul__(self, alpha):  # ref:1525-1531
+        self.scale(alpha)
+        return self
+
+    def inplaceAdd(self, other):  # ref:1533-1540
+        self.axpy(1.0, other)
+
+    def inplaceSubtract(self, other):  # ref:1542-1549
+        self.axpy(-1.0, other)
+
+    def zeroValues(self):  # ref:1591-1594
+        self.zero()
+
+    def hasSameNonZeroPattern(self, other):  # ref:1366-1385
+        same = ctypes.c_int()
+        check(_lib.load().smm_hip_csr_same_pattern(self._h, other._h, ctypes.byref(same)))
+        return bool(same.value)
+
+    def update_entries(self, rows, cols, vals, add=False):
+        """Apply (rows[i], cols[i], vals[i]) in one device pass as if one after another (SET, or ADD with add=True); returns the bool
+        mask of the entries that are stored (the others changed nothing)"""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        vals = np.ascontiguousarray(vals, dtype=self.dtype)
+        n = rows.size
+        if cols.size != n or vals.size != n:
+            raise ValueError("rows, cols and vals must have the same length")
+        found = np.zeros(n, dtype=np.uint8)
+        check(_fn("smm_hip_csr_update_entries", self._suf)(self._h, n, _host(rows, np.int32, "rows"), _host(cols, np.int32, "cols"), _host(vals, self.dtype, "vals"),
+                                                          1 if add else 0, _host(found, np.uint8, "found")))
+        return found.astype(bool)
+
+    def update_entries_dev(self, n, d_rows, d_cols, d_vals, add=False, d_found=None, stream=None):
+        check(_fn("smm_hip_csr_update_entries_dev", self._suf)(self._h, int(n), _dptr(d_rows), _dptr(d_cols), _dptr(d_vals), 1 if add else 0, _dptr(d_found),
+                                                              _dptr(stream)))
+        self._edited(stream)
+
+    def updateEntry(self, row, col, value):  # ref:1572-1580
+        return bool(self.update_entries([row], [col], [value])[0])
+
+    def addEntry(self, row, col, value):  # ref:1596-1604
+        return bool(self.update_entries([row], [col], [value], add=True)[0])
+
+    def set_values(self, values):
+        """replace all nnz values from a host array (only values[] is uploaded)"""
+        values = np.ascontiguousarray(values, dtype=self.dtype)
+        check(_fn("smm_hip_csr_set_values", self._suf)(self._h, _host(values, self.dtype, "values", self.nnz)))
+
+    def set_values_dev(self, d_values, stream=None):
+        check(_fn("smm_hip_csr_set_values_dev", self._suf)(self._h, _dptr(d_values), _dptr(stream)))
+        self._edited(stream)
+
+    def get_values(self):
+        out = np.empty(self.nnz, dtype=self.dtype)
+        check(_fn("smm_hip_csr_get_values", self._suf)(self._h, _host(out, self.dtype, "out")))
+        return out
+
+    def values_changed(self, stream=None):
+        """from_device matrices: the caller has written d_values itself (ordered before this call on `stream`)"""
+        check(_fn("smm_hip_csr_values_changed", self._suf)(self._h, _dptr(stream)))
+        self._edited(stream)
+
     def spmv_fused_dev(self, op, d_lhs, d_x, d_out, dot_mode, d_w1, d_partials, stream=None, finish=False):
         """SpMV with the dot products of the fresh out[] in its epilogue (dot_mode 1: out.w1; 2: out.out and out.w1).  finish=False:
         d_partials receives 2 x partials_count() per-workgroup sums; finish=True: d_partials is a finishing buffer of finish_len()
