@@ -180,6 +180,11 @@ int smm_hip_set_cg_fuse_p(int on);
 /* allow = 0: a matrix with constant diagonals keeps reading values[] (the MASKS kernels); 1 (default): CONST where it applies.  For
  * measurements of one against the other; the results are the same bits either way. */
 int smm_hip_csr_pattern_allow_const(smm_hip_csr* m, int allow);
+/* The PATTERN family's slots kernel (row masks with values read, 2 or 4 lanes per row: the values of every 64-row wave whose rows hold the
+ * same offsets copied once, wave by wave, at about nnz * sizeof(value) bytes of device memory).  mode -1 (default): AUTO -- where the
+ * library adopted the family by itself, >= 99 % of the waves qualify and the copy fits (SMM_HIP_PATTERN_SLOTS=0|1 turns it off / forces it);
+ * 0: off; 1: wherever it applies; 2: AUTO's rules also on a kernel set with smm_hip_csr_set_kernel.  Same bits as the tile kernel. */
+int smm_hip_csr_pattern_slots(smm_hip_csr* m, int mode);
 /* Times the candidate SpMV configurations on this matrix and keeps the fastest. */
 int smm_hip_csr_autotune(smm_hip_csr* m);
 

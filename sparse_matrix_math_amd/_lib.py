@@ -108,6 +108,7 @@ _PLAIN = {
     "smm_hip_set_cg_lazy_x_min_bytes": (c_int, [c_longlong]),
     "smm_hip_set_cg_fuse_p": (c_int, [c_int]),
     "smm_hip_csr_pattern_allow_const": (c_int, [_P, c_int]),
+    "smm_hip_csr_pattern_slots": (c_int, [_P, c_int]),
     "smm_hip_csr_same_pattern": (c_int, [_P, _P, POINTER(c_int)]),
     "smm_hip_precond_create": (c_int, [_P, c_int, POINTER(_P)]),
     "smm_hip_precond_create_block": (c_int, [_P, c_int, c_int, POINTER(_P)]),

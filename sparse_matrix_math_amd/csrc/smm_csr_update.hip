@@ -7,7 +7,8 @@
 //     diagonal values exactly and in stream order (cvalUpdateKernel) (every entry of a diagonal holds the same bits, so the per-entry result is the per-diagonal one); any
 //     other edit re-verifies every entry (reverifyConst) and drops the handle to the mask encoding with values read when a diagonal
 //     is no longer constant.  A handle that was not constant is never promoted (same bits either way: a question of speed only);
-//   * the single-launch BiCGStab's slot-major copy of the values (d_res_ell) is rewritten in place.
+//   * the single-launch BiCGStab's slot-major copy of the values (d_res_ell) and the PATTERN slots kernel's wave-sliced copy
+//     (d_pat_slots, smm_spmv_slots.hip) are rewritten in place.
 // Preconditioners: SGS reads A's values at every apply; ILU0 / IC0 / JACOBI / BLOCK_* hold factors computed at create (snapshots).
 #include <algorithm>
 #include <cstring>
@@ -327,6 +328,7 @@ int valuesEdited(smm_hip_csr* m, hipStream_t s, int edit, T alpha, const smm_hip
 			SMM_TRY(reverifyConst(m, s));
 		}
 	}
+	SMM_TRY(refreshPatternSlots(m, s));
 	return refreshResEll(m, s);
 }
 

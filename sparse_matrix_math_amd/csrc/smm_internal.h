@@ -175,6 +175,14 @@ struct smm_hip_csr {
 	std::vector<unsigned long long> pat_cval_host;  // the same raw bits on the host (the single-launch BiCGStab passes them as kernel arguments)
 	void* d_res_ell = nullptr;  // MASKS with varying diagonals: values by offset slot, [pat_k][rows], built on first use by smm_resident_bicg.hip (under tileMutex)
 	bool pat_const_off = false;  // smm_hip_csr_pattern_allow_const(m, 0): keep reading values[] (A/B measurements)
+	// MASKS with values read, 2 or 4 lanes per row: the values of every UNIFORM 64-row wave (all rows hold the same offsets) copied wave by
+	// wave, [slot][lane] inside a wave's block, for spmvPatternSlotsKernel (smm_spmv_slots.hip).  Built on first use under tileMutex.
+	void* d_pat_slots = nullptr;
+	long long* d_pat_slot_base = nullptr;  // per wave: element index of its block in d_pat_slots, -1 for a wave read from CSR
+	int pat_slots_state = 0;               // 0 not tried, 1 built, -1 refused (too few uniform waves, or no memory)
+	int pat_slots_mode = -1;               // smm_hip_csr_pattern_slots: -1 AUTO (SMM_HIP_PATTERN_SLOTS), 0 off, 1 forced, 2 AUTO's rules on a set kernel
+	long long pat_slots_elems = 0;         // slots copied (the entries of the uniform waves)
+	int pat_slots_waves = 0, pat_slots_uniform = 0;
 	int pat_max_off = 0;  // largest |column - row| of the offset list
 	// CONST on grid-shaped matrices: the plan of the 2.5-D kernel (smm_spmv_march.hip), made once at the end of the CONST analysis
 	bool march_ok = false;
@@ -303,6 +311,13 @@ const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes)
 void planMarch(smm_hip_csr* m);
 // values edited (smm_csr_update.hip): rewrite the single-launch BiCGStab's slot-major copy of the values (smm_resident_bicg.hip; asynchronous)
 int refreshResEll(smm_hip_csr* a, hipStream_t s);
+// the wave-sliced value copy of the PATTERN slots kernel (smm_spmv_slots.hip).  ensurePatternSlots: build it if this launch would use it
+// (caller holds tileMutex; false: stay on the tile kernel); refreshPatternSlots: rewrite it in place after an edit (asynchronous, under
+// tileMutex); patternSlotsChosen / patternSlotsBytes: the launch's choice and its bytes, for smm_hip_csr_kernel_desc
+bool ensurePatternSlots(smm_hip_csr* m, int lanes, hipStream_t s);
+bool patternSlotsChosen(const smm_hip_csr* m, int lanes);
+long long patternSlotsBytes(const smm_hip_csr* m);
+int refreshPatternSlots(smm_hip_csr* m, hipStream_t s);
 int marchBuildMasks32(smm_hip_csr* m, hipStream_t s);
 // Launch plumbing of the persistent SpMV kernels (per template instantiation: `slot` / `granted` are statics of the launcher).
 // occupancyCached: workgroups per CU of `kernel` at `lds` bytes of dynamic LDS, asked from the runtime once per LDS size -- the query costs
@@ -357,6 +372,9 @@ bool launchPatMasksMarch(const smm_hip_csr* m, int op, const T* lhs, const T* di
 template <typename T>
 bool launchPatConstMarch(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                          const int* doneFlag, hipStream_t s);
+template <typename T>
+void launchPatSlots(const smm_hip_csr* m, int lanes, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
+                    const int* doneFlag, hipStream_t s);
 template <typename T>
 int launchSpmvPattern(const smm_hip_csr* m, int lanes, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                       const int* doneFlag, hipStream_t s);

@@ -758,6 +758,8 @@ int smm_hip_csr_destroy(smm_hip_csr* m) {
 	devFree(m->d_pat_codes);
 	devFree(m->d_pat_cval);
 	devFree(m->d_res_ell);
+	devFree(m->d_pat_slots);
+	devFree(m->d_pat_slot_base);
 	devFree(m->d_pat_masks32);
 	devFree(m->d_pat_masks8);
 	devFree(m->d_pat_rowblocks);

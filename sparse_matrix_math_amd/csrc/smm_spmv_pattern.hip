@@ -1672,7 +1672,13 @@ const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes)
 		}();
 		if (waveEnv != 0 && m->pat_k <= 16) return "spmvPatternWaveKernel";
 	}
-	if ((L == 2 || L == 4) && patUseTile(L)) return "spmvPatternTileKernel";
+	if ((L == 2 || L == 4) && patUseTile(L)) {
+		if (patternSlotsChosen(m, L)) {  // (smm_spmv_slots.hip: the copy was built by an earlier launch)
+			*bytes = patternSlotsBytes(m);
+			return "spmvPatternSlotsKernel";
+		}
+		return "spmvPatternTileKernel";
+	}
 	return "spmvPatternKernel";
 }
 
@@ -1709,12 +1715,19 @@ int launchSpmvPattern(const smm_hip_csr* m, int lanes, int op, const T* lhs, con
 	const int L = std::min(lanes, WAVE);
 	const int capNnz = patCap<T>(m, L) - 3;
 	const int maxRows = TPB / L;
+	bool slots = false;
 	if (patNeedsTiles(m, L)) {  // (the one-lane kernels of stencil shape -- gather, wave, march -- walk rows, not tiles)
 		std::lock_guard<std::mutex> lock(mm->tileMutex);
 		if (!m->d_pat_rowblocks || m->pat_nnz_cap != capNnz || m->pat_max_rows != maxRows) {
 			SetupTrace trace("pattern: tile table");
 			SMM_TRY(buildPatternTiles(mm, capNnz, maxRows, s));
 		}
+		slots = ensurePatternSlots(mm, L, s);  // where the tile kernel would run: the wave-sliced value copy (smm_spmv_slots.hip)
+	}
+	if (slots) {
+		launchPatSlots<T>(m, L, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s);
+		SMM_HIP_TRY(hipGetLastError());
+		return SMM_HIP_OK;
 	}
 	switch (L) {
 	case 1: launchPat<T, 1>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s); break;

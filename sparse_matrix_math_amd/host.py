@@ -324,6 +324,11 @@ class CSRMatrix:
         """False: a matrix with constant diagonals keeps reading values[] (measurements); same bits either way"""
         check(_lib.load().smm_hip_csr_pattern_allow_const(self._h, 1 if allow else 0))
 
+    def pattern_slots(self, mode):
+        """the PATTERN slots kernel: -1 AUTO (default), 0 off, 1 wherever it applies, 2 AUTO's rules also on a kernel set with set_kernel;
+        same bits as the tile kernel"""
+        check(_lib.load().smm_hip_csr_pattern_slots(self._h, int(mode)))
+
     # ---- editing the values on the device (the pattern stays; smm_hip.h "editing the VALUES of a matrix") ----
     # The reference's names (ref:1525-1604) return once the edit is done on the GPU; the batch / bulk forms below take an optional
     # stream and are then only enqueued on it.  Preconditioners made before an edit: SGS follows it, the other kinds are snapshots.
