@@ -183,8 +183,15 @@ int smm_hip_csr_pattern_allow_const(smm_hip_csr* m, int allow);
 /* The PATTERN family's slots kernel (row masks with values read, 2 or 4 lanes per row: the values of every 64-row wave whose rows hold the
  * same offsets copied once, wave by wave, at about nnz * sizeof(value) bytes of device memory).  mode -1 (default): AUTO -- where the
  * library adopted the family by itself, >= 99 % of the waves qualify and the copy fits (SMM_HIP_PATTERN_SLOTS=0|1 turns it off / forces it);
- * 0: off; 1: wherever it applies; 2: AUTO's rules also on a kernel set with smm_hip_csr_set_kernel.  Same bits as the tile kernel. */
+ * 0: off; 1: wherever it applies; 2: AUTO's rules also on a kernel set with smm_hip_csr_set_kernel; 3: wherever it applies, and the copy
+ * walked by the sweep kernel (offset-major, up to 32 x 64 rows per wave held in registers, so that x stays in the L2 between two offsets;
+ * SMM_HIP_PATTERN_SLOTS=3 is the same per process).  AUTO and mode 2 take the sweep kernel by themselves where it was measured to win:
+ * fp32, from about 9.4 M rows, offsets spanning more than a row-by-row walk keeps cached.  Same bits as the tile kernel in every mode. */
 int smm_hip_csr_pattern_slots(smm_hip_csr* m, int mode);
+/* Test / measurement knob: how many 64-row waves a hardware wave of the sweep kernel holds open (8, 16 or 32; 0 restores the default,
+ * SMM_HIP_PATTERN_SWEEP_ROWS in the environment).  Same bits at every setting.  SMM_HIP_PATTERN_SWEEP_WGS=1..8 in the environment (read
+ * once per process) is the other lab knob: workgroups of that kernel per CU, default 3 or as many as the variant's registers allow. */
+int smm_hip_set_pattern_sweep_rows(int rows_open);
 /* Times the candidate SpMV configurations on this matrix and keeps the fastest. */
 int smm_hip_csr_autotune(smm_hip_csr* m);
 

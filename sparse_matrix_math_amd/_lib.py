@@ -109,6 +109,7 @@ _PLAIN = {
     "smm_hip_set_cg_fuse_p": (c_int, [c_int]),
     "smm_hip_csr_pattern_allow_const": (c_int, [_P, c_int]),
     "smm_hip_csr_pattern_slots": (c_int, [_P, c_int]),
+    "smm_hip_set_pattern_sweep_rows": (c_int, [c_int]),
     "smm_hip_csr_same_pattern": (c_int, [_P, _P, POINTER(c_int)]),
     "smm_hip_precond_create": (c_int, [_P, c_int, POINTER(_P)]),
     "smm_hip_precond_create_block": (c_int, [_P, c_int, c_int, POINTER(_P)]),

@@ -180,7 +180,7 @@ struct smm_hip_csr {
 	void* d_pat_slots = nullptr;
 	long long* d_pat_slot_base = nullptr;  // per wave: element index of its block in d_pat_slots, -1 for a wave read from CSR
 	int pat_slots_state = 0;               // 0 not tried, 1 built, -1 refused (too few uniform waves, or no memory)
-	int pat_slots_mode = -1;               // smm_hip_csr_pattern_slots: -1 AUTO (SMM_HIP_PATTERN_SLOTS), 0 off, 1 forced, 2 AUTO's rules on a set kernel
+	int pat_slots_mode = -1;               // smm_hip_csr_pattern_slots: -1 AUTO (SMM_HIP_PATTERN_SLOTS), 0 off, 1 forced, 2 AUTO's rules on a set kernel, 3 forced + sweep kernel
 	long long pat_slots_elems = 0;         // slots copied (the entries of the uniform waves)
 	int pat_slots_waves = 0, pat_slots_uniform = 0;
 	int pat_max_off = 0;  // largest |column - row| of the offset list
@@ -318,6 +318,11 @@ bool ensurePatternSlots(smm_hip_csr* m, int lanes, hipStream_t s);
 bool patternSlotsChosen(const smm_hip_csr* m, int lanes);
 long long patternSlotsBytes(const smm_hip_csr* m);
 int refreshPatternSlots(smm_hip_csr* m, hipStream_t s);
+// the sweep kernel on the same copy (smm_spmv_sweep.hip): patternSweepRows -- 0: the slots kernel runs, else the 64-row waves a hardware
+// wave holds open (8, 16, 32); patternSweepGroupWaves -- the waves one XCD group holds open at that setting (one full super-block), at the
+// workgroups per CU that variant's launch gets
+int patternSweepRows(const smm_hip_csr* m, int lanes);
+int patternSweepGroupWaves(const smm_hip_csr* m, int lanes, int rowsOpen);
 int marchBuildMasks32(smm_hip_csr* m, hipStream_t s);
 // Launch plumbing of the persistent SpMV kernels (per template instantiation: `slot` / `granted` are statics of the launcher).
 // occupancyCached: workgroups per CU of `kernel` at `lds` bytes of dynamic LDS, asked from the runtime once per LDS size -- the query costs
@@ -375,6 +380,9 @@ bool launchPatConstMarch(const smm_hip_csr* m, int op, const T* lhs, const T* di
 template <typename T>
 void launchPatSlots(const smm_hip_csr* m, int lanes, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                     const int* doneFlag, hipStream_t s);
+template <typename T>
+void launchPatSweep(const smm_hip_csr* m, int lanes, int rowsOpen, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1,
+                    T* partials, const int* doneFlag, hipStream_t s);
 template <typename T>
 int launchSpmvPattern(const smm_hip_csr* m, int lanes, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                       const int* doneFlag, hipStream_t s);

@@ -1674,8 +1674,8 @@ const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes)
 	}
 	if ((L == 2 || L == 4) && patUseTile(L)) {
 		if (patternSlotsChosen(m, L)) {  // (smm_spmv_slots.hip: the copy was built by an earlier launch)
-			*bytes = patternSlotsBytes(m);
-			return "spmvPatternSlotsKernel";
+			*bytes = patternSlotsBytes(m);  // (the sweep kernel reads the same copy: the same bytes)
+			return patternSweepRows(m, L) ? "spmvPatternSweepKernel" : "spmvPatternSlotsKernel";
 		}
 		return "spmvPatternTileKernel";
 	}

@@ -20,6 +20,12 @@ namespace smm {
 
 constexpr int SLOT_WAVES = TPB / WAVE;  // waves per workgroup
 
+// the sweep kernel under AUTO (DESIGN 3.1 has the measurements these stand on)
+constexpr int SWEEP_ROWS_DEFAULT = 16;  // (r09, benchmark matrix: 8 / 16 / 32 -> 439 / 430 / 541 us per launch; 32 leaves two waves per SIMD)
+constexpr int SWEEP_MIN_BLOCKS = 3;  // (10 M rows: 3.2 blocks per XCD group, 427 against 479 us; 4 M rows: 1.3 blocks, 240 against 197)
+constexpr long long SWEEP_FRONT_REACH = 16384;  // rows between two touches of an x line that a row-major front's L2 still bridges
+constexpr double SWEEP_MIN_RATIO = 1.5;         // modelled x fetches, front over sweep, from which the sweep is taken
+
 // per wave: the elements of its block (popcount of the shared mask x 64 lanes) if the wave is uniform and whole, else 0; uniform waves counted
 __global__ __launch_bounds__(TPB) void slotsCountKernel(int rows, int nWaves, const unsigned long long* __restrict__ masks, long long* __restrict__ counts,
                                                         int* __restrict__ uniformWaves) {
@@ -150,11 +156,12 @@ __global__ __launch_bounds__(TPB) void spmvPatternSlotsKernel(int rows, int nWav
 
 // ---- selection ----------------------------------------------------------------------------------------------------------------------
 // SMM_HIP_PATTERN_SLOTS=0: never; =1: wherever it applies (also on a kernel set with smm_hip_csr_set_kernel, whatever the share of uniform
-// waves); unset: AUTO.  A handle's own smm_hip_csr_pattern_slots mode wins over the variable.
+// waves); =3: the same, walked by the sweep kernel (smm_spmv_sweep.hip); unset: AUTO.  A handle's own smm_hip_csr_pattern_slots mode wins
+// over the variable.
 static int slotsEnvMode() {
 	static const int mode = [] {
 		const char* env = getenv("SMM_HIP_PATTERN_SLOTS");
-		return env ? (atoi(env) != 0 ? 1 : 0) : -1;
+		return env ? (atoi(env) == 3 ? 3 : atoi(env) != 0 ? 1 : 0) : -1;
 	}();
 	return mode;
 }
@@ -176,9 +183,9 @@ static bool slotsApplies(const smm_hip_csr* m, int lanes) {
 // AUTO: only where the family was adopted by the library itself, and only with >= 99 % uniform waves
 static bool slotsWanted(const smm_hip_csr* m, int lanes, bool* forced) {
 	const int mode = slotsMode(m);
-	*forced = mode == 1;
+	*forced = mode == 1 || mode == 3;
 	if (mode == 0 || !slotsApplies(m, lanes)) return false;
-	return mode == 1 || mode == 2 || !m->kernelForced;
+	return mode >= 1 || !m->kernelForced;
 }
 
 static bool slotsUniformEnough(const smm_hip_csr* m) {
@@ -191,6 +198,47 @@ bool patternSlotsChosen(const smm_hip_csr* m, int lanes) {
 	return forced || slotsUniformEnough(m);
 }
 
+// ---- the sweep kernel (smm_spmv_sweep.hip) on the same copy ------------------------------------------------------------------------
+// 64-row waves a hardware wave holds open: SMM_HIP_PATTERN_SWEEP_ROWS=8|16|32 for lab runs, smm_hip_set_pattern_sweep_rows for the tests
+static std::atomic<int> g_sweepRows{0};
+
+static int sweepRowsOpen() {
+	if (const int forced = g_sweepRows.load(std::memory_order_relaxed)) return forced;
+	static const int env = [] {
+		const char* e = getenv("SMM_HIP_PATTERN_SWEEP_ROWS");
+		const int r = e ? atoi(e) : 0;
+		return r == 8 || r == 16 || r == 32 ? r : 0;
+	}();
+	return env ? env : SWEEP_ROWS_DEFAULT;
+}
+
+// x lines fetched per line of x, from the sorted offsets: a row-major front re-fetches a line at every gap between two
+// offsets that its L2 cannot bridge (SWEEP_FRONT_REACH rows); the sweep of blocks of B rows fetches min(gap, B) / B of its window again
+static bool sweepSpanWins(const smm_hip_csr* m, long long blockRows) {
+	const std::vector<int>& offs = m->pat_offs_host;
+	double front = 1.0, sweep = 1.0;
+	for (size_t i = 1; i < offs.size(); ++i) {
+		const long long gap = static_cast<long long>(offs[i]) - offs[i - 1];
+		if (gap > SWEEP_FRONT_REACH) front += 1.0;
+		sweep += static_cast<double>(std::min(gap, blockRows)) / static_cast<double>(blockRows);
+	}
+	return sweep * SWEEP_MIN_RATIO <= front;
+}
+
+// 0: the slots kernel; else the sweep kernel with that many waves open.  Mode 3 takes it wherever the slots kernel runs; AUTO (and mode 2)
+// only where it was measured to win (profiles/r09/span_and_size.txt): fp32, an XCD group with at least SWEEP_MIN_BLOCKS full super-blocks,
+// and offsets that span more than a row-major front keeps in its L2.
+int patternSweepRows(const smm_hip_csr* m, int lanes) {
+	const int mode = slotsMode(m);
+	const int r = sweepRowsOpen();
+	if (mode == 3) return r;
+	if (mode == 1 || mode == 0) return 0;
+	if (m->dtype != SMM_DTYPE_F32) return 0;  // (fp64 at 10 M rows: 1018 us against the slots kernel's 986 -- two waves per SIMD)
+	const long long groupWaves = patternSweepGroupWaves(m, lanes, r);  // (at the workgroups per CU the launch will get)
+	if (m->pat_slots_waves / 8 < SWEEP_MIN_BLOCKS * groupWaves) return 0;
+	return sweepSpanWins(m, groupWaves * WAVE) ? r : 0;
+}
+
 template <typename T>
 static int slotsFill(smm_hip_csr* m, hipStream_t s) {
 	const int nWaves = m->pat_slots_waves;
@@ -201,6 +249,9 @@ static int slotsFill(smm_hip_csr* m, hipStream_t s) {
 	return SMM_HIP_OK;
 }
 
+// Layout: base[] is the plain inclusive scan of the counts, so the blocks of consecutive uniform waves lie end to end, popcount x 64
+// elements apart, without padding -- the sweep kernel's uniform path (smm_spmv_sweep.hip) steps from one wave's block to the next by that
+// distance.  A layout that pads or reorders the blocks has to change that path with it.
 // the per-wave header (counts, scan, marks) and, when the kernel is to be used, the copy; published only after the stream has finished
 // (a launch on another stream may read it at once), like d_res_ell (smm_resident_bicg.hip)
 template <typename T>
@@ -326,6 +377,10 @@ static void launchSlotsL(const smm_hip_csr* m, int op, const T* lhs, const T* di
 template <typename T>
 void launchPatSlots(const smm_hip_csr* m, int lanes, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                     const int* doneFlag, hipStream_t s) {
+	if (const int rowsOpen = patternSweepRows(m, lanes)) {
+		launchPatSweep<T>(m, lanes, rowsOpen, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s);
+		return;
+	}
 	if (lanes == 2) {
 		launchSlotsL<T, 2>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s);
 	} else {
@@ -341,12 +396,21 @@ template void launchPatSlots<double>(const smm_hip_csr*, int, int, const double*
 }  // namespace smm
 
 extern "C" int smm_hip_csr_pattern_slots(smm_hip_csr* m, int mode) {
-	if (!m || mode < -1 || mode > 2) {
-		smm::setError("csr_pattern_slots: null matrix or a mode other than -1, 0, 1, 2");
+	if (!m || mode < -1 || mode > 3) {
+		smm::setError("csr_pattern_slots: null matrix or a mode other than -1, 0, 1, 2, 3");
 		return SMM_HIP_ERR_INVALID;
 	}
 	std::lock_guard<std::mutex> lock(m->tileMutex);
 	m->pat_slots_mode = mode;
-	if (mode == 1 && m->pat_slots_state < 0) m->pat_slots_state = 0;  // (a forced handle may try again)
+	if ((mode == 1 || mode == 3) && m->pat_slots_state < 0) m->pat_slots_state = 0;  // (a forced handle may try again)
+	return SMM_HIP_OK;
+}
+
+extern "C" int smm_hip_set_pattern_sweep_rows(int rows_open) {
+	if (rows_open != 0 && rows_open != 8 && rows_open != 16 && rows_open != 32) {
+		smm::setError("set_pattern_sweep_rows: 8, 16, 32, or 0 for the default");
+		return SMM_HIP_ERR_INVALID;
+	}
+	smm::g_sweepRows.store(rows_open, std::memory_order_relaxed);
 	return SMM_HIP_OK;
 }

@@ -122,6 +122,11 @@ def set_march_min_rows(const_diagonals_rows=-1, values_read_rows=-1):
     check(_lib.load().smm_hip_set_march_min_rows(int(const_diagonals_rows), int(values_read_rows)))
 
 
+def set_pattern_sweep_rows(rows_open=0):
+    """how many 64-row waves a hardware wave of the PATTERN sweep kernel holds open: 8, 16, 32 (0: the default); same bits at each"""
+    check(_lib.load().smm_hip_set_pattern_sweep_rows(int(rows_open)))
+
+
 def profile_read_waits(reset=True):
     """(exposed ms, exchanges): what the halo exchanges of the row-partitioned SpMVs cost BEYOND the local block that ran beside them"""
     ms, n = ctypes.c_double(), ctypes.c_longlong()
@@ -325,8 +330,8 @@ class CSRMatrix:
         check(_lib.load().smm_hip_csr_pattern_allow_const(self._h, 1 if allow else 0))
 
     def pattern_slots(self, mode):
-        """the PATTERN slots kernel: -1 AUTO (default), 0 off, 1 wherever it applies, 2 AUTO's rules also on a kernel set with set_kernel;
-        same bits as the tile kernel"""
+        """the PATTERN slots kernel: -1 AUTO (default), 0 off, 1 wherever it applies, 2 AUTO's rules also on a kernel set with set_kernel,
+        3 wherever it applies and walked by the sweep kernel; same bits as the tile kernel"""
         check(_lib.load().smm_hip_csr_pattern_slots(self._h, int(mode)))
 
     # ---- editing the values on the device (the pattern stays; smm_hip.h "editing the VALUES of a matrix") ----
