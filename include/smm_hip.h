@@ -261,6 +261,52 @@ int smm_hip_csr_values_changed_f64(smm_hip_csr* m, smm_hip_stream stream);
  * like smm_hip_csr_axpy_*. */
 int smm_hip_csr_same_pattern(const smm_hip_csr* a, const smm_hip_csr* b, int* same);
 
+/* ---- assembling a matrix from TRIPLETS on the device (TripletMatrix::addEntry ref:606-618 + CSRMatrix::fillArrays ref:1606-1641) -----
+ * A plan (smm_hip_assembly) is the symbolic result of ONE list of n (row, col) pairs, independent of dtype and of values: the pairs
+ * sorted once (stable, on the device), the runs of equal pairs found, the pattern written.  With the plan, turning a list of n values --
+ * values[i] belongs to pair i -- into the values of the matrix is one gather-and-sum pass (csrc/smm_assembly.hip): what a time or Newton
+ * loop repeats for every new set of element contributions, instead of a sort and a search per call (smm_hip_csr_update_entries_*).
+ *
+ * Pattern: the stored entries are the distinct (row, col) pairs, rows ascending, columns ascending inside a row (ref:1634-1635);
+ *   start[rows + 1], positions[nnz] and first_active_start (smm_hip_csr_info) exactly as fillArrays leaves them (ref:1619-1628).  n == 0,
+ *   empty rows and rows == 0 are legal.
+ * Values: the value of a stored entry is that of the reference's addEntry calls IN LIST ORDER: the first contribution of a pair is taken
+ *   as it is (not 0 + v: a lone -0.0 stays -0.0), every later one is added to it in list order, one rounding each.  Bit for bit: no
+ *   floating-point atomics, no tree sums -- the result does not depend on the launch geometry.
+ * Out of range: a pair with row outside [0, rows) or col outside [0, cols) (the reference asserts) makes create return
+ *   SMM_HIP_ERR_INVALID, with the FIRST offending list index named in smm_hip_last_error(); nothing is created.  Found by a flag on the
+ *   device, never by a fault.
+ * Limits: n > 2^31 - 1 returns SMM_HIP_ERR_INVALID (the library's 32-bit limit; nnz <= n).
+ * create_dev may synchronise `stream` (nnz is needed on the host to allocate); the index arrays are only read and are not needed once
+ *   the call has returned.  Host forms take host arrays and synchronise.
+ * csr_create_*: a matrix that owns its three device arrays and does not depend on the plan's lifetime -- an smm_hip_csr like any other
+ *   (AUTO kernel choice, PATTERN analysis on first use, edits, preconditioners, smm_hip_csr_same_pattern) --, stamped by the plan.
+ * refill_*: new values for a matrix THIS plan created (same dtype), else SMM_HIP_ERR_INVALID and nothing changes.  mode SMM_UPDATE_SET:
+ *   the values of the assembly of the new list, the bits of a fresh csr_create from it; SMM_UPDATE_ADD: values[k] = values[k] +
+ *   assembled[k], one rounding.  A refill is a value edit like smm_hip_csr_set_values_dev_*: what was derived from the pattern is kept
+ *   (the first SpMV after it runs no analysis), what was derived from the values follows (constant diagonals re-verified -- that call
+ *   then synchronises `stream` --, the slots / sweep copy, the single-launch BiCGStab's copy), and the rules for preconditioners made
+ *   before an edit apply unchanged.
+ * Cost of csr_create / refill: n (s + 4) + (nnz + 1) 4 bytes read, nnz s written (+ nnz s read for ADD), s = sizeof(T); without repeated
+ *   pairs n (s + 4) read and n s written.  The gather of values[] is as local as the caller's list order.
+ * Distributed handles are not covered. */
+typedef struct smm_hip_assembly smm_hip_assembly;
+int smm_hip_assembly_create(int rows, int cols, long long n, const int* row_idx, const int* col_idx, smm_hip_assembly** out);
+int smm_hip_assembly_create_dev(int rows, int cols, long long n, const int* d_row_idx, const int* d_col_idx, smm_hip_stream stream, smm_hip_assembly** out);
+/* n = pairs in the list, nnz = distinct pairs, longest_run = the most contributions any one entry receives (any pointer may be NULL) */
+int smm_hip_assembly_info(const smm_hip_assembly* plan, int* rows, int* cols, long long* n, int* nnz, int* longest_run);
+/* copies start[rows + 1] / positions[nnz] to host memory (synchronous; either may be NULL) */
+int smm_hip_assembly_pattern(const smm_hip_assembly* plan, int* start, int* positions);
+int smm_hip_assembly_destroy(smm_hip_assembly* plan);
+int smm_hip_assembly_csr_create_f32(const smm_hip_assembly* plan, const float* values, smm_hip_csr** out);
+int smm_hip_assembly_csr_create_f64(const smm_hip_assembly* plan, const double* values, smm_hip_csr** out);
+int smm_hip_assembly_csr_create_dev_f32(const smm_hip_assembly* plan, const float* d_values, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_assembly_csr_create_dev_f64(const smm_hip_assembly* plan, const double* d_values, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_assembly_refill_f32(const smm_hip_assembly* plan, smm_hip_csr* m, const float* values, int mode);
+int smm_hip_assembly_refill_f64(const smm_hip_assembly* plan, smm_hip_csr* m, const double* values, int mode);
+int smm_hip_assembly_refill_dev_f32(const smm_hip_assembly* plan, smm_hip_csr* m, const float* d_values, int mode, smm_hip_stream stream);
+int smm_hip_assembly_refill_dev_f64(const smm_hip_assembly* plan, smm_hip_csr* m, const double* d_values, int mode, smm_hip_stream stream);
+
 /* ---- SpMV: CSRMatrix<T>::rMult / rMultAdd / rMultSub (ref:1458-1515) -------------------------------------- */
 /* out[i] = op(lhs[i], sum_k values[k]*x[positions[k]]); empty rows give op(lhs[i],0) (ref:1479-1483);
  * out may alias lhs, x must not alias out (ref:1503).  lhs is ignored for SMM_OP_ASSIGN. */

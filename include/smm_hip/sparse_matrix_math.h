@@ -22,6 +22,8 @@
 // Additions the reference lacks: CSRMatrix::init(rows, cols, start, positions, values) (raw CSR arrays, ref can only be
 // filled through a std::map), JacobiPreconditioner, a working ILU0Preconditioner, Matrix Market `general` matrices, and value edits
 // made ON THE GPU once the matrix has a device mirror (the pattern and everything derived from it are kept: see "Editing the values").
+// Also an addition: SMM::AssemblyPlan with CSRMatrix::init(plan, values) / assemble(plan, values) -- the triplets sorted once and summed
+// on the GPU in list order, for callers that assemble the same pattern again and again; init(TripletMatrix) is unchanged.
 #pragma once
 
 #include <algorithm>
@@ -72,6 +74,8 @@ struct Abi<float> {
 	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f32(m, nullptr); }
 	static int update(smm_hip_csr* m, int n, const int* r, const int* c, const float* v) { return smm_hip_csr_update_entries_f32(m, n, r, c, v, SMM_UPDATE_SET, nullptr); }
 	static int getValues(const smm_hip_csr* m, float* v) { return smm_hip_csr_get_values_f32(m, v); }
+	static int assembled(const smm_hip_assembly* p, const float* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f32(p, v, o); }
+	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const float* v, int mode) { return smm_hip_assembly_refill_f32(p, m, v, mode); }
 };
 template <>
 struct Abi<double> {
@@ -91,6 +95,8 @@ struct Abi<double> {
 	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f64(m, nullptr); }
 	static int update(smm_hip_csr* m, int n, const int* r, const int* c, const double* v) { return smm_hip_csr_update_entries_f64(m, n, r, c, v, SMM_UPDATE_SET, nullptr); }
 	static int getValues(const smm_hip_csr* m, double* v) { return smm_hip_csr_get_values_f64(m, v); }
+	static int assembled(const smm_hip_assembly* p, const double* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f64(p, v, o); }
+	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const double* v, int mode) { return smm_hip_assembly_refill_f64(p, m, v, mode); }
 };
 inline int& statusSlot() noexcept {
 	static thread_local int st = SMM_HIP_OK;
@@ -215,6 +221,57 @@ private:
 	static uint64_t key(int row, int col) { return (static_cast<uint64_t>(static_cast<uint32_t>(row)) << 32) | static_cast<uint32_t>(col); }
 	std::map<uint64_t, T> data;
 	int denseRowCount = 0, denseColCount = 0;
+};
+
+// ---- AssemblyPlan (addition): one list of (row, col) pairs sorted ONCE on the GPU -- the symbolic half of TripletMatrix + CSRMatrix(triplet).
+// CSRMatrix<T>::init(plan, values) / assemble(plan, values) then sum the values of repeated pairs in list order (the bits of addEntry,
+// ref:606-618, the first contribution taken as it is) in one device pass; smm_hip.h "assembling a matrix from TRIPLETS".  A pair outside the
+// matrix, or no GPU: status() / lastHipStatus() != 0 and the plan is empty (valid() == false).
+class AssemblyPlan {
+public:
+	AssemblyPlan() noexcept = default;
+	AssemblyPlan(int rows, int cols, long long n, const int* rowIdx, const int* colIdx) noexcept { init(rows, cols, n, rowIdx, colIdx); }
+	AssemblyPlan(const AssemblyPlan&) = delete;
+	AssemblyPlan& operator=(const AssemblyPlan&) = delete;
+	AssemblyPlan(AssemblyPlan&& o) noexcept { *this = std::move(o); }
+	AssemblyPlan& operator=(AssemblyPlan&& o) noexcept {
+		if (this != &o) {
+			smm_hip_assembly_destroy(plan);
+			plan = o.plan;
+			st = o.st;
+			o.plan = nullptr;
+		}
+		return *this;
+	}
+	~AssemblyPlan() { smm_hip_assembly_destroy(plan); }
+	int init(int rows, int cols, long long n, const int* rowIdx, const int* colIdx) noexcept {
+		smm_hip_assembly_destroy(plan);
+		plan = nullptr;
+		st = detail::note(smm_hip_assembly_create(rows, cols, n, rowIdx, colIdx, &plan));
+		if (st != SMM_HIP_OK) plan = nullptr;
+		return st;
+	}
+	bool valid() const noexcept { return plan != nullptr; }
+	int status() const noexcept { return st; }
+	int getDenseRowCount() const noexcept { return info(0); }
+	int getDenseColCount() const noexcept { return info(1); }
+	int getNonZeroCount() const noexcept { return info(2); }
+	int getLongestRun() const noexcept { return info(3); }
+	long long getTripletCount() const noexcept {
+		long long n = 0;
+		if (plan) smm_hip_assembly_info(plan, nullptr, nullptr, &n, nullptr, nullptr);
+		return n;
+	}
+	const smm_hip_assembly* handle() const noexcept { return plan; }
+
+private:
+	int info(int which) const noexcept {
+		int v[4] = {0, 0, 0, 0};
+		if (plan) smm_hip_assembly_info(plan, &v[0], &v[1], nullptr, &v[2], &v[3]);
+		return v[which];
+	}
+	smm_hip_assembly* plan = nullptr;
+	int st = SMM_HIP_OK;
 };
 
 // ref:1002-1006; JACOBI and the BLOCK_ forms (ILU0 / SGS of the block-diagonal part of A, smm_hip.h) are additions
@@ -424,6 +481,46 @@ public:
 		std::copy(valuesIn, valuesIn + nnz, values.get());
 		computeFirstActive();
 		return 0;
+	}
+	// addition: the matrix of an AssemblyPlan's pairs with values[i] the contribution of pair i, assembled on the GPU (repeated pairs add up
+	// in list order); the host arrays are filled from the device result, so iterators, getValue and the single-entry edits work as after
+	// any other init.  Returns 0, or the SMM_HIP_* status (also in lastHipStatus()) with the matrix left empty.
+	int init(const AssemblyPlan& plan, const T* valuesIn) noexcept {
+		release();
+		values.reset();
+		positions.reset();
+		start.reset();
+		denseRowCount = denseColCount = firstActiveStart = 0;
+		if (!plan.valid()) return detail::note(plan.status() != SMM_HIP_OK ? plan.status() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(detail::Abi<T>::assembled(plan.handle(), valuesIn, &d)) != SMM_HIP_OK) return lastHipStatus();
+		const int rows = plan.getDenseRowCount(), nnz = plan.getNonZeroCount();
+		std::unique_ptr<T[]> v(new T[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> p(new int[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> s(new int[rows + 1]());
+		int abi = smm_hip_assembly_pattern(plan.handle(), s.get(), p.get());
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(d, v.get());
+		if (detail::note(abi) != SMM_HIP_OK) {
+			smm_hip_csr_destroy(d);
+			return abi;
+		}
+		values = std::move(v);
+		positions = std::move(p);
+		start = std::move(s);
+		denseRowCount = rows;
+		denseColCount = plan.getDenseColCount();
+		computeFirstActive();
+		dev = d;
+		return 0;
+	}
+	// addition: new values for a matrix made by init(plan, ...) from the same plan -- those of init(plan, valuesIn), or added to the present
+	// ones (add) -- in one device pass; the pattern and what the library derived from it stay.  Non-zero (the SMM_HIP_* status): not this
+	// plan's matrix, no GPU; nothing changed then.
+	int assemble(const AssemblyPlan& plan, const T* valuesIn, bool add = false) {
+		if (!plan.valid() || !flushedMirror()) return detail::note(SMM_HIP_ERR_INVALID);
+		const int abi = detail::Abi<T>::refill(plan.handle(), dev, valuesIn, add ? SMM_UPDATE_ADD : SMM_UPDATE_SET);
+		deviceEdited(abi);
+		return abi;
 	}
 	int getNonZeroCount() const noexcept { return start ? start[denseRowCount] : 0; }
 	int getDenseRowCount() const noexcept { return denseRowCount; }

@@ -14,6 +14,7 @@ from .host import (  # noqa: F401
     SPMV_PATTERN,
     SPMV_STREAM,
     SPMV_VECTOR,
+    AssemblyPlan,
     BiCGStab,
     BiCGSymmetric,
     ConjugateGradient,

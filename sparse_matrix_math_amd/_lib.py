@@ -81,6 +81,10 @@ _TYPED = {
     "smm_hip_csr_set_values_dev": (c_int, [_P, _P, _P]),
     "smm_hip_csr_get_values": (c_int, [_P, _P]),
     "smm_hip_csr_values_changed": (c_int, [_P, _P]),
+    "smm_hip_assembly_csr_create": (c_int, [_P, _P, POINTER(_P)]),
+    "smm_hip_assembly_csr_create_dev": (c_int, [_P, _P, _P, POINTER(_P)]),
+    "smm_hip_assembly_refill": (c_int, [_P, _P, _P, c_int]),
+    "smm_hip_assembly_refill_dev": (c_int, [_P, _P, _P, c_int, _P]),
 }
 
 
@@ -111,6 +115,11 @@ _PLAIN = {
     "smm_hip_csr_pattern_slots": (c_int, [_P, c_int]),
     "smm_hip_set_pattern_sweep_rows": (c_int, [c_int]),
     "smm_hip_csr_same_pattern": (c_int, [_P, _P, POINTER(c_int)]),
+    "smm_hip_assembly_create": (c_int, [c_int, c_int, c_longlong, _P, _P, POINTER(_P)]),
+    "smm_hip_assembly_create_dev": (c_int, [c_int, c_int, c_longlong, _P, _P, _P, POINTER(_P)]),
+    "smm_hip_assembly_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_longlong), POINTER(c_int), POINTER(c_int)]),
+    "smm_hip_assembly_pattern": (c_int, [_P, _P, _P]),
+    "smm_hip_assembly_destroy": (c_int, [_P]),
     "smm_hip_precond_create": (c_int, [_P, c_int, POINTER(_P)]),
     "smm_hip_precond_create_block": (c_int, [_P, c_int, c_int, POINTER(_P)]),
     "smm_hip_precond_create_block_capped": (c_int, [_P, c_int, c_int, c_int, POINTER(_P)]),

@@ -491,6 +491,11 @@ int valuesChanged(smm_hip_csr* m, hipStream_t s) {
 }
 
 }  // namespace
+
+int csrValuesEdited(smm_hip_csr* m, hipStream_t s) {
+	return m->dtype == SMM_DTYPE_F32 ? valuesEdited<float>(m, s, EDIT_OTHER, 0.f, nullptr) : valuesEdited<double>(m, s, EDIT_OTHER, 0.0, nullptr);
+}
+
 }  // namespace smm
 
 using namespace smm;

@@ -210,6 +210,8 @@ struct smm_hip_csr {
 	std::atomic<unsigned long long> uid{0};
 	std::mutex editMutex;
 	std::vector<std::pair<unsigned long long, bool>> patternSeen;
+	// the stamp of the assembly plan that created this matrix (smm_assembly.hip; 0: none did): what smm_hip_assembly_refill_* looks for
+	unsigned long long assemblyStamp = 0;
 };
 
 struct smm_hip_precond {
@@ -311,6 +313,8 @@ const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes)
 void planMarch(smm_hip_csr* m);
 // values edited (smm_csr_update.hip): rewrite the single-launch BiCGStab's slot-major copy of the values (smm_resident_bicg.hip; asynchronous)
 int refreshResEll(smm_hip_csr* a, hipStream_t s);
+// values[] of a ready matrix was rewritten on `s` by another unit (smm_assembly.hip): the path of smm_hip_csr_values_changed_*
+int csrValuesEdited(smm_hip_csr* m, hipStream_t s);
 // the wave-sliced value copy of the PATTERN slots kernel (smm_spmv_slots.hip).  ensurePatternSlots: build it if this launch would use it
 // (caller holds tileMutex; false: stay on the tile kernel); refreshPatternSlots: rewrite it in place after an edit (asynchronous, under
 // tileMutex); patternSlotsChosen / patternSlotsBytes: the launch's choice and its bytes, for smm_hip_csr_kernel_desc

@@ -261,6 +261,26 @@ class CSRMatrix:
         self._read_info()
         return self
 
+    @classmethod
+    def from_triplets(cls, rows, cols, row_idx, col_idx, values):
+        """The reference's TripletMatrix + CSRMatrix(triplet) in one call, assembled on the device: repeated (row, col) pairs add up in
+        list order.  The plan is created and dropped; keep an AssemblyPlan to assemble the same list of pairs again."""
+        plan = AssemblyPlan(rows, cols, row_idx, col_idx)
+        try:
+            return plan.assemble(values)
+        finally:
+            plan.close()
+
+    @classmethod
+    def _adopt(cls, handle, dtype):
+        self = cls.__new__(cls)
+        self.dtype = np.dtype(dtype)
+        self._suf = _suffix(self.dtype)
+        self._h = handle
+        self._keep = None
+        self._read_info()
+        return self
+
     def _read_info(self):
         r, c, n, d, f = (ctypes.c_int() for _ in range(5))
         check(_lib.load().smm_hip_csr_info(self._h, ctypes.byref(r), ctypes.byref(c), ctypes.byref(n), ctypes.byref(d), ctypes.byref(f)))
@@ -429,6 +449,84 @@ class CSRMatrix:
     def close(self):
         if self._h:
             _lib.load().smm_hip_csr_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AssemblyPlan:
+    """The symbolic half of assembling a CSRMatrix from triplets on the device (smm_hip.h "assembling a matrix from TRIPLETS"): one list
+    of (row, col) pairs sorted once; assemble / refill then turn a list of values -- values[i] belongs to pair i -- into the matrix's
+    values with one gather-and-sum pass.  Repeated pairs add up in list order, bit for bit like the reference's addEntry (ref:606-618).
+    A pair outside the matrix raises SmmHipError (SMM_HIP_ERR_INVALID) naming its list index."""
+
+    def __init__(self, rows, cols, row_idx, col_idx):
+        row_idx = np.ascontiguousarray(row_idx, dtype=np.int32)
+        col_idx = np.ascontiguousarray(col_idx, dtype=np.int32)
+        if row_idx.ndim != 1 or row_idx.shape != col_idx.shape:
+            raise ValueError("row_idx and col_idx must be one-dimensional and of the same length")
+        self._h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_assembly_create(int(rows), int(cols), row_idx.size, _host(row_idx, np.int32, "row_idx"), _host(col_idx, np.int32, "col_idx"),
+                                                  ctypes.byref(self._h)))
+        self._read_info()
+
+    @classmethod
+    def from_device(cls, rows, cols, n, d_row_idx, d_col_idx, stream=None):
+        """n pairs in int32 device arrays (only read, not needed after the call); may synchronise `stream`"""
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_assembly_create_dev(int(rows), int(cols), int(n), _dptr(d_row_idx), _dptr(d_col_idx), _dptr(stream), ctypes.byref(self._h)))
+        self._read_info()
+        return self
+
+    def _read_info(self):
+        r, c, z, l = (ctypes.c_int() for _ in range(4))
+        n = ctypes.c_longlong()
+        check(_lib.load().smm_hip_assembly_info(self._h, ctypes.byref(r), ctypes.byref(c), ctypes.byref(n), ctypes.byref(z), ctypes.byref(l)))
+        self.rows, self.cols, self.n, self.nnz, self.longest_run = r.value, c.value, n.value, z.value, l.value
+
+    def pattern(self):
+        """(start[rows + 1], positions[nnz]) as the reference's fillArrays leaves them"""
+        start = np.empty(self.rows + 1, dtype=np.int32)
+        positions = np.empty(self.nnz, dtype=np.int32)
+        check(_lib.load().smm_hip_assembly_pattern(self._h, _host(start, np.int32, "start"), _host(positions, np.int32, "positions")))
+        return start, positions
+
+    def _values(self, values, dtype=None):
+        values = np.ascontiguousarray(values) if dtype is None else np.ascontiguousarray(values, dtype=dtype)
+        if values.ndim != 1 or values.size != self.n:
+            raise ValueError(f"values must hold one number per pair of the list ({self.n})")
+        return values
+
+    def assemble(self, values):
+        """a new CSRMatrix of values.dtype that owns its arrays (it does not need the plan afterwards, except for refill)"""
+        values = self._values(values)
+        suf = _suffix(values.dtype)
+        h = ctypes.c_void_p()
+        check(_fn("smm_hip_assembly_csr_create", suf)(self._h, _host(values, values.dtype, "values"), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, values.dtype)
+
+    def assemble_dev(self, d_values, dtype, stream=None):
+        h = ctypes.c_void_p()
+        check(_fn("smm_hip_assembly_csr_create_dev", _suffix(dtype))(self._h, _dptr(d_values), _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, dtype)
+
+    def refill(self, A, values, add=False):
+        """new values for a matrix this plan created: those of assemble(values), or added to the present ones (add=True)"""
+        values = self._values(values, A.dtype)
+        check(_fn("smm_hip_assembly_refill", A._suf)(self._h, A._h, _host(values, A.dtype, "values"), 1 if add else 0))
+
+    def refill_dev(self, A, d_values, add=False, stream=None):
+        check(_fn("smm_hip_assembly_refill_dev", A._suf)(self._h, A._h, _dptr(d_values), 1 if add else 0, _dptr(stream)))
+        A._edited(stream)
+
+    def close(self):
+        if self._h:
+            _lib.load().smm_hip_assembly_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
