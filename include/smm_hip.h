@@ -315,6 +315,22 @@ int smm_hip_spmv_f64(const smm_hip_csr* m, int op, const double* lhs, const doub
 int smm_hip_spmv_dev_f32(const smm_hip_csr* m, int op, const float* d_lhs, const float* d_x, float* d_out, smm_hip_stream stream);
 int smm_hip_spmv_dev_f64(const smm_hip_csr* m, int op, const double* d_lhs, const double* d_x, double* d_out, smm_hip_stream stream);
 
+/* ---- several right-hand sides at once: CSR SpMM (csrc/smm_spmm.hip) ------------------------------------------
+ * An addition: the reference multiplies by one vector (ref:1501-1515).  A block of k vectors is ONE dense array of n x k elements,
+ * row-major ("interleaved"): element (i, j) is at i * k + j; 1 <= k <= SMM_HIP_MAX_RHS.  x has cols x k elements, lhs and out rows x k.
+ *   out(i, j) = op(lhs(i, j), sum_e values[e] * x(positions[e], j))
+ * The matrix is streamed once for all k columns.  Column j of out carries the bits smm_hip_spmv_* gives for column j alone with one
+ * lane per row (a row's entries in stored order through _smm_fma, ref:1484-1490), whatever smm_hip_csr_set_kernel chose for the
+ * SpMV; only a row longer than one tile of the STREAM family's tile table (smm_hip_csr_tile_info: tile_nnz_cap) is split over the
+ * lanes of a wavefront and agrees to the rounding of a re-ordered sum.  It reads the handle's CSR arrays, so it follows every edit of
+ * the values (smm_hip_csr_scale / _update_entries / smm_hip_assembly_refill ...).  out may alias lhs, x must not alias out (ref:1503);
+ * lhs is ignored for SMM_OP_ASSIGN.  k outside 1 .. SMM_HIP_MAX_RHS, a null array or a dtype mismatch: SMM_HIP_ERR_INVALID. */
+#define SMM_HIP_MAX_RHS 8
+int smm_hip_spmm_f32(const smm_hip_csr* m, int op, int k, const float* lhs, const float* x, float* out);
+int smm_hip_spmm_f64(const smm_hip_csr* m, int op, int k, const double* lhs, const double* x, double* out);
+int smm_hip_spmm_dev_f32(const smm_hip_csr* m, int op, int k, const float* d_lhs, const float* d_x, float* d_out, smm_hip_stream stream);
+int smm_hip_spmm_dev_f64(const smm_hip_csr* m, int op, int k, const double* d_lhs, const double* d_x, double* d_out, smm_hip_stream stream);
+
 /* ---- reductions: Vector<T>::operator* (ref:305-328), secondNormSquared (ref:296-303) ---------------------- */
 int smm_hip_dot_f32(int n, const float* a, const float* b, float* result);
 int smm_hip_dot_f64(int n, const double* a, const double* b, double* result);
@@ -391,6 +407,36 @@ int smm_hip_bicgstab_functor_f32(const smm_hip_csr* a, float* b, float* x, int m
                                  int* solver_status, int* iterations, float* resnorm);
 int smm_hip_bicgstab_functor_f64(const smm_hip_csr* a, double* b, double* x, int maxIterations, double eps, smm_hip_apply_fn_f64 apply, void* user,
                                  int* solver_status, int* iterations, double* resnorm);
+
+/* ---- several right-hand sides at once: batched BiCGStab / ConjugateGradient (csrc/smm_solvers_batch.hip) --------------------
+ * Additions: the reference's solvers take one b (ref:2191, 2316).  b, x (and x0) are interleaved rows x k blocks as for smm_hip_spmm_*,
+ * 1 <= k <= SMM_HIP_MAX_RHS; solver_status, iterations and resnorm are HOST arrays of k elements (each may be NULL).  Every SpMM of the
+ * loop streams the matrix once for all k columns.  Column j is solved exactly as smm_hip_bicgstab_* / smm_hip_cg_* solve it alone:
+ * its own alpha / omega / beta and dot products, the reference's loop do { } while (res_j > eps && it_j < maxIterations) with the same
+ * clamp of maxIterations, status rule and NaN behaviour (ref:2200-2283, 2330-2398).  A column that has left its loop is frozen -- its
+ * x, iterations, status and resnorm are not written again while the others go on -- and nothing of it (a NaN, a zero) reaches another
+ * column.  The dot products add the rows in another (fixed) partition than the single loops, so x agrees with the single solve to the
+ * rounding of re-ordered sums, not bit for bit.  The plain loops only: no resident, lazy-x or PATTERN form is entered from here.
+ *   bicgstab_batch: M may be NULL or of kind SMM_PRECOND_NONE / SMM_PRECOND_JACOBI (created for `a`; its division is folded into the
+ *   rows of the SpMM as in the single loop); every other kind returns SMM_HIP_ERR_INVALID.  cg_batch takes no preconditioner; a column
+ *   whose first residual already passes reports 0 iterations and its x(:, j) is not written (ref:2342-2344).
+ * SMM_HIP_ERR_INVALID: k outside 1 .. SMM_HIP_MAX_RHS, null arrays, dtype mismatch, a matrix that is not square. */
+int smm_hip_bicgstab_batch_f32(const smm_hip_csr* a, int k, float* b, float* x, int maxIterations, float eps, const smm_hip_precond* M,
+                               int* solver_status, int* iterations, float* resnorm);
+int smm_hip_bicgstab_batch_f64(const smm_hip_csr* a, int k, double* b, double* x, int maxIterations, double eps, const smm_hip_precond* M,
+                               int* solver_status, int* iterations, double* resnorm);
+int smm_hip_bicgstab_batch_dev_f32(const smm_hip_csr* a, int k, const float* d_b, float* d_x, int maxIterations, float eps, const smm_hip_precond* M,
+                                   smm_hip_stream stream, int* solver_status, int* iterations, float* resnorm);
+int smm_hip_bicgstab_batch_dev_f64(const smm_hip_csr* a, int k, const double* d_b, double* d_x, int maxIterations, double eps, const smm_hip_precond* M,
+                                   smm_hip_stream stream, int* solver_status, int* iterations, double* resnorm);
+int smm_hip_cg_batch_f32(const smm_hip_csr* a, int k, const float* b, const float* x0, float* x, int maxIterations, float eps, int* solver_status,
+                         int* iterations, float* resnorm2);
+int smm_hip_cg_batch_f64(const smm_hip_csr* a, int k, const double* b, const double* x0, double* x, int maxIterations, double eps, int* solver_status,
+                         int* iterations, double* resnorm2);
+int smm_hip_cg_batch_dev_f32(const smm_hip_csr* a, int k, const float* d_b, const float* d_x0, float* d_x, int maxIterations, float eps,
+                             smm_hip_stream stream, int* solver_status, int* iterations, float* resnorm2);
+int smm_hip_cg_batch_dev_f64(const smm_hip_csr* a, int k, const double* d_b, const double* d_x0, double* d_x, int maxIterations, double eps,
+                             smm_hip_stream stream, int* solver_status, int* iterations, double* resnorm2);
 
 /* BiCGSymmetric (ref:2021-2102): same kernels as CG plus the DIVERGED heuristics (ref:2056-2058, 2079-2081) */
 int smm_hip_bicgsymmetric_f32(const smm_hip_csr* a, float* b, float* x, int maxIterations, float eps, int* solver_status, int* iterations);

@@ -76,6 +76,13 @@ struct Abi<float> {
 	static int getValues(const smm_hip_csr* m, float* v) { return smm_hip_csr_get_values_f32(m, v); }
 	static int assembled(const smm_hip_assembly* p, const float* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f32(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const float* v, int mode) { return smm_hip_assembly_refill_f32(p, m, v, mode); }
+	static int spmm(const smm_hip_csr* m, int op, int k, const float* l, const float* x, float* o) { return smm_hip_spmm_f32(m, op, k, l, x, o); }
+	static int bicgstabBatch(const smm_hip_csr* a, int k, float* b, float* x, int it, float eps, const smm_hip_precond* M, int* st) {
+		return smm_hip_bicgstab_batch_f32(a, k, b, x, it, eps, M, st, nullptr, nullptr);
+	}
+	static int cgBatch(const smm_hip_csr* a, int k, const float* b, const float* x0, float* x, int it, float eps, int* st) {
+		return smm_hip_cg_batch_f32(a, k, b, x0, x, it, eps, st, nullptr, nullptr);
+	}
 };
 template <>
 struct Abi<double> {
@@ -97,6 +104,13 @@ struct Abi<double> {
 	static int getValues(const smm_hip_csr* m, double* v) { return smm_hip_csr_get_values_f64(m, v); }
 	static int assembled(const smm_hip_assembly* p, const double* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f64(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const double* v, int mode) { return smm_hip_assembly_refill_f64(p, m, v, mode); }
+	static int spmm(const smm_hip_csr* m, int op, int k, const double* l, const double* x, double* o) { return smm_hip_spmm_f64(m, op, k, l, x, o); }
+	static int bicgstabBatch(const smm_hip_csr* a, int k, double* b, double* x, int it, double eps, const smm_hip_precond* M, int* st) {
+		return smm_hip_bicgstab_batch_f64(a, k, b, x, it, eps, M, st, nullptr, nullptr);
+	}
+	static int cgBatch(const smm_hip_csr* a, int k, const double* b, const double* x0, double* x, int it, double eps, int* st) {
+		return smm_hip_cg_batch_f64(a, k, b, x0, x, it, eps, st, nullptr, nullptr);
+	}
 };
 inline int& statusSlot() noexcept {
 	static thread_local int st = SMM_HIP_OK;
@@ -606,6 +620,12 @@ public:
 	void rMult(const T* const mult, T* const res) const noexcept { spmv(SMM_OP_ASSIGN, nullptr, mult, res); }
 	void rMultAdd(const T* const lhs, const T* const mult, T* const out) const noexcept { spmv(SMM_OP_ADD, lhs, mult, out); }
 	void rMultSub(const T* const lhs, const T* const mult, T* const out) const noexcept { spmv(SMM_OP_SUB, lhs, mult, out); }
+	// additions with no counterpart in the reference: k right-hand sides at once (1 <= k <= SMM_HIP_MAX_RHS).  X is an interleaved block of
+	// getDenseColCount() x k elements, Lhs / Out of getDenseRowCount() x k: element (i, j) at i * k + j.  The matrix is streamed once for all k
+	// columns; column j of Out is what rMult / rMultAdd / rMultSub give for column j alone (smm_hip.h "CSR SpMM").  Out may be Lhs, not X.
+	void rMult(const T* const X, T* const Out, const int k) const noexcept { spmm(SMM_OP_ASSIGN, k, nullptr, X, Out); }
+	void rMultAdd(const T* const Lhs, const T* const X, T* const Out, const int k) const noexcept { spmm(SMM_OP_ADD, k, Lhs, X, Out); }
+	void rMultSub(const T* const Lhs, const T* const X, T* const Out, const int k) const noexcept { spmm(SMM_OP_SUB, k, Lhs, X, Out); }
 
 	// ref:1643-1651.  WHAT THE KINDS COST ON THE GPU (measured, MI355X, BiCGStab to 1e-8 on the 1.26 M-row convection-diffusion problem of
 	// BASELINE config 5; INTEGRATION.md "What a preconditioner costs"): the reference's own kind, SYMMETRIC_GAUS_SEIDEL, and ILU0 are EXACT
@@ -668,6 +688,12 @@ private:
 	void spmv(int op, const T* lhs, const T* mult, T* out) const noexcept {
 		const smm_hip_csr* d = device();  // a failed mirror has already noted its status
 		if (!d || detail::note(detail::Abi<T>::spmv(d, op, lhs, mult, out)) != SMM_HIP_OK) detail::fillNaN(out, denseRowCount);
+	}
+	void spmm(int op, int k, const T* lhs, const T* mult, T* out) const noexcept {
+		const smm_hip_csr* d = device();
+		if (!d || detail::note(detail::Abi<T>::spmm(d, op, k, lhs, mult, out)) != SMM_HIP_OK) {
+			detail::fillNaN(out, k >= 1 && k <= SMM_HIP_MAX_RHS ? denseRowCount * k : 0);  // (a k out of range says nothing about out's size)
+		}
 	}
 	void computeFirstActive() noexcept {  // ref:1619-1628
 		firstActiveStart = denseRowCount;
@@ -826,6 +852,40 @@ inline SolverStatus BiCGStab(const CSRMatrix<T>& a, T* b, T* x, int maxIteration
 template <typename T>
 inline SolverStatus BiCGStab(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps) {
 	return BiCGStab(a, b, x, maxIterations, eps, typename CSRMatrix<T>::IDPreconditioner());
+}
+
+// ---- additions with no counterpart in the reference: k right-hand sides at once (smm_hip.h "batched BiCGStab / ConjugateGradient") ----
+// B, X (and X0) are interleaved blocks of rows x k elements, element (i, j) at i * k + j, 1 <= k <= SMM_HIP_MAX_RHS; status[j] (k entries, may
+// be null) receives what BiCGStab / ConjugateGradient return for column j alone: every column runs the reference's loop for its own b
+// (ref:2200-2283, 2330-2398) and is left alone once it has ended.  The return value is SUCCESS when the call ran (whatever the columns'
+// statuses) and DIVERGED, with lastHipStatus() != 0, when it could not (no GPU, k out of range, an unsupported preconditioner).
+// BiCGStabBatch takes the IDPreconditioner or the JacobiPreconditioner; every other kind is refused.
+template <typename Preconditioner, typename T>
+inline SolverStatus BiCGStabBatch(const CSRMatrix<T>& a, T* B, T* X, int k, int maxIterations, T eps, const Preconditioner& preconditioner, SolverStatus* status) {
+	static_assert(std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value ||
+	                  std::is_base_of<typename CSRMatrix<T>::PreconditionerBase, Preconditioner>::value,
+	              "BiCGStabBatch runs the library's own preconditioners only (IDPreconditioner, JacobiPreconditioner)");
+	const smm_hip_csr* d = a.device();
+	if (!d) return SolverStatus::DIVERGED;
+	const smm_hip_precond* h = preconditioner.handle();
+	if (!std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value && !h) return SolverStatus::DIVERGED;
+	int st[SMM_HIP_MAX_RHS] = {};
+	if (detail::note(detail::Abi<T>::bicgstabBatch(d, k, B, X, maxIterations, eps, h, st)) != SMM_HIP_OK) return SolverStatus::DIVERGED;
+	for (int j = 0; status && j < k; ++j) status[j] = static_cast<SolverStatus>(st[j]);
+	return SolverStatus::SUCCESS;
+}
+template <typename T>
+inline SolverStatus BiCGStabBatch(const CSRMatrix<T>& a, T* B, T* X, int k, int maxIterations, T eps, SolverStatus* status) {
+	return BiCGStabBatch(a, B, X, k, maxIterations, eps, typename CSRMatrix<T>::IDPreconditioner(), status);
+}
+template <typename T>
+inline SolverStatus ConjugateGradientBatch(const CSRMatrix<T>& a, const T* B, const T* X0, T* X, int k, int maxIterations, T eps, SolverStatus* status) {
+	const smm_hip_csr* d = a.device();
+	if (!d) return SolverStatus::DIVERGED;
+	int st[SMM_HIP_MAX_RHS] = {};
+	if (detail::note(detail::Abi<T>::cgBatch(d, k, B, X0, X, maxIterations, eps, st)) != SMM_HIP_OK) return SolverStatus::DIVERGED;
+	for (int j = 0; status && j < k; ++j) status[j] = static_cast<SolverStatus>(st[j]);
+	return SolverStatus::SUCCESS;
 }
 
 // ref:2021-2102

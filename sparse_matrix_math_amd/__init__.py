@@ -15,14 +15,19 @@ from .host import (  # noqa: F401
     SPMV_STREAM,
     SPMV_VECTOR,
     AssemblyPlan,
+    MAX_RHS,
     BiCGStab,
+    BiCGStabBatch,
     BiCGSymmetric,
     ConjugateGradient,
+    ConjugateGradientBatch,
     CSRMatrix,
     Preconditioner,
     SolverPreconditioner,
     SolverStatus,
+    bicgstab_batch_dev,
     bicgstab_dev,
+    cg_batch_dev,
     cg_dev,
     device_info,
     dot,

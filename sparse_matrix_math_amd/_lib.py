@@ -44,6 +44,8 @@ _TYPED = {
     "smm_hip_csr_create_dev": (c_int, [c_int, c_int, _P, _P, _P, POINTER(_P)]),
     "smm_hip_spmv": (c_int, [_P, c_int, _P, _P, _P]),
     "smm_hip_spmv_dev": (c_int, [_P, c_int, _P, _P, _P, _P]),
+    "smm_hip_spmm": (c_int, [_P, c_int, c_int, _P, _P, _P]),
+    "smm_hip_spmm_dev": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
     "smm_hip_dot": (c_int, [c_int, _P, _P, _P]),
     "smm_hip_dot_dev": (c_int, [c_int, _P, _P, _P, _P]),
     "smm_hip_axpy_dev": (c_int, [c_int, "T", _P, _P, _P, _P]),
@@ -52,6 +54,10 @@ _TYPED = {
     "smm_hip_bicgstab": (c_int, [_P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicgstab_dev": (c_int, [_P, _P, _P, c_int, "T", _P, _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicgstab_functor": (c_int, [_P, _P, _P, c_int, "T", "APPLY", _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_bicgstab_batch": (c_int, [_P, c_int, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_bicgstab_batch_dev": (c_int, [_P, c_int, _P, _P, c_int, "T", _P, _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_cg_batch": (c_int, [_P, c_int, _P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_cg_batch_dev": (c_int, [_P, c_int, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicgsymmetric": (c_int, [_P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int)]),
     "smm_hip_precond_apply": (c_int, [_P, _P, _P]),
     "smm_hip_precond_apply_dev": (c_int, [_P, _P, _P, _P]),

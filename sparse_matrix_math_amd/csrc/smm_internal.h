@@ -244,6 +244,16 @@ template <typename T>
 int launchSpmv(const smm_hip_csr* m, int op, const T* lhs, const T* x, T* out, int dotMode, const T* w1, T* partials,
                const int* doneFlag, hipStream_t s, int extraFlags = 0, const T* divisor = nullptr);
 
+// Several right-hand sides at once (smm_spmm.hip): lhs / x / out / w1 are interleaved n x k blocks (element (i, j) at i * k + j),
+// 1 <= k <= SMM_HIP_MAX_RHS.  op: SMM_OP_ASSIGN / ADD / SUB, or the internal SPMV_OP_DIV (out = (A x) / divisor) and SPMM_OP_SUB_DIV
+// (out = (lhs - A x) / divisor) with `divisor` ONE vector of n elements shared by the columns (the Jacobi diagonal).  dotMode as in
+// launchSpmv, per column: column j's partial sums land at partials[j * 2 * NPART ...] (k * 2 * NPART elements in all), laid out inside
+// that block as launchSpmv lays out its single set.  Reads the handle's CSR arrays and the STREAM family's tile table only.
+template <typename T>
+int launchSpmm(const smm_hip_csr* m, int op, int k, const T* lhs, const T* x, T* out, int dotMode, const T* w1, T* partials, const int* doneFlag,
+               hipStream_t s, const T* divisor = nullptr);
+constexpr int SPMM_OP_SUB_DIV = 5;
+
 // live event timing of SpMV launches (smm_hip_profile_*): begin returns a slot or -1 when profiling is off
 int profBegin(hipStream_t s);
 void profEnd(int slot, hipStream_t s);

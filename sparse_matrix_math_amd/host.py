@@ -37,6 +37,7 @@ class SolverPreconditioner(enum.IntEnum):
 
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
+MAX_RHS = 8  # SMM_HIP_MAX_RHS: the most right-hand sides one block holds
 SPMV_AUTO, SPMV_VECTOR, SPMV_STREAM, SPMV_PATTERN = 0, 1, 2, 3
 SWEEP_AUTO, SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD = 0, 1, 2, 3
 
@@ -72,6 +73,22 @@ def _dptr(t):
     if hasattr(t, "data_ptr"):
         return ctypes.c_void_p(t.data_ptr())
     return ctypes.c_void_p(int(t))
+
+
+def _block(a, dtype, name, rows, k=None, writable=False):
+    """an interleaved block of right-hand sides: a C-contiguous (rows, k) array of `dtype`, 1 <= k <= MAX_RHS (k given: exactly that
+    many columns).  Checked here, before the library is touched.  Returns (pointer, k)."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.dtype(dtype) or a.ndim != 2 or not a.flags.c_contiguous:
+        raise TypeError(f"{name} must be a C-contiguous (n, k) numpy array of {np.dtype(dtype)}")
+    if writable and not a.flags.writeable:
+        raise TypeError(f"{name} must be writable")
+    if not 1 <= a.shape[1] <= MAX_RHS:
+        raise ValueError(f"{name} has {a.shape[1]} columns, a block holds 1 .. {MAX_RHS}")
+    if k is not None and a.shape[1] != k:
+        raise ValueError(f"{name} has {a.shape[1]} columns, the other blocks have {k}")
+    if a.shape[0] != rows:
+        raise ValueError(f"{name} has {a.shape[0]} rows, needs {rows}")
+    return a.ctypes.data_as(ctypes.c_void_p), a.shape[1]
 
 
 def init(device=0):
@@ -325,6 +342,26 @@ class CSRMatrix:
     def spmv_dev(self, op, d_lhs, d_x, d_out, stream=None):
         check(_fn("smm_hip_spmv_dev", self._suf)(self._h, int(op), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), _dptr(stream)))
 
+    # ---- several right-hand sides at once (smm_hip.h "CSR SpMM"): X is (cols, k), Lhs / Out are (rows, k), C-contiguous, k <= MAX_RHS.
+    # Additions: the reference multiplies by one vector.  Column j of Out is what rMult / rMultAdd / rMultSub give for column j alone.
+    def _spmm(self, op, lhs, mult, out):
+        pout, k = _block(out, self.dtype, "Out", self.rows, None, True)
+        px, _ = _block(mult, self.dtype, "X", self.cols, k)
+        plhs = _block(lhs, self.dtype, "Lhs", self.rows, k)[0] if op != OP_ASSIGN else ctypes.c_void_p(0)
+        check(_fn("smm_hip_spmm", self._suf)(self._h, op, k, plhs, px, pout))
+
+    def rMultBlock(self, X, Out):
+        self._spmm(OP_ASSIGN, None, X, Out)
+
+    def rMultAddBlock(self, Lhs, X, Out):
+        self._spmm(OP_ADD, Lhs, X, Out)
+
+    def rMultSubBlock(self, Lhs, X, Out):
+        self._spmm(OP_SUB, Lhs, X, Out)
+
+    def spmm_dev(self, op, k, d_lhs, d_x, d_out, stream=None):
+        check(_fn("smm_hip_spmm_dev", self._suf)(self._h, int(op), int(k), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), _dptr(stream)))
+
     def tile_info(self):
         """(tiles, nonzeros per tile, rows per tile, 1 if spmvTileKernel serves the launches) of the STREAM family's tile table"""
         v = [ctypes.c_int() for _ in range(4)]
@@ -574,6 +611,60 @@ def BiCGStab(a, b, x, maxIterations, eps, M=None, info=None):
     if info is not None:
         info.update(iterations=it.value, resnorm=res.value)
     return SolverStatus(st.value)
+
+
+def _batch_out(suf):
+    return (ctypes.c_int * MAX_RHS)(), (ctypes.c_int * MAX_RHS)(), (_CT[suf] * MAX_RHS)()
+
+
+def _batch_result(k, st, it, res, info, resname, dtype):
+    if info is not None:
+        info.update({"iterations": np.array(it[:k], dtype=np.int32), resname: np.array(res[:k], dtype=dtype)})
+    return [SolverStatus(v) for v in st[:k]]
+
+
+def BiCGStabBatch(a, B, X, maxIterations, eps, M=None, info=None):
+    """BiCGStab (ref:2191-2303) for the k columns of B at once -- an addition: B and X are C-contiguous (n, k) arrays, k <= MAX_RHS; X
+    holds the initial guesses and receives the results.  M: None or a NONE / JACOBI preconditioner.  Column j is solved as BiCGStab
+    solves it alone (its own iteration count, status and NaN behaviour).  Returns a list of k SolverStatus; `info`, when a dict,
+    receives `iterations` and `resnorm` as arrays of length k."""
+    suf = a._suf
+    pb, k = _block(B, a.dtype, "B", a.rows)
+    px, _ = _block(X, a.dtype, "X", a.rows, k, True)
+    st, it, res = _batch_out(suf)
+    check(_fn("smm_hip_bicgstab_batch", suf)(a._h, k, pb, px, int(maxIterations), a.dtype.type(eps), _mh(M), st, it, res))
+    return _batch_result(k, st, it, res, info, "resnorm", a.dtype)
+
+
+def ConjugateGradientBatch(a, B, X0, X, maxIterations, eps, info=None):
+    """ConjugateGradient (ref:2316-2398) for the k columns of B at once -- an addition: B, X0 and X are C-contiguous (n, k) arrays,
+    k <= MAX_RHS; X may be X0.  A column whose first residual already passes reports 0 iterations and is not written.  Returns a list
+    of k SolverStatus; `info`, when a dict, receives `iterations` and `resnorm2` as arrays of length k."""
+    suf = a._suf
+    pb, k = _block(B, a.dtype, "B", a.rows)
+    px0, _ = _block(X0, a.dtype, "X0", a.rows, k)
+    px, _ = _block(X, a.dtype, "X", a.rows, k, True)
+    st, it, res = _batch_out(suf)
+    check(_fn("smm_hip_cg_batch", suf)(a._h, k, pb, px0, px, int(maxIterations), a.dtype.type(eps), st, it, res))
+    return _batch_result(k, st, it, res, info, "resnorm2", a.dtype)
+
+
+def bicgstab_batch_dev(a, k, d_b, d_x, maxIterations, eps, M=None, stream=None):
+    """device-pointer BiCGStabBatch; returns ([SolverStatus] * k, iterations[k], resnorm[k]).  Synchronises `stream`."""
+    suf = a._suf
+    k = int(k)  # (the library checks the range: SMM_HIP_ERR_INVALID)
+    st, it, res = _batch_out(suf)
+    check(_fn("smm_hip_bicgstab_batch_dev", suf)(a._h, k, _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), _mh(M), _dptr(stream), st, it, res))
+    return [SolverStatus(v) for v in st[:k]], np.array(it[:k], dtype=np.int32), np.array(res[:k], dtype=a.dtype)
+
+
+def cg_batch_dev(a, k, d_b, d_x0, d_x, maxIterations, eps, stream=None):
+    """device-pointer ConjugateGradientBatch; returns ([SolverStatus] * k, iterations[k], resnorm2[k]).  Synchronises `stream`."""
+    suf = a._suf
+    k = int(k)  # (the library checks the range: SMM_HIP_ERR_INVALID)
+    st, it, res = _batch_out(suf)
+    check(_fn("smm_hip_cg_batch_dev", suf)(a._h, k, _dptr(d_b), _dptr(d_x0), _dptr(d_x), int(maxIterations), a.dtype.type(eps), _dptr(stream), st, it, res))
+    return [SolverStatus(v) for v in st[:k]], np.array(it[:k], dtype=np.int32), np.array(res[:k], dtype=a.dtype)
 
 
 def BiCGSymmetric(a, b, x, maxIterations, eps, info=None):
