@@ -20,6 +20,10 @@
  *     work unless they must return a value to the host (solvers synchronise the stream before returning their
  *     status).  Temporaries are recycled in stream order: drive one matrix from one stream at a time.
  *     Host-pointer functions run on a private non-blocking stream of the library.
+ *   - pointers: an array needs the alignment of its ELEMENT type only (4 bytes for int / float, 8 for double) -- host or device, the
+ *     arrays smm_hip_csr_create_dev_* borrows included.  A view into the middle of a larger allocation (several matrices packed into
+ *     one buffer, a slice of a vector) is a valid argument and gives the bits of the same call on an allocation of its own.  No call
+ *     reads or writes outside [p, p + n) of an array of n elements.  tests/test_gpu_device_views.py holds both.
  *   - there is NO CPU fallback: without a HIP device every call fails with SMM_HIP_ERR_NO_DEVICE.
  *   - rounding: multiply-adds are a*x+b (two roundings) like the reference's default _smm_fma (ref:28-36);
  *     a library built with -DSMM_WITH_STD_FMA uses fma(a,x,b) instead.  smm_hip_uses_std_fma() tells which.

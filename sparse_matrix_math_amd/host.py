@@ -586,6 +586,11 @@ def dot_dev(n, d_a, d_b, d_result, dtype, stream=None):
     check(_fn("smm_hip_dot_dev", _suffix(dtype))(int(n), _dptr(d_a), _dptr(d_b), _dptr(d_result), _dptr(stream)))
 
 
+def axpy_dev(n, a, d_x, d_y, d_out, dtype, stream=None):
+    """out[i] = a * x[i] + y[i] on device pointers (the update loops of ref:2245-2274); out may alias x or y"""
+    check(_fn("smm_hip_axpy_dev", _suffix(dtype))(int(n), float(a), _dptr(d_x), _dptr(d_y), _dptr(d_out), _dptr(stream)))
+
+
 def _mh(M):
     return M._h if M is not None else ctypes.c_void_p(0)
 
