@@ -446,6 +446,33 @@ int smm_hip_cg_batch_dev_f64(const smm_hip_csr* a, int k, const double* d_b, con
 int smm_hip_bicgsymmetric_f32(const smm_hip_csr* a, float* b, float* x, int maxIterations, float eps, int* solver_status, int* iterations);
 int smm_hip_bicgsymmetric_f64(const smm_hip_csr* a, double* b, double* x, int maxIterations, double eps, int* solver_status, int* iterations);
 
+/* smm_hip_cgs_*  replaces  SolverStatus ConjugateGradientSquared(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps)
+ *                                                                                                        (ref:2104-2178)
+ * The transpose-free method for general matrices: two SpMVs per pass, like BiCGStab (csrc/smm_solvers_cgs.hip).
+ * THE ONE REPAIR: the semantics are exactly ref:2110-2178 with `residualSquared` declared before the `do`, so that the loop
+ * condition reads the value the body has just computed.  As published it is declared inside the body and read in the `while`
+ * (ref:2171-2172), so the reference's template compiles only as long as nobody instantiates it.
+ * Everything else is the reference's text:
+ *   - x is in/out; maxIterations is clamped to rows, -1 means rows (ref:2111-2114);
+ *   - r = b - A x, p = u = r0 = r, rr0 = r.r0 (ref:2118-2128); the body is do { } while (r.r > eps*eps && iterations < maxIterations):
+ *     it always runs once, even for maxIterations == 0, and a NaN residual leaves the loop;
+ *   - per element q = _smm_fma(-alpha, ap, u); alphaUQ = alpha * (u + q) (an add, then a multiply); x = x + alphaUQ;
+ *     r = r - A alphaUQ; u = _smm_fma(beta, q, r); p = _smm_fma(beta, _smm_fma(beta, p, q), u) (ref:2145-2166);
+ *   - status is SUCCESS unless iterations > maxIterations (ref:2174-2177): only maxIterations == 0 gives MAX_ITERATIONS_REACHED, with
+ *     1 iteration; never DIVERGED;
+ *   - there is no breakdown test (ref:2134, 2153 leave it open): a zero ap.r0 or rr0 puts Inf / NaN into x, as in the reference.
+ * rows == 0 takes the same path as smm_hip_bicgstab_* does: the body runs once on empty vectors -- 1 iteration, and since
+ * maxIterations is clamped to 0 rows, MAX_ITERATIONS_REACHED; nothing is read or written through b / x (they may be NULL).
+ * SMM_HIP_ERR_INVALID: a null or dtype-mismatched matrix, a matrix that is not square, null vectors with rows > 0.
+ * Additive outputs (may be NULL): iterations = loop passes executed, resnorm2 = the last r.r the loop computed.
+ * In fp32 the method is fragile (the residual polynomial of BiCG is squared, rounding errors with it): see INTEGRATION.md. */
+int smm_hip_cgs_f32(const smm_hip_csr* a, float* b, float* x, int maxIterations, float eps, int* solver_status, int* iterations, float* resnorm2);
+int smm_hip_cgs_f64(const smm_hip_csr* a, double* b, double* x, int maxIterations, double eps, int* solver_status, int* iterations, double* resnorm2);
+int smm_hip_cgs_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, int maxIterations, float eps, smm_hip_stream stream, int* solver_status,
+                        int* iterations, float* resnorm2);
+int smm_hip_cgs_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, smm_hip_stream stream, int* solver_status,
+                        int* iterations, double* resnorm2);
+
 /* ---- preconditioners: `int apply(const T* rhs, T* x) const noexcept` (ref:1173-1235) --------------------------
  * create: replaces CSRMatrix<T>::getPreconditioner<kind>() (ref:1643-1651) / IC0Preconditioner::init (ref:1798).
  * The matrix must outlive the preconditioner (the reference holds a const CSRMatrix&).  Structural failures

@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::loadMatrix
 //
 // compiles against this header unchanged and runs those calls on an MI355X: same names, same argument order and meaning,
 // same return values (SolverStatus; int != 0 on failure for init / apply).  Matrix assembly (TripletMatrix, CSR arrays)
@@ -68,6 +68,7 @@ struct Abi<float> {
 		return smm_hip_bicgstab_f32(a, b, x, it, eps, M, st, nullptr, nullptr);
 	}
 	static int bicgsym(const smm_hip_csr* a, float* b, float* x, int it, float eps, int* st) { return smm_hip_bicgsymmetric_f32(a, b, x, it, eps, st, nullptr); }
+	static int cgs(const smm_hip_csr* a, float* b, float* x, int it, float eps, int* st) { return smm_hip_cgs_f32(a, b, x, it, eps, st, nullptr, nullptr); }
 	static int apply(const smm_hip_precond* M, const float* r, float* x) { return smm_hip_precond_apply_f32(M, r, x); }
 	static int scale(smm_hip_csr* m, float a) { return smm_hip_csr_scale_f32(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, float a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f32(m, a, o, nullptr); }
@@ -96,6 +97,7 @@ struct Abi<double> {
 		return smm_hip_bicgstab_f64(a, b, x, it, eps, M, st, nullptr, nullptr);
 	}
 	static int bicgsym(const smm_hip_csr* a, double* b, double* x, int it, double eps, int* st) { return smm_hip_bicgsymmetric_f64(a, b, x, it, eps, st, nullptr); }
+	static int cgs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int* st) { return smm_hip_cgs_f64(a, b, x, it, eps, st, nullptr, nullptr); }
 	static int apply(const smm_hip_precond* M, const double* r, double* x) { return smm_hip_precond_apply_f64(M, r, x); }
 	static int scale(smm_hip_csr* m, double a) { return smm_hip_csr_scale_f64(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, double a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f64(m, a, o, nullptr); }
@@ -894,6 +896,16 @@ inline SolverStatus BiCGSymmetric(const CSRMatrix<T>& a, T* b, T* x, int maxIter
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const int rc = d ? detail::Abi<T>::bicgsym(d, b, x, maxIterations, eps, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// ref:2104-2178, with `residualSquared` declared before the `do` so that the loop condition reads the value the body has just computed
+// (as published, ref:2171-2172, the template cannot be instantiated): the one repair, stated in smm_hip.h
+template <typename T>
+inline SolverStatus ConjugateGradientSquared(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const int rc = d ? detail::Abi<T>::cgs(d, b, x, maxIterations, eps, &st) : SMM_HIP_ERR_NO_DEVICE;
 	return detail::toStatus(rc, st);
 }
 

@@ -21,6 +21,7 @@ from .host import (  # noqa: F401
     BiCGSymmetric,
     ConjugateGradient,
     ConjugateGradientBatch,
+    ConjugateGradientSquared,
     CSRMatrix,
     Preconditioner,
     SolverPreconditioner,
@@ -29,6 +30,7 @@ from .host import (  # noqa: F401
     bicgstab_dev,
     cg_batch_dev,
     cg_dev,
+    cgs_dev,
     device_info,
     dot,
     dot_dev,

@@ -59,6 +59,8 @@ _TYPED = {
     "smm_hip_cg_batch": (c_int, [_P, c_int, _P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_cg_batch_dev": (c_int, [_P, c_int, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicgsymmetric": (c_int, [_P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int)]),
+    "smm_hip_cgs": (c_int, [_P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_cgs_dev": (c_int, [_P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_precond_apply": (c_int, [_P, _P, _P]),
     "smm_hip_precond_apply_dev": (c_int, [_P, _P, _P, _P]),
     "smm_hip_precond_apply_spmv": (c_int, [_P, _P, _P]),

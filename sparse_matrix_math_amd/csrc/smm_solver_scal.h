@@ -45,5 +45,11 @@ __device__ __forceinline__ T sumPartsAll(const T* __restrict__ partials, T* red5
 	return v;
 }
 
+// launches an update kernel templated on <T, NT> with the cache policy updateNT chose (T and TPB are those of the unit that expands it)
+#define SMM_LAUNCH_UPDATE(KERNEL, NTFLAG, GRID, STREAM, ...)                    \
+	do {                                                                       \
+		if (NTFLAG) KERNEL<T, true><<<(GRID), TPB, 0, (STREAM)>>>(__VA_ARGS__); \
+		else KERNEL<T, false><<<(GRID), TPB, 0, (STREAM)>>>(__VA_ARGS__);       \
+	} while (0)
 
 }  // namespace smm

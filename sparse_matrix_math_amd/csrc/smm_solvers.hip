@@ -493,12 +493,6 @@ bool updateNT(long long n, size_t elemBytes, int vectors) {
 	return static_cast<double>(n) * static_cast<double>(elemBytes) * vectors > 192.0 * 1024 * 1024;
 }
 
-#define SMM_LAUNCH_UPDATE(KERNEL, NTFLAG, GRID, STREAM, ...)                    \
-	do {                                                                       \
-		if (NTFLAG) KERNEL<T, true><<<(GRID), TPB, 0, (STREAM)>>>(__VA_ARGS__); \
-		else KERNEL<T, false><<<(GRID), TPB, 0, (STREAM)>>>(__VA_ARGS__);       \
-	} while (0)
-
 static int checkInterval(int it) { return std::max(4, std::min(64, it / 4)); }
 
 // from how many bytes per vector CG defers its x update (cgLazyXP): where five vectors no longer fit the 256 MB Infinity Cache the passes

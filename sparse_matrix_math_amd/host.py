@@ -2,7 +2,8 @@
 
 Names, argument order and error behaviour follow include/sparse_matrix_math.h of vasil-pashov/sparse_matrix_math:
 CSRMatrix.rMult / rMultAdd / rMultSub (ref:1501-1515), getPreconditioner (ref:1643-1651), ConjugateGradient
-(ref:2316-2398, IC0 overload ref:2414-2505), BiCGStab (ref:2191-2303), BiCGSymmetric (ref:2021-2102), SolverStatus
+(ref:2316-2398, IC0 overload ref:2414-2505), BiCGStab (ref:2191-2303), BiCGSymmetric (ref:2021-2102), ConjugateGradientSquared
+(ref:2104-2178), SolverStatus
 (ref:2010-2014), SolverPreconditioner (ref:1002-1006).  Vectors are numpy arrays in host memory, like the
 reference's raw T* arguments; the `*_dev` helpers take device pointers (ints or objects with .data_ptr()) for
 callers that keep their data in HBM (bench.py, the multi-GPU driver).
@@ -681,6 +682,28 @@ def BiCGSymmetric(a, b, x, maxIterations, eps, info=None):
     if info is not None:
         info.update(iterations=it.value)
     return SolverStatus(st.value)
+
+
+def ConjugateGradientSquared(a, b, x, maxIterations, eps, info=None):
+    """ref:2104-2178 with `residualSquared` declared before the `do` (the one repair, include/smm_hip.h).  For general matrices; x is the
+    initial guess and receives the result.  The body always runs once; no breakdown test: a zero ap.r0 or rr0 leaves Inf / NaN in x.
+    `info`, when a dict, receives iterations and resnorm2 (the last r.r)."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_cgs", suf)(a._h, _host(b, a.dtype, "b", a.rows), _host(x, a.dtype, "x", a.rows, True), int(maxIterations),
+                                  a.dtype.type(eps), ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+    if info is not None:
+        info.update(iterations=it.value, resnorm2=res.value)
+    return SolverStatus(st.value)
+
+
+def cgs_dev(a, d_b, d_x, maxIterations, eps, stream=None):
+    """device-pointer ConjugateGradientSquared; returns (SolverStatus, iterations, resnorm2).  Synchronises `stream`."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_cgs_dev", suf)(a._h, _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), _dptr(stream), ctypes.byref(st),
+                                      ctypes.byref(it), ctypes.byref(res)))
+    return SolverStatus(st.value), it.value, res.value
 
 
 def cg_dev(a, d_b, d_x0, d_x, maxIterations, eps, M=None, stream=None):
