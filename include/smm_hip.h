@@ -311,6 +311,37 @@ int smm_hip_assembly_refill_f64(const smm_hip_assembly* plan, smm_hip_csr* m, co
 int smm_hip_assembly_refill_dev_f32(const smm_hip_assembly* plan, smm_hip_csr* m, const float* d_values, int mode, smm_hip_stream stream);
 int smm_hip_assembly_refill_dev_f64(const smm_hip_assembly* plan, smm_hip_csr* m, const double* d_values, int mode, smm_hip_stream stream);
 
+/* ---- the TRANSPOSE of a matrix, built on the device (csrc/smm_transpose.hip); additions with no counterpart in the reference --------------
+ * transpose_create: *out is the cols x rows matrix Aᵀ of `a`'s dtype.  It owns its three device arrays and does not depend on `a`'s
+ *   lifetime -- an smm_hip_csr like any other (AUTO kernel choice, PATTERN analysis on first use, edits, preconditioners,
+ *   smm_hip_csr_same_pattern).  May synchronise `stream`.
+ * Pattern: row j of Aᵀ holds the entries of column j of A with columns (A's rows) ascending -- a stable sort of the entries by column.
+ *   start[cols + 1], positions[nnz] and what smm_hip_csr_info reports are those of smm_hip_csr_create_* for the same arrays built on the
+ *   host.  Rectangular matrices, empty rows and columns, nnz == 0, rows == 0 or cols == 0 are legal.
+ * Values: copied bit for bit (-0.0 stays -0.0, NaN payloads are kept).  No arithmetic and no floating-point atomics: the result does not
+ *   depend on the launch geometry.
+ * A column outside [0, cols), or a start[] that does not ascend from 0, is found by a flag on the device before it is used as an address:
+ *   SMM_HIP_ERR_INVALID, never a fault; nothing is created.
+ * transpose_refresh_*: `at` must have been made by transpose_create from a matrix with `a`'s pattern; the library keeps the permutation
+ *   perm[nnz] (4 bytes per entry) in `at`.  values_T[k] = a.values[perm[k]]: one gather pass, asynchronous on `stream`, and a value edit of
+ *   `at` with exactly the rules of smm_hip_csr_set_values_dev_* (what was derived from the pattern stays, no analysis on the next SpMV,
+ *   constant diagonals re-verified, the slots / sweep / single-launch copies follow).  Cost: nnz (2 s + 4) bytes (s = sizeof(T)) plus the
+ *   locality of the gather -- local for banded matrices, whose perm[k] stays within the band's width of k.
+ *   SMM_HIP_ERR_INVALID, nothing changed: `at` was not made by transpose_create; a dtype differs; `a`'s rows / cols / nnz do not match; `a`
+ *   has another pattern than the matrix `at` was built from.  The verdict on the pattern is cached in `a` like that of
+ *   smm_hip_csr_same_pattern (the source handle itself costs nothing; another handle one device pass and a synchronisation, once).
+ *   Distributed handles are not covered.
+ * is_symmetric (synchronous): a matrix that is not square gives 0 / 0.  *pattern_symmetric = 1 when start[] / positions[] of Aᵀ equal those
+ *   of A; *values_symmetric = 1 when in addition every values_T[k] == values[k] by IEEE == (-0.0 equals +0.0, a NaN is never equal).
+ *   Builds a temporary transpose and frees it; either output may be NULL.
+ * get_pattern (synchronous): start[rows + 1] and positions[nnz] copied to host memory (either may be NULL), the companion of
+ *   smm_hip_csr_get_values_*: how a caller reads a matrix the device built. */
+int smm_hip_csr_transpose_create(const smm_hip_csr* a, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_transpose_refresh_f32(smm_hip_csr* at, const smm_hip_csr* a, smm_hip_stream stream);
+int smm_hip_csr_transpose_refresh_f64(smm_hip_csr* at, const smm_hip_csr* a, smm_hip_stream stream);
+int smm_hip_csr_is_symmetric(const smm_hip_csr* a, int* pattern_symmetric, int* values_symmetric);
+int smm_hip_csr_get_pattern(const smm_hip_csr* m, int* start, int* positions);
+
 /* ---- SpMV: CSRMatrix<T>::rMult / rMultAdd / rMultSub (ref:1458-1515) -------------------------------------- */
 /* out[i] = op(lhs[i], sum_k values[k]*x[positions[k]]); empty rows give op(lhs[i],0) (ref:1479-1483);
  * out may alias lhs, x must not alias out (ref:1503).  lhs is ignored for SMM_OP_ASSIGN. */
@@ -445,6 +476,42 @@ int smm_hip_cg_batch_dev_f64(const smm_hip_csr* a, int k, const double* d_b, con
 /* BiCGSymmetric (ref:2021-2102): same kernels as CG plus the DIVERGED heuristics (ref:2056-2058, 2079-2081) */
 int smm_hip_bicgsymmetric_f32(const smm_hip_csr* a, float* b, float* x, int maxIterations, float eps, int* solver_status, int* iterations);
 int smm_hip_bicgsymmetric_f64(const smm_hip_csr* a, double* b, double* x, int maxIterations, double eps, int* solver_status, int* iterations);
+
+/* smm_hip_bicg_*: BiCG for GENERAL matrices -- an addition: BiCGSymmetric (ref:2021-2102) is this method with Aᵀ = A assumed; here the
+ * shadow sequence is written out and runs on `at` (csrc/smm_solvers_bicg.hip).
+ * `at` is Aᵀ, e.g. from smm_hip_csr_transpose_create.  NULL: the library builds a transpose for the duration of the solve (a device sort
+ *   of the entries and 2 nnz (s + 4) bytes of memory per call: keep a transpose when solving more than once).  `a` itself: the caller
+ *   asserts symmetry.  Checked, SMM_HIP_ERR_INVALID: the dtypes, at.rows == a.cols, at.cols == a.rows, equal nnz, `a` square.  THAT `at`
+ *   REALLY IS THE TRANSPOSE IS THE CALLER'S CONTRACT: another matrix of that shape gives another (meaningless) iteration, not an error.
+ * Semantics (x in/out):
+ *   maxIterations = min(maxIterations, rows); -1 -> rows                                                   (ref:2030-2033)
+ *   r = b - A x;  rt = r;  p = r;  pt = rt;  rho = rt.r;  rr = r.r;  iterations = 0
+ *   do {
+ *     ap = A p;  atp = At pt;  denom = sum ap[i] * pt[i]
+ *     if (eps > |denom| && rr > 1) return DIVERGED                                                         (ref:2056)
+ *     alpha = rho / denom
+ *     x[i] += alpha * p[i];  r[i] -= alpha * ap[i];  rt[i] -= alpha * atp[i]       (plain forms, ref:2069-2070, not _smm_fma)
+ *     newRho = rt.r;  newRR = r.r
+ *     if (newRR > 1 && rr < eps) return DIVERGED                                                           (ref:2079)
+ *     beta = newRho / rho
+ *     p[i] = r[i] + beta * p[i];  pt[i] = rt[i] + beta * pt[i]                                             (ref:2091)
+ *     rho = newRho;  rr = newRR;  iterations++
+ *   } while (rr > eps * eps && iterations < maxIterations)
+ *   status: MAX_ITERATIONS_REACHED iff iterations > maxIterations, else SUCCESS                            (ref:2098-2100)
+ * No further breakdown test: rho == 0 puts Inf / NaN into x, as in smm_hip_cgs_*; a NaN rr leaves the loop.  rows == 0 behaves as
+ * smm_hip_cgs_* does (one pass over empty vectors, MAX_ITERATIONS_REACHED).  Additive outputs (may be NULL): iterations, resnorm2 = the
+ * last rr.
+ * THE BIT RULE: when `at` gives the bits of `a` -- the same handle, or a built transpose of a symmetric matrix -- rt == r, pt == p and
+ * rho == rr hold bit for bit and the solve returns the status, iteration count and x of smm_hip_bicgsymmetric_* bit for bit: the sums
+ * are partitioned and the updates written exactly as there. */
+int smm_hip_bicg_f32(const smm_hip_csr* a, const smm_hip_csr* at, float* b, float* x, int maxIterations, float eps, int* solver_status, int* iterations,
+                     float* resnorm2);
+int smm_hip_bicg_f64(const smm_hip_csr* a, const smm_hip_csr* at, double* b, double* x, int maxIterations, double eps, int* solver_status, int* iterations,
+                     double* resnorm2);
+int smm_hip_bicg_dev_f32(const smm_hip_csr* a, const smm_hip_csr* at, const float* d_b, float* d_x, int maxIterations, float eps, smm_hip_stream stream,
+                         int* solver_status, int* iterations, float* resnorm2);
+int smm_hip_bicg_dev_f64(const smm_hip_csr* a, const smm_hip_csr* at, const double* d_b, double* d_x, int maxIterations, double eps, smm_hip_stream stream,
+                         int* solver_status, int* iterations, double* resnorm2);
 
 /* smm_hip_cgs_*  replaces  SolverStatus ConjugateGradientSquared(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps)
  *                                                                                                        (ref:2104-2178)

@@ -6,6 +6,7 @@
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
 //     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::loadMatrix
+//     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric)
 //
 // compiles against this header unchanged and runs those calls on an MI355X: same names, same argument order and meaning,
 // same return values (SolverStatus; int != 0 on failure for init / apply).  Matrix assembly (TripletMatrix, CSR arrays)
@@ -69,6 +70,7 @@ struct Abi<float> {
 	}
 	static int bicgsym(const smm_hip_csr* a, float* b, float* x, int it, float eps, int* st) { return smm_hip_bicgsymmetric_f32(a, b, x, it, eps, st, nullptr); }
 	static int cgs(const smm_hip_csr* a, float* b, float* x, int it, float eps, int* st) { return smm_hip_cgs_f32(a, b, x, it, eps, st, nullptr, nullptr); }
+	static int bicg(const smm_hip_csr* a, const smm_hip_csr* at, float* b, float* x, int it, float eps, int* st) { return smm_hip_bicg_f32(a, at, b, x, it, eps, st, nullptr, nullptr); }
 	static int apply(const smm_hip_precond* M, const float* r, float* x) { return smm_hip_precond_apply_f32(M, r, x); }
 	static int scale(smm_hip_csr* m, float a) { return smm_hip_csr_scale_f32(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, float a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f32(m, a, o, nullptr); }
@@ -98,6 +100,7 @@ struct Abi<double> {
 	}
 	static int bicgsym(const smm_hip_csr* a, double* b, double* x, int it, double eps, int* st) { return smm_hip_bicgsymmetric_f64(a, b, x, it, eps, st, nullptr); }
 	static int cgs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int* st) { return smm_hip_cgs_f64(a, b, x, it, eps, st, nullptr, nullptr); }
+	static int bicg(const smm_hip_csr* a, const smm_hip_csr* at, double* b, double* x, int it, double eps, int* st) { return smm_hip_bicg_f64(a, at, b, x, it, eps, st, nullptr, nullptr); }
 	static int apply(const smm_hip_precond* M, const double* r, double* x) { return smm_hip_precond_apply_f64(M, r, x); }
 	static int scale(smm_hip_csr* m, double a) { return smm_hip_csr_scale_f64(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, double a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f64(m, a, o, nullptr); }
@@ -529,6 +532,39 @@ public:
 		dev = d;
 		return 0;
 	}
+	// addition: this matrix becomes the transpose of `a`, built on the GPU through a's device mirror (smm_hip.h "the TRANSPOSE of a matrix":
+	// row j holds column j's entries, source rows ascending; values bit for bit); the host arrays are filled from the device result as
+	// init(plan, values) fills them, and the built handle becomes this matrix's mirror.  Returns 0, or the SMM_HIP_* status (also in
+	// lastHipStatus()) with the matrix left empty.  SMM::transpose(a, out) is this call.
+	int initTransposeOf(const CSRMatrix& a) noexcept {
+		release();
+		values.reset();
+		positions.reset();
+		start.reset();
+		denseRowCount = denseColCount = firstActiveStart = 0;
+		const smm_hip_csr* src = a.device();
+		if (!src) return detail::note(a.start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(smm_hip_csr_transpose_create(src, nullptr, &d)) != SMM_HIP_OK) return lastHipStatus();
+		const int rows = a.denseColCount, nnz = a.getNonZeroCount();
+		std::unique_ptr<T[]> v(new T[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> p(new int[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> s(new int[rows + 1]());
+		int abi = smm_hip_csr_get_pattern(d, s.get(), p.get());
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(d, v.get());
+		if (detail::note(abi) != SMM_HIP_OK) {
+			smm_hip_csr_destroy(d);
+			return abi;
+		}
+		values = std::move(v);
+		positions = std::move(p);
+		start = std::move(s);
+		denseRowCount = rows;
+		denseColCount = a.denseRowCount;
+		computeFirstActive();
+		dev = d;
+		return 0;
+	}
 	// addition: new values for a matrix made by init(plan, ...) from the same plan -- those of init(plan, valuesIn), or added to the present
 	// ones (add) -- in one device pass; the pattern and what the library derived from it stay.  Non-zero (the SMM_HIP_* status): not this
 	// plan's matrix, no GPU; nothing changed then.
@@ -906,6 +942,40 @@ inline SolverStatus ConjugateGradientSquared(const CSRMatrix<T>& a, T* b, T* x, 
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const int rc = d ? detail::Abi<T>::cgs(d, b, x, maxIterations, eps, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// ---- additions with no counterpart in the reference: the transpose, the symmetry check and BiCG for general matrices (smm_hip.h) ----
+// out becomes Aᵀ, built on the GPU (CSRMatrix::initTransposeOf); 0, or the SMM_HIP_* status with out left empty
+template <typename T>
+inline int transpose(const CSRMatrix<T>& a, CSRMatrix<T>& out) noexcept {
+	return out.initTransposeOf(a);
+}
+// the pattern equals the transpose's and every value equals its mirror image by IEEE == (a NaN never does); false also when the check
+// could not run (lastHipStatus() != 0 then)
+template <typename T>
+inline bool isSymmetric(const CSRMatrix<T>& a) noexcept {
+	const smm_hip_csr* d = a.device();
+	int pattern = 0, vals = 0;
+	if (!d || detail::note(smm_hip_csr_is_symmetric(d, &pattern, &vals)) != SMM_HIP_OK) return false;
+	return pattern != 0 && vals != 0;
+}
+// BiCGSymmetric's text (ref:2021-2102) with the shadow sequence on `at`, the transpose of `a` (SMM::transpose): for matrices that are not
+// symmetric.  That `at` is the transpose is the caller's contract; `a` itself as `at` asserts symmetry and gives BiCGSymmetric's bits.
+template <typename T>
+inline SolverStatus BiCG(const CSRMatrix<T>& a, const CSRMatrix<T>& at, T* b, T* x, int maxIterations, T eps) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_csr* dt = &at == &a ? d : at.device();
+	const int rc = d && dt ? detail::Abi<T>::bicg(d, dt, b, x, maxIterations, eps, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+// ... with a transpose the library builds for the duration of the solve (a device sort per call: keep one when solving more than once)
+template <typename T>
+inline SolverStatus BiCG(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const int rc = d ? detail::Abi<T>::bicg(d, nullptr, b, x, maxIterations, eps, &st) : SMM_HIP_ERR_NO_DEVICE;
 	return detail::toStatus(rc, st);
 }
 

@@ -21,6 +21,7 @@ from .host import (  # noqa: F401
     BiCGSymmetric,
     ConjugateGradient,
     ConjugateGradientBatch,
+    BiCG,
     ConjugateGradientSquared,
     CSRMatrix,
     Preconditioner,
@@ -30,6 +31,7 @@ from .host import (  # noqa: F401
     bicgstab_dev,
     cg_batch_dev,
     cg_dev,
+    bicg_dev,
     cgs_dev,
     device_info,
     dot,

@@ -61,6 +61,8 @@ _TYPED = {
     "smm_hip_bicgsymmetric": (c_int, [_P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int)]),
     "smm_hip_cgs": (c_int, [_P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_cgs_dev": (c_int, [_P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_bicg": (c_int, [_P, _P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_bicg_dev": (c_int, [_P, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_precond_apply": (c_int, [_P, _P, _P]),
     "smm_hip_precond_apply_dev": (c_int, [_P, _P, _P, _P]),
     "smm_hip_precond_apply_spmv": (c_int, [_P, _P, _P]),
@@ -93,6 +95,7 @@ _TYPED = {
     "smm_hip_assembly_csr_create_dev": (c_int, [_P, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_refill": (c_int, [_P, _P, _P, c_int]),
     "smm_hip_assembly_refill_dev": (c_int, [_P, _P, _P, c_int, _P]),
+    "smm_hip_csr_transpose_refresh": (c_int, [_P, _P, _P]),
 }
 
 
@@ -123,6 +126,9 @@ _PLAIN = {
     "smm_hip_csr_pattern_slots": (c_int, [_P, c_int]),
     "smm_hip_set_pattern_sweep_rows": (c_int, [c_int]),
     "smm_hip_csr_same_pattern": (c_int, [_P, _P, POINTER(c_int)]),
+    "smm_hip_csr_transpose_create": (c_int, [_P, _P, POINTER(_P)]),
+    "smm_hip_csr_is_symmetric": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
+    "smm_hip_csr_get_pattern": (c_int, [_P, _P, _P]),
     "smm_hip_assembly_create": (c_int, [c_int, c_int, c_longlong, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_create_dev": (c_int, [c_int, c_int, c_longlong, _P, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_longlong), POINTER(c_int), POINTER(c_int)]),

@@ -492,6 +492,22 @@ int valuesChanged(smm_hip_csr* m, hipStream_t s) {
 
 }  // namespace
 
+unsigned long long csrUid(const smm_hip_csr* m) { return uidOf(m); }
+
+int csrPatternVerdict(const smm_hip_csr* a, unsigned long long uid) {
+	if (uidOf(a) == uid) return 1;
+	std::lock_guard<std::mutex> lock(const_cast<smm_hip_csr*>(a)->editMutex);
+	for (const auto& e : a->patternSeen) {
+		if (e.first == uid) return e.second ? 1 : 0;
+	}
+	return -1;
+}
+
+void csrPatternRecord(const smm_hip_csr* a, unsigned long long uid, bool same) {
+	std::lock_guard<std::mutex> lock(const_cast<smm_hip_csr*>(a)->editMutex);
+	const_cast<smm_hip_csr*>(a)->patternSeen.emplace_back(uid, same);
+}
+
 int csrValuesEdited(smm_hip_csr* m, hipStream_t s) {
 	return m->dtype == SMM_DTYPE_F32 ? valuesEdited<float>(m, s, EDIT_OTHER, 0.f, nullptr) : valuesEdited<double>(m, s, EDIT_OTHER, 0.0, nullptr);
 }

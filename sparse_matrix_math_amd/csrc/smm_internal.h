@@ -213,6 +213,10 @@ struct smm_hip_csr {
 	std::vector<std::pair<unsigned long long, bool>> patternSeen;
 	// the stamp of the assembly plan that created this matrix (smm_assembly.hip; 0: none did): what smm_hip_assembly_refill_* looks for
 	unsigned long long assemblyStamp = 0;
+	// a transpose built by smm_hip_csr_transpose_create (smm_transpose.hip): values[k] = source.values[d_tperm[k]] (nnz entries, owned) and the
+	// uid of the handle it was built from (0: not a transpose); smm_hip_csr_transpose_refresh_* gathers through d_tperm
+	int* d_tperm = nullptr;
+	unsigned long long transposeOf = 0;
 };
 
 struct smm_hip_precond {
@@ -326,6 +330,14 @@ void planMarch(smm_hip_csr* m);
 int refreshResEll(smm_hip_csr* a, hipStream_t s);
 // values[] of a ready matrix was rewritten on `s` by another unit (smm_assembly.hip): the path of smm_hip_csr_values_changed_*
 int csrValuesEdited(smm_hip_csr* m, hipStream_t s);
+// the pattern-comparison cache of the value edits (smm_csr_update.hip), for units that compare a pattern with one that may be gone:
+// csrUid -- the handle's number (drawn on first demand, never reused); csrPatternVerdict -- 1 / 0 what `a` has on record about the
+// pattern numbered `uid`, -1 nothing; csrPatternRecord files a verdict in `a`
+unsigned long long csrUid(const smm_hip_csr* m);
+int csrPatternVerdict(const smm_hip_csr* a, unsigned long long uid);
+void csrPatternRecord(const smm_hip_csr* a, unsigned long long uid, bool same);
+// Aᵀ as a handle of its own (smm_transpose.hip); may synchronise `s`
+int csrTransposeCreate(const smm_hip_csr* a, hipStream_t s, smm_hip_csr** out);
 // the wave-sliced value copy of the PATTERN slots kernel (smm_spmv_slots.hip).  ensurePatternSlots: build it if this launch would use it
 // (caller holds tileMutex; false: stay on the tile kernel); refreshPatternSlots: rewrite it in place after an edit (asynchronous, under
 // tileMutex); patternSlotsChosen / patternSlotsBytes: the launch's choice and its bytes, for smm_hip_csr_kernel_desc

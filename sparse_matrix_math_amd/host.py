@@ -474,6 +474,34 @@ class CSRMatrix:
         check(_fn("smm_hip_csr_values_changed", self._suf)(self._h, _dptr(stream)))
         self._edited(stream)
 
+    # ---- the transpose, built on the device (smm_hip.h "the TRANSPOSE of a matrix") ----
+    def transpose(self, stream=None):
+        """Aᵀ as a new CSRMatrix that owns its arrays and does not need this one afterwards: row j holds column j's entries, source rows
+        ascending; values bit for bit.  May synchronise `stream`."""
+        h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_csr_transpose_create(self._h, _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, self.dtype)
+
+    def transpose_refresh(self, A, stream=None):
+        """called on a matrix made by transpose(): take over the present values of A (the source, or a matrix with its pattern) in one
+        gather pass -- a value edit of this matrix.  SmmHipError (SMM_HIP_ERR_INVALID, nothing changed) for any other pair."""
+        check(_fn("smm_hip_csr_transpose_refresh", self._suf)(self._h, A._h, _dptr(stream)))
+        self._edited(stream)
+
+    def isSymmetric(self):
+        """(pattern, values): the pattern equals the transpose's; in addition every value equals its mirror image by IEEE == (a NaN never
+        does).  (False, False) for a matrix that is not square."""
+        p, v = ctypes.c_int(), ctypes.c_int()
+        check(_lib.load().smm_hip_csr_is_symmetric(self._h, ctypes.byref(p), ctypes.byref(v)))
+        return bool(p.value), bool(v.value)
+
+    def get_pattern(self):
+        """(start[rows + 1], positions[nnz]) copied from the device"""
+        start = np.empty(self.rows + 1, dtype=np.int32)
+        positions = np.empty(self.nnz, dtype=np.int32)
+        check(_lib.load().smm_hip_csr_get_pattern(self._h, _host(start, np.int32, "start"), _host(positions, np.int32, "positions")))
+        return start, positions
+
     def spmv_fused_dev(self, op, d_lhs, d_x, d_out, dot_mode, d_w1, d_partials, stream=None, finish=False):
         """SpMV with the dot products of the fresh out[] in its epilogue (dot_mode 1: out.w1; 2: out.out and out.w1).  finish=False:
         d_partials receives 2 x partials_count() per-workgroup sums; finish=True: d_partials is a finishing buffer of finish_len()
@@ -703,6 +731,28 @@ def cgs_dev(a, d_b, d_x, maxIterations, eps, stream=None):
     st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
     check(_fn("smm_hip_cgs_dev", suf)(a._h, _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), _dptr(stream), ctypes.byref(st),
                                       ctypes.byref(it), ctypes.byref(res)))
+    return SolverStatus(st.value), it.value, res.value
+
+
+def BiCG(a, b, x, maxIterations, eps, at=None, info=None):
+    """BiCG for general matrices: BiCGSymmetric's text (ref:2021-2102) with the shadow sequence on `at`, the transpose (a.transpose()).
+    at=None builds one for the duration of the solve; at=a asserts symmetry and gives BiCGSymmetric's bits.  That `at` is the transpose
+    is trusted.  x is the initial guess and receives the result; `info`, when a dict, receives iterations and resnorm2 (the last r.r)."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_bicg", suf)(a._h, _mh(at), _host(b, a.dtype, "b", a.rows), _host(x, a.dtype, "x", a.rows, True), int(maxIterations),
+                                   a.dtype.type(eps), ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+    if info is not None:
+        info.update(iterations=it.value, resnorm2=res.value)
+    return SolverStatus(st.value)
+
+
+def bicg_dev(a, d_b, d_x, maxIterations, eps, at=None, stream=None):
+    """device-pointer BiCG; returns (SolverStatus, iterations, resnorm2).  Synchronises `stream`."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_bicg_dev", suf)(a._h, _mh(at), _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), _dptr(stream), ctypes.byref(st),
+                                       ctypes.byref(it), ctypes.byref(res)))
     return SolverStatus(st.value), it.value, res.value
 
 
