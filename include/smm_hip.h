@@ -540,6 +540,54 @@ int smm_hip_cgs_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, int 
 int smm_hip_cgs_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, smm_hip_stream stream, int* solver_status,
                         int* iterations, double* resnorm2);
 
+/* smm_hip_gmres_*: restarted GMRES(restart) with right preconditioning -- an addition, the reference has no GMRES
+ * (csrc/smm_solvers_gmres.hip; the definition, line by line, is tests/gmres_restatement.py).
+ * For general matrices.  Its residual never grows, it needs no transpose and divides by no inner product that can vanish.
+ * Semantics (x in/out; `iterations` counts Arnoldi steps):
+ *   maxIterations < 0 means rows; there is no other clamp (a restarted run may need more than `rows` steps)
+ *   r = b - A x;  rr = r.r
+ *   while (rr > eps*eps && iterations < maxIterations && not DIVERGED) {              -- a cycle
+ *     beta = sqrt(rr);  v_0 = r / beta;  g = (beta, 0, ...)
+ *     for j = 0 .. restart-1:
+ *       w = A M^-1 v_j                                              (right preconditioning: the residual tested is the true one)
+ *       twice (classical Gram-Schmidt): h_i = v_i.w for all i <= j from the same w; w = _smm_fma(-h_i, v_i, w), i ascending
+ *       H[i][j] = the sum of the two passes' h_i;  H[j+1][j] = sqrt(w.w);  the earlier rotations are applied to the column
+ *       d = sqrt(H[j][j]^2 + H[j+1][j]^2);  iterations++;  d == 0 or not finite: the column is dropped, DIVERGED, the cycle ends
+ *       the new rotation (cs = H[j][j] / d, sn = H[j+1][j] / d) is applied to the column and to g
+ *       H[j+1][j] != 0: v_{j+1} = w / H[j+1][j]
+ *       the cycle ends when !(g[j+1]^2 > eps*eps), iterations >= maxIterations or H[j+1][j] == 0
+ *     y by back-substitution;  x = x + M^-1 (sum_i y_i v_i);  r = b - A x;  rr = r.r
+ *   }
+ *   status: DIVERGED if a column was dropped or rr is not finite; else SUCCESS if rr <= eps*eps; else MAX_ITERATIONS_REACHED
+ * A solve that starts with rr <= eps*eps (an exact x included) returns x untouched, 0 iterations, SUCCESS.  rows == 0: SUCCESS, 0
+ * iterations, nothing is read or written through b / x.  A matrix whose stored values are all zero: DIVERGED after 1 step, x untouched.
+ * M: NULL, or any kind smm_hip_bicgstab_* accepts (JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS created for `a`).
+ * Memory: (restart + 1) * rows elements for the basis (leading dimension rounded up to 64) plus two vectors.
+ * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one solve give the same bits.
+ * SMM_HIP_ERR_INVALID: restart outside 1 .. SMM_GMRES_MAX_RESTART, a null or dtype-mismatched matrix, a matrix that is not square,
+ * null vectors with rows > 0, a preconditioner of another matrix or kind.
+ * Additive outputs (may be NULL, like solver_status): iterations, resnorm2 = the last rr. */
+#define SMM_GMRES_MAX_RESTART 64
+int smm_hip_gmres_f32(const smm_hip_csr* a, float* b, float* x, int maxIterations, float eps, int restart, const smm_hip_precond* M, int* solver_status,
+                      int* iterations, float* resnorm2);
+int smm_hip_gmres_f64(const smm_hip_csr* a, double* b, double* x, int maxIterations, double eps, int restart, const smm_hip_precond* M, int* solver_status,
+                      int* iterations, double* resnorm2);
+int smm_hip_gmres_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, int maxIterations, float eps, int restart, const smm_hip_precond* M,
+                          smm_hip_stream stream, int* solver_status, int* iterations, float* resnorm2);
+int smm_hip_gmres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, int restart, const smm_hip_precond* M,
+                          smm_hip_stream stream, int* solver_status, int* iterations, double* resnorm2);
+
+/* The two dense kernels of GMRES's Gram-Schmidt on device pointers: d_V holds k columns of n elements, column i at d_V + i * ld (ld >= n;
+ * what lies between n and ld is never read), 1 <= k <= SMM_GMRES_MAX_RESTART + 1.  Asynchronous on `stream`.
+ *   multi_dot:  d_out[i] = v_i . d_w for all i < k, d_w read once per 8 columns; accumulation in T, fixed order
+ *   multi_axpy: d_out = d_w + sum_i d_coef[i] v_i, i ascending, each term through _smm_fma; d_out may alias d_w (not d_V)
+ * Every pointer may be element-aligned; 16-byte loads are used when d_V, d_w (and d_out) are 16-byte aligned and ld keeps the columns so.
+ * SMM_HIP_ERR_INVALID: n < 0, k out of range, ld < n, a null array with n > 0 (multi_dot: a null d_out always). */
+int smm_hip_multi_dot_dev_f32(int n, int k, const float* d_V, long long ld, const float* d_w, float* d_out, smm_hip_stream stream);
+int smm_hip_multi_dot_dev_f64(int n, int k, const double* d_V, long long ld, const double* d_w, double* d_out, smm_hip_stream stream);
+int smm_hip_multi_axpy_dev_f32(int n, int k, const float* d_V, long long ld, const float* d_coef, const float* d_w, float* d_out, smm_hip_stream stream);
+int smm_hip_multi_axpy_dev_f64(int n, int k, const double* d_V, long long ld, const double* d_coef, const double* d_w, double* d_out, smm_hip_stream stream);
+
 /* ---- preconditioners: `int apply(const T* rhs, T* x) const noexcept` (ref:1173-1235) --------------------------
  * create: replaces CSRMatrix<T>::getPreconditioner<kind>() (ref:1643-1651) / IC0Preconditioner::init (ref:1798).
  * The matrix must outlive the preconditioner (the reference holds a const CSRMatrix&).  Structural failures

@@ -23,6 +23,7 @@ from .host import (  # noqa: F401
     ConjugateGradientBatch,
     BiCG,
     ConjugateGradientSquared,
+    GMRES,
     CSRMatrix,
     Preconditioner,
     SolverPreconditioner,
@@ -33,6 +34,9 @@ from .host import (  # noqa: F401
     cg_dev,
     bicg_dev,
     cgs_dev,
+    gmres_dev,
+    multi_axpy_dev,
+    multi_dot_dev,
     device_info,
     dot,
     dot_dev,

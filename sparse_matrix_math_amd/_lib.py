@@ -61,6 +61,10 @@ _TYPED = {
     "smm_hip_bicgsymmetric": (c_int, [_P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int)]),
     "smm_hip_cgs": (c_int, [_P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_cgs_dev": (c_int, [_P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_gmres": (c_int, [_P, _P, _P, c_int, "T", c_int, _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_gmres_dev": (c_int, [_P, _P, _P, c_int, "T", c_int, _P, _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_multi_dot_dev": (c_int, [c_int, c_int, _P, c_longlong, _P, _P, _P]),
+    "smm_hip_multi_axpy_dev": (c_int, [c_int, c_int, _P, c_longlong, _P, _P, _P, _P]),
     "smm_hip_bicg": (c_int, [_P, _P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicg_dev": (c_int, [_P, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_precond_apply": (c_int, [_P, _P, _P]),

@@ -734,6 +734,38 @@ def cgs_dev(a, d_b, d_x, maxIterations, eps, stream=None):
     return SolverStatus(st.value), it.value, res.value
 
 
+def GMRES(a, b, x, maxIterations, eps, restart=30, M=None, info=None):
+    """Restarted GMRES(restart) with right preconditioning -- an addition (include/smm_hip.h states the loop).  For general matrices; x
+    is the initial guess and receives the result; maxIterations < 0 means rows, with no other clamp.  M: None or any preconditioner
+    BiCGStab accepts.  `info`, when a dict, receives iterations (Arnoldi steps) and resnorm2 (the last r.r)."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_gmres", suf)(a._h, _host(b, a.dtype, "b", a.rows), _host(x, a.dtype, "x", a.rows, True), int(maxIterations),
+                                    a.dtype.type(eps), int(restart), _mh(M), ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+    if info is not None:
+        info.update(iterations=it.value, resnorm2=res.value)
+    return SolverStatus(st.value)
+
+
+def gmres_dev(a, d_b, d_x, maxIterations, eps, restart=30, M=None, stream=None):
+    """device-pointer GMRES; returns (SolverStatus, iterations, resnorm2).  Synchronises `stream`."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_gmres_dev", suf)(a._h, _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), int(restart), _mh(M), _dptr(stream),
+                                        ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+    return SolverStatus(st.value), it.value, res.value
+
+
+def multi_dot_dev(n, k, d_V, ld, d_w, d_out, dtype, stream=None):
+    """d_out[i] = v_i . w for the k columns of V (column i at d_V + i * ld) on device pointers; asynchronous"""
+    check(_fn("smm_hip_multi_dot_dev", _suffix(dtype))(int(n), int(k), _dptr(d_V), int(ld), _dptr(d_w), _dptr(d_out), _dptr(stream)))
+
+
+def multi_axpy_dev(n, k, d_V, ld, d_coef, d_w, d_out, dtype, stream=None):
+    """d_out = d_w + sum_i d_coef[i] v_i, i ascending through _smm_fma, on device pointers; d_out may alias d_w; asynchronous"""
+    check(_fn("smm_hip_multi_axpy_dev", _suffix(dtype))(int(n), int(k), _dptr(d_V), int(ld), _dptr(d_coef), _dptr(d_w), _dptr(d_out), _dptr(stream)))
+
+
 def BiCG(a, b, x, maxIterations, eps, at=None, info=None):
     """BiCG for general matrices: BiCGSymmetric's text (ref:2021-2102) with the shadow sequence on `at`, the transpose (a.transpose()).
     at=None builds one for the duration of the solve; at=a asserts symmetry and gives BiCGSymmetric's bits.  That `at` is the transpose
