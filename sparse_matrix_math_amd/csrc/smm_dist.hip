@@ -41,6 +41,7 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_solver_host.h"
 #include "smm_p2p.h"
 #include "smm_solver_scal.h"
 
@@ -2164,7 +2165,7 @@ __global__ __launch_bounds__(TPB) void distCgFlushOnly(RowRanges rg, const DistS
 		else KERNEL<T, false><<<(GRID), TPB, 0, (STREAM)>>>(__VA_ARGS__);        \
 	} while (0)
 
-static int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, NPART))); }
+static int gridFor(long long n) { return solverGrid(n); }  // (smm_solver_host.h)
 // Leaving the loop early must be the SAME decision on every rank (a rank that stops issuing iterations while another goes on leaves the
 // other one alone in its next collective).  The `done` flag is formed from all-reduced -- hence identical -- numbers at the same
 // iteration on every rank, so a BLOCKING read of it at fixed iteration numbers is consistent; the asynchronous mailbox of the single-GPU

@@ -51,11 +51,11 @@ struct SetupTrace {
 		}();
 		return v;
 	}
-	explicit SetupTrace(const char* w) : what(w) {
-		if (on()) t0 = std::chrono::steady_clock::now();
+	explicit SetupTrace(const char* w) : what(w) {  // (null: this stage is not traced)
+		if (what && on()) t0 = std::chrono::steady_clock::now();
 	}
 	~SetupTrace() {
-		if (on()) {
+		if (what && on()) {
 			const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 			std::fprintf(stderr, "[smm-hip setup] %-40s %8.3f ms\n", what, ms);
 		}

@@ -1,0 +1,118 @@
+// smm_solver_host.h -- the host frame of the device-resident Krylov drivers (smm_solvers*.hip): the argument check, the grid of an update
+// kernel, the host's look at the loop's `done` word, the read-back that ends a loop, and the host-pointer form of a driver.  What a driver
+// launches per iteration stays written out in its own file.
+#pragma once
+#include <algorithm>
+
+#include "smm_internal.h"
+#include "smm_solver_scal.h"
+
+namespace smm {
+
+// workgroups of an update kernel of 256 lanes over n elements: at most one per partial-sum slot
+inline int solverGrid(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + SCAL_TPB - 1) / SCAL_TPB, NPART))); }
+
+// The argument check of a driver and of its host-pointer wrapper: a matrix of T's dtype, square, and no null vector when it has rows.
+template <typename T, typename... V>
+int solverCheck(const char* who, const smm_hip_csr* a, const V*... vectors) {
+	if (!a || a->dtype != dtypeOf<T>()) {
+		setError("%s: null matrix or dtype mismatch", who);
+		return SMM_HIP_ERR_INVALID;
+	}
+	if (a->rows != a->cols) {
+		setError("%s: matrix must be square", who);
+		return SMM_HIP_ERR_INVALID;
+	}
+	if (a->rows > 0 && !(true && ... && (vectors != nullptr))) {
+		setError("%s: null vector", who);
+		return SMM_HIP_ERR_INVALID;
+	}
+	return SMM_HIP_OK;
+}
+
+// Synchronises `s` when the scope is left while still armed.  Declared after whatever the queued work touches (staging buffers, a
+// transpose built for the solve) and disarmed on the path that has synchronised anyway: no error return releases them under queued work.
+struct SyncOnExit {
+	hipStream_t s;
+	bool armed = true;
+	~SyncOnExit() {
+		if (armed) (void)hipStreamSynchronize(s);
+	}
+};
+
+// The host's look at a loop's device `done` word (DonePoller: no stall of the queue).  One poller per host thread, reused by every solve
+// of that thread.  The word is first asked for at iteration `first`, then `every` iterations later each time; every == 0: after
+// max(4, min(64, i / 4)) iterations -- kernels enqueued past the end of the loop are no-ops, so a late answer costs launches, not results.
+struct LoopWatch {
+	DonePoller* poller = nullptr;
+	const int* flag = nullptr;
+	int next = 0, every = 0;
+	int rc = SMM_HIP_OK;  // what a failed look returned: loopFinish hands it on
+	int begin(hipStream_t s, const int* doneFlag, int first, int fixedInterval = 0) {
+		static thread_local DonePoller threadPoller;
+		poller = &threadPoller;
+		flag = doneFlag;
+		next = first;
+		every = fixedInterval;
+		return poller->init(s);
+	}
+	// true: enqueue no iteration i -- the loop was seen done, or the look failed (rc)
+	bool leave(int i) {
+		if (i != next) return false;
+		const int seen = poller->post(flag);
+		if (seen < 0) rc = seen;
+		next = i + (every ? every : std::max(4, std::min(64, i / 4)));
+		return seen != 0;
+	}
+};
+
+// The end of every loop: the watch's or a launch's error, else `bytes` of the loop's device scalars on the host; synchronises `s`.
+inline int loopFinish(const LoopWatch& watch, void* h, const void* d, size_t bytes, hipStream_t s) {
+	SMM_TRY(watch.rc);
+	SMM_HIP_TRY(hipGetLastError());
+	SMM_HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s));
+	SMM_HIP_TRY(hipStreamSynchronize(s));
+	return SMM_HIP_OK;
+}
+
+// labels of a traced wrapper's SetupTrace lines (null: not traced)
+struct HostTrace {
+	const char *all = nullptr, *alloc = nullptr, *in = nullptr, *loop = nullptr, *out = nullptr;
+};
+
+// The host-pointer form of a driver, the reference's calling convention: b, x0 (null: the solver has none) and x, `count` elements each in
+// caller-owned host memory, are staged onto the device, run(d_b, d_x0, d_x, stream) is the driver on the copies, and x comes back -- when
+// `wrote` is given only if *wrote != 0 afterwards.  A failure on the way synchronises the stream before the copies are released.
+template <typename T, typename Run>
+int solveFromHost(size_t count, const T* b, const T* x0, T* x, Run&& run, const int* wrote = nullptr, const HostTrace& tr = {}) {
+	SMM_TRY(ensureInit());
+	hipStream_t s = libStream();
+	SetupTrace traceAll(tr.all);
+	DevBuf<T> db, dx0, dx;
+	SyncOnExit drain{s};
+	{
+		SetupTrace trace(tr.alloc);
+		SMM_TRY(db.alloc(count));
+		if (x0) SMM_TRY(dx0.alloc(count));
+		SMM_TRY(dx.alloc(count));
+	}
+	if (count) {
+		SetupTrace trace(tr.in);
+		SMM_TRY(hostToDev(db, b, sizeof(T) * count, s));
+		if (x0) SMM_TRY(hostToDev(dx0, x0, sizeof(T) * count, s));
+		SMM_TRY(hostToDev(dx, x, sizeof(T) * count, s));
+		if (tr.in && SetupTrace::on()) SMM_HIP_TRY(hipStreamSynchronize(s));
+	}
+	{
+		SetupTrace trace(tr.loop);
+		SMM_TRY(run(static_cast<const T*>(db), static_cast<const T*>(dx0), static_cast<T*>(dx), s));
+	}
+	if (count && (!wrote || *wrote)) {
+		SetupTrace trace(tr.out);
+		SMM_TRY(devToHost(x, dx, sizeof(T) * count, s));
+	}
+	drain.armed = false;  // (the driver's read-back and devToHost have synchronised)
+	return SMM_HIP_OK;
+}
+
+}  // namespace smm

@@ -45,6 +45,21 @@ __device__ __forceinline__ T sumPartsAll(const T* __restrict__ partials, T* red5
 	return v;
 }
 
+// the start of BiCGStab (ref:2231) and of ConjugateGradientSquared (ref:2128): rr0 = r.r0 ; iterations = 0 (one workgroup)
+template <typename T>
+__global__ __launch_bounds__(SCAL_TPB) void rr0InitScal(const T* __restrict__ partials, Scal<T>* sc) {
+	__shared__ T red[4];
+	const T rr0 = sumParts(partials, red);
+	if (threadIdx.x == 0) {
+		sc->rr = rr0;
+		sc->rrPing[0] = rr0;
+		sc->res = T(0);
+		sc->iters = 0;
+		sc->done = 0;
+		sc->status = SMM_SOLVER_SUCCESS;
+	}
+}
+
 // launches an update kernel templated on <T, NT> with the cache policy updateNT chose (T and TPB are those of the unit that expands it)
 #define SMM_LAUNCH_UPDATE(KERNEL, NTFLAG, GRID, STREAM, ...)                    \
 	do {                                                                       \

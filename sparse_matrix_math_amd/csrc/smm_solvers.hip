@@ -18,6 +18,7 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_solver_host.h"
 #include "smm_solver_scal.h"
 
 namespace smm {
@@ -381,21 +382,6 @@ __global__ __launch_bounds__(TPB) void dot2Partials(int n, const T* __restrict__
 	}
 }
 
-// ---- BiCGStab stages -----------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(TPB) void bicgInitScal(const T* __restrict__ partials, Scal<T>* sc) {
-	__shared__ T red[4];
-	const T rr0 = sumParts(partials, red);  // ref:2231
-	if (threadIdx.x == 0) {
-		sc->rr = rr0;
-		sc->rrPing[0] = rr0;
-		sc->res = T(0);
-		sc->iters = 0;
-		sc->done = 0;
-		sc->status = SMM_SOLVER_SUCCESS;
-	}
-}
-
 // ---- BiCGSymmetric stages (ref:2021-2102) ----------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(TPB) void bsymInitScal(const T* __restrict__ partials, Scal<T>* sc) {
@@ -480,8 +466,6 @@ __global__ __launch_bounds__(TPB) void bsymUpdateP(int n, const Scal<T>* __restr
 // ---------------------------------------------------------------------------------------------------------
 // host drivers
 // ---------------------------------------------------------------------------------------------------------
-static int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, NPART))); }
-
 // Non-temporal loads / stores for an update kernel whose vectors cannot stay in the 256 MB Infinity Cache until the next kernel
 // reads them anyway; cache-resident problems keep the default policy.  SMM_HIP_UPDATE_NT=0/1 overrides (measurements).
 bool updateNT(long long n, size_t elemBytes, int vectors) {
@@ -492,8 +476,6 @@ bool updateNT(long long n, size_t elemBytes, int vectors) {
 	if (forced >= 0) return forced != 0;
 	return static_cast<double>(n) * static_cast<double>(elemBytes) * vectors > 192.0 * 1024 * 1024;
 }
-
-static int checkInterval(int it) { return std::max(4, std::min(64, it / 4)); }
 
 // from how many bytes per vector CG defers its x update (cgLazyXP): where five vectors no longer fit the 256 MB Infinity Cache the passes
 // are what an iteration costs; below, the extra ring of directions buys nothing.  smm_hip_set_cg_lazy_x_min_bytes (tests) / SMM_HIP_CG_LAZY_X=0
@@ -509,23 +491,9 @@ long long cgLazyMinBytes() {
 }
 
 template <typename T>
-static int readScal(const Scal<T>* d_sc, Scal<T>* h, hipStream_t s) {
-	SMM_HIP_TRY(hipMemcpyAsync(h, d_sc, sizeof(Scal<T>), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
-	return SMM_HIP_OK;
-}
-
-template <typename T>
 int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations, T eps, const smm_hip_precond* M, hipStream_t s, int* status,
           int* iterations, T* resnorm2) {
-	if (!a || a->dtype != dtypeOf<T>()) {
-		setError("cg: null matrix or dtype mismatch");
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (a->rows != a->cols) {
-		setError("cg: matrix must be square");
-		return SMM_HIP_ERR_INVALID;
-	}
+	SMM_TRY(solverCheck<T>("cg", a, b, x0, x));
 	const int pcg = M != nullptr;
 	if (pcg && (M->kind != SMM_PRECOND_IC0 || M->a != a)) {
 		// the reference only has the IC0 overload (ref:2414-2422)
@@ -533,10 +501,6 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int n = a->rows;
-	if (n > 0 && (!b || !x0 || !x)) {
-		setError("cg: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
 	if (!pcg) {
 		// a matrix that fits the chip's register file is solved in one launch (smm_resident.hip)
 		bool handled = false;
@@ -571,7 +535,7 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
 	SMM_TRY(parts.alloc(2 * NPART));
 	SMM_TRY(parts2.alloc(NPART));
 	SMM_TRY(sc.alloc(1));
-	const int g = gridFor(n);
+	const int g = solverGrid(n);
 
 	SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x0, r, 0, nullptr, nullptr, nullptr, s));  // r = b - A x0, ref:2337
 	if (pcg) {
@@ -586,18 +550,10 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
 	cgInitScal<T><<<1, TPB, 0, s>>>(parts, sc, eps, pcg, parts2);
 	if (maxIterations == -1) maxIterations = n;  // ref:2345-2347 (no clamp otherwise)
 
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
-	int seenDone = 0;
-	int nextCheck = 0;
 	const int* doneFlag = &sc.p->done;
-	for (int i = 0; i < maxIterations && !seenDone; ++i) {
-		if (i == nextCheck) {
-			seenDone = poller.post(doneFlag);
-			if (seenDone < 0) return seenDone;
-			if (seenDone) break;
-			nextCheck = i + checkInterval(i);
-		}
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 0));
+	for (int i = 0; i < maxIterations && !watch.leave(i); ++i) {
 		if (lazy && fuseP) {
 			// the direction is formed INSIDE the SpMV (2.5-D constant-diagonal kernel): SpMV' (bookkeeping of iteration i - 1, p_i, A p_i, p.Ap),
 			// the flush of x behind it (scheduled every LAZY_M-th iteration; or because SpMV' found iteration i - 1 converged), the r update
@@ -651,9 +607,8 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
 			SMM_LAUNCH_UPDATE(cgFusedXP, updateNT(n, sizeof(T), 5), g, s, n, sc, i & 1, parts2, eps, p, r, xcur, x);
 		}
 	}
-	SMM_HIP_TRY(hipGetLastError());
 	Scal<T> h;
-	SMM_TRY(readScal<T>(sc, &h, s));
+	SMM_TRY(loopFinish(watch, &h, sc.p, sizeof(h), s));
 	if (status) *status = h.status;
 	if (iterations) *iterations = h.iters;
 	if (resnorm2) *resnorm2 = h.res;
@@ -732,13 +687,12 @@ static int bicgstabLoop(const smm_hip_csr* a, const T* b, T* x, int maxIteration
 	}
 	SMM_TRY(launchCopy2<T>(n, r, r0, p, s));                     // ref:2225-2226
 	SMM_TRY(launchDotPartials<T>(n, r, r0, parts, nullptr, s));  // ref:2231
-	bicgInitScal<T><<<1, TPB, 0, s>>>(parts, sc);
+	rr0InitScal<T><<<1, TPB, 0, s>>>(parts, sc);  // (smm_solver_scal.h)
 
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);  // do { } while: the body always runs once (ref:2232, 2277)
-	int nextCheck = 1;
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 1));
 	for (int i = 0; i < planned; ++i) {
 		if (Applier::hostSide && i > 0) {
 			// a host functor drains the stream at every apply anyway: test the flag directly so that it is never called for an
@@ -747,11 +701,8 @@ static int bicgstabLoop(const smm_hip_csr* a, const T* b, T* x, int maxIteration
 			SMM_HIP_TRY(hipMemcpyAsync(&done, doneFlag, sizeof(int), hipMemcpyDeviceToHost, s));
 			SMM_HIP_TRY(hipStreamSynchronize(s));
 			if (done) break;
-		} else if (i == nextCheck) {
-			const int seen = poller.post(doneFlag);
-			if (seen < 0) return seen;
-			if (seen) break;
-			nextCheck = i + checkInterval(i);
+		} else if (watch.leave(i)) {
+			break;
 		}
 		if (jacobiDiag) {
 			SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, jacobiDiag, p, ap, 1, r0, parts, doneFlag, s, SPMV_DIV_LHS));  // ref:2234-2235 + 2243 fused
@@ -770,7 +721,7 @@ static int bicgstabLoop(const smm_hip_csr* a, const T* b, T* x, int maxIteration
 			SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, r0, parts, doneFlag, s));  // ref:2240 + 2243 fused
 		}
 		// alpha, omega and beta are formed inside the three update kernels that consume them (no scalar launches)
-		SMM_LAUNCH_UPDATE(bicgFusedS, updateNT(n, sizeof(T), 3), gridFor(n), s, n, sc, i & 1, parts, ap, r, sv);
+		SMM_LAUNCH_UPDATE(bicgFusedS, updateNT(n, sizeof(T), 3), solverGrid(n), s, n, sc, i & 1, parts, ap, r, sv);
 		if (jacobiDiag) {
 			SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, jacobiDiag, sv, as, 2, sv, parts, doneFlag, s, SPMV_DIV_LHS));  // ref:2250-2251 + 2256-2261 fused
 		} else if (blockM) {
@@ -789,11 +740,10 @@ static int bicgstabLoop(const smm_hip_csr* a, const T* b, T* x, int maxIteration
 			SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, sv, as, 2, sv, parts, doneFlag, s));
 		}
 		SMM_LAUNCH_UPDATE(bicgFusedXR, updateNT(n, sizeof(T), 7), g, s, n, sc, parts, p, sv, as, r0, x, r, parts2);
-		SMM_LAUNCH_UPDATE(bicgFusedP, updateNT(n, sizeof(T), 4), gridFor(n), s, n, sc, i & 1, parts2, eps, ap, r, p);
+		SMM_LAUNCH_UPDATE(bicgFusedP, updateNT(n, sizeof(T), 4), solverGrid(n), s, n, sc, i & 1, parts2, eps, ap, r, p);
 	}
-	SMM_HIP_TRY(hipGetLastError());
 	Scal<T> h;
-	SMM_TRY(readScal<T>(sc, &h, s));
+	SMM_TRY(loopFinish(watch, &h, sc.p, sizeof(h), s));
 	if (status) *status = h.iters > maxIterations ? SMM_SOLVER_MAX_ITERATIONS_REACHED : SMM_SOLVER_SUCCESS;  // ref:2279-2282
 	if (iterations) *iterations = h.iters;
 	if (resnorm) *resnorm = h.res;
@@ -801,26 +751,9 @@ static int bicgstabLoop(const smm_hip_csr* a, const T* b, T* x, int maxIteration
 }
 
 template <typename T>
-static int bicgstabCheck(const smm_hip_csr* a, const T* b, T* x) {
-	if (!a || a->dtype != dtypeOf<T>()) {
-		setError("bicgstab: null matrix or dtype mismatch");
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (a->rows != a->cols) {
-		setError("bicgstab: matrix must be square");
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (a->rows > 0 && (!b || !x)) {
-		setError("bicgstab: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	return SMM_HIP_OK;
-}
-
-template <typename T>
 int bicgstabDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T eps, const smm_hip_precond* M, hipStream_t s, int* status,
                 int* iterations, T* resnorm) {
-	SMM_TRY(bicgstabCheck<T>(a, b, x));
+	SMM_TRY(solverCheck<T>("bicgstab", a, b, x));
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;  // ref:2209
 	if (precondition && (M->a != a || M->kind == SMM_PRECOND_IC0)) {
 		setError("bicgstab: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS created for this matrix");
@@ -849,45 +782,25 @@ static int bicgstabFunctorHost(const smm_hip_csr* a, T* b, T* x, int maxIteratio
 		setError("bicgstab_functor: null apply function");
 		return SMM_HIP_ERR_INVALID;
 	}
-	SMM_TRY(ensureInit());
-	SMM_TRY(bicgstabCheck<T>(a, b, x));
+	SMM_TRY(solverCheck<T>("bicgstab", a, b, x));
 	const int n = a->rows;
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx;
-	SMM_TRY(db.alloc(n));
-	SMM_TRY(dx.alloc(n));
-	T* pinned = nullptr;
-	SMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pinned), sizeof(T) * 2 * static_cast<size_t>(std::max(1, n)), hipHostMallocDefault));
-	struct Unpin {
-		T* p;
-		~Unpin() { hipHostFree(p); }
-	} unpin{pinned};
-	if (n) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * n, s));
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * n, s));
-	}
-	const HostApplier<T> apply{fn, user, n, pinned, pinned + std::max(1, n)};
-	const int rc = bicgstabLoop<T, HostApplier<T>>(a, db, dx, maxIterations, eps, true, apply, s, status, iterations, resnorm);
-	if (rc != SMM_HIP_OK) {
-		hipStreamSynchronize(s);  // kernels of the abandoned loop may still be queued on buffers that are about to be released
+	return solveFromHost<T>(n, b, nullptr, x, [&](const T* db, const T*, T* dx, hipStream_t s) {
+		T* pinned = nullptr;
+		SMM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pinned), sizeof(T) * 2 * static_cast<size_t>(std::max(1, n)), hipHostMallocDefault));
+		struct Unpin {
+			T* p;
+			~Unpin() { hipHostFree(p); }
+		} unpin{pinned};
+		const HostApplier<T> apply{fn, user, n, pinned, pinned + std::max(1, n)};
+		const int rc = bicgstabLoop<T, HostApplier<T>>(a, db, dx, maxIterations, eps, true, apply, s, status, iterations, resnorm);
+		if (rc != SMM_HIP_OK) (void)hipStreamSynchronize(s);  // an apply's copy out of `pinned` may still be queued
 		return rc;
-	}
-	if (n) {
-		SMM_TRY(devToHost(x, dx, sizeof(T) * n, s));
-	}
-	return SMM_HIP_OK;
+	});
 }
 
 template <typename T>
 int bicgsymmetricDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T eps, hipStream_t s, int* status, int* iterations) {
-	if (!a || a->dtype != dtypeOf<T>()) {
-		setError("bicgsymmetric: null matrix or dtype mismatch");
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (a->rows != a->cols) {
-		setError("bicgsymmetric: matrix must be square");
-		return SMM_HIP_ERR_INVALID;
-	}
+	SMM_TRY(solverCheck<T>("bicgsymmetric", a, b, x));
 	const int n = a->rows;
 	maxIterations = std::min(maxIterations, n);  // ref:2030-2033
 	if (maxIterations == -1) maxIterations = n;
@@ -904,27 +817,19 @@ int bicgsymmetricDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, 
 	SMM_TRY(launchCopy2<T>(n, r, p, nullptr, s));
 	SMM_TRY(launchDotPartials<T>(n, r, r, parts, nullptr, s));
 	bsymInitScal<T><<<1, TPB, 0, s>>>(parts, sc);
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);
-	int nextCheck = 1;
-	for (int i = 0; i < planned; ++i) {
-		if (i == nextCheck) {
-			const int seen = poller.post(doneFlag);
-			if (seen < 0) return seen;
-			if (seen) break;
-			nextCheck = i + checkInterval(i);
-		}
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 1));
+	for (int i = 0; i < planned && !watch.leave(i); ++i) {
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, p, parts, doneFlag, s));  // ref:2048-2049
 		bsymAlphaScal<T><<<1, TPB, 0, s>>>(parts, sc, eps);
 		bsymUpdateXR<T><<<NPART, TPB, 0, s>>>(n, sc, p, ap, x, r, parts);
 		bsymBetaScal<T><<<1, TPB, 0, s>>>(parts, sc, eps);
-		bsymUpdateP<T><<<gridFor(n), TPB, 0, s>>>(n, sc, r, p);
+		bsymUpdateP<T><<<solverGrid(n), TPB, 0, s>>>(n, sc, r, p);
 	}
-	SMM_HIP_TRY(hipGetLastError());
 	Scal<T> h;
-	SMM_TRY(readScal<T>(sc, &h, s));
+	SMM_TRY(loopFinish(watch, &h, sc.p, sizeof(h), s));
 	int st = h.status;
 	if (st == SMM_SOLVER_SUCCESS && h.iters > maxIterations) st = SMM_SOLVER_MAX_ITERATIONS_REACHED;  // ref:2098-2100
 	if (status) *status = st;
@@ -936,99 +841,33 @@ int bicgsymmetricDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, 
 template <typename T>
 static int cgHost(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations, T eps, const smm_hip_precond* M, int* status,
                   int* iterations, T* resnorm2) {
-	if (!a) {
-		setError("cg: null matrix");
-		return SMM_HIP_ERR_INVALID;
-	}
-	SMM_TRY(ensureInit());
-	const int n = a->rows;
-	if (n > 0 && (!b || !x0 || !x)) {
-		setError("cg: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx0, dx;
-	SMM_TRY(db.alloc(n));
-	SMM_TRY(dx0.alloc(n));
-	SMM_TRY(dx.alloc(n));
-	if (n) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * n, s));
-		SMM_TRY(hostToDev(dx0, x0, sizeof(T) * n, s));
-		// x is only written once the loop runs (ref:2342-2344): start the device copy from the caller's x
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * n, s));
-	}
+	SMM_TRY(solverCheck<T>("cg", a, b, x0, x));
+	// x is only written once the loop runs (ref:2342-2344): the device copy starts from the caller's x and comes back only then
 	int it = 0;
-	SMM_TRY(cgDev<T>(a, db, dx0, dx, maxIterations, eps, M, s, status, &it, resnorm2));
+	SMM_TRY(solveFromHost<T>(a->rows, b, x0, x, [&](const T* db, const T* dx0, T* dx, hipStream_t s) {
+		return cgDev<T>(a, db, dx0, dx, maxIterations, eps, M, s, status, &it, resnorm2);
+	}, &it));
 	if (iterations) *iterations = it;
-	if (n && it > 0) {
-		SMM_TRY(devToHost(x, dx, sizeof(T) * n, s));
-	}
 	return SMM_HIP_OK;
 }
 
 template <typename T>
 static int bicgstabHost(const smm_hip_csr* a, T* b, T* x, int maxIterations, T eps, const smm_hip_precond* M, int* status, int* iterations,
                         T* resnorm) {
-	if (!a) {
-		setError("bicgstab: null matrix");
-		return SMM_HIP_ERR_INVALID;
-	}
-	SMM_TRY(ensureInit());
-	const int n = a->rows;
-	if (n > 0 && (!b || !x)) {
-		setError("bicgstab: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	hipStream_t s = libStream();
-	SetupTrace traceAll("bicgstab (host pointers): whole call");
-	DevBuf<T> db, dx;
-	{
-		SetupTrace trace("bicgstab (host pointers):   allocate b, x");
-		SMM_TRY(db.alloc(n));
-		SMM_TRY(dx.alloc(n));
-	}
-	if (n) {
-		SetupTrace trace("bicgstab (host pointers):   copy b, x in");
-		SMM_TRY(hostToDev(db, b, sizeof(T) * n, s));
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * n, s));
-		if (SetupTrace::on()) SMM_HIP_TRY(hipStreamSynchronize(s));
-	}
-	{
-		SetupTrace trace("bicgstab (host pointers):   device loop");
-		SMM_TRY(bicgstabDev<T>(a, db, dx, maxIterations, eps, M, s, status, iterations, resnorm));
-	}
-	if (n) {
-		SetupTrace trace("bicgstab (host pointers):   copy x out");
-		SMM_TRY(devToHost(x, dx, sizeof(T) * n, s));
-	}
-	return SMM_HIP_OK;
+	SMM_TRY(solverCheck<T>("bicgstab", a, b, x));
+	const HostTrace trace{"bicgstab (host pointers): whole call", "bicgstab (host pointers):   allocate b, x", "bicgstab (host pointers):   copy b, x in",
+	                      "bicgstab (host pointers):   device loop", "bicgstab (host pointers):   copy x out"};
+	return solveFromHost<T>(a->rows, b, nullptr, x, [&](const T* db, const T*, T* dx, hipStream_t s) {
+		return bicgstabDev<T>(a, db, dx, maxIterations, eps, M, s, status, iterations, resnorm);
+	}, nullptr, trace);
 }
 
 template <typename T>
 static int bicgsymmetricHost(const smm_hip_csr* a, T* b, T* x, int maxIterations, T eps, int* status, int* iterations) {
-	if (!a) {
-		setError("bicgsymmetric: null matrix");
-		return SMM_HIP_ERR_INVALID;
-	}
-	SMM_TRY(ensureInit());
-	const int n = a->rows;
-	if (n > 0 && (!b || !x)) {
-		setError("bicgsymmetric: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx;
-	SMM_TRY(db.alloc(n));
-	SMM_TRY(dx.alloc(n));
-	if (n) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * n, s));
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * n, s));
-	}
-	SMM_TRY(bicgsymmetricDev<T>(a, db, dx, maxIterations, eps, s, status, iterations));
-	if (n) {
-		SMM_TRY(devToHost(x, dx, sizeof(T) * n, s));
-	}
-	return SMM_HIP_OK;
+	SMM_TRY(solverCheck<T>("bicgsymmetric", a, b, x));
+	return solveFromHost<T>(a->rows, b, nullptr, x, [&](const T* db, const T*, T* dx, hipStream_t s) {
+		return bicgsymmetricDev<T>(a, db, dx, maxIterations, eps, s, status, iterations);
+	});
 }
 
 // every translation unit of the library is a code object of its own, built for the device at the FIRST launch of any of its kernels

@@ -19,6 +19,7 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_solver_host.h"
 #include "smm_solver_scal.h"
 
 namespace smm {
@@ -314,9 +315,6 @@ __global__ __launch_bounds__(TPB) void cgBatchXP(int n, Scal<T>* sc, int* allDon
 	});
 }
 
-int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, NPART))); }
-int checkInterval(int it) { return std::max(4, std::min(64, it / 4)); }
-
 // KERNEL<T, k> for the run-time k (one instantiation per number of columns: the row of a block is a compile-time struct)
 #define SMM_BATCH_LAUNCH(KERNEL, K, GRID, STREAM, ...)                         \
 	do {                                                                       \
@@ -332,40 +330,22 @@ int checkInterval(int it) { return std::max(4, std::min(64, it / 4)); }
 		}                                                                      \
 	} while (0)
 
-template <typename T>
-int batchCheck(const char* who, const smm_hip_csr* a, int k) {
-	if (!a || a->dtype != dtypeOf<T>()) {
-		setError("%s: null matrix or dtype mismatch", who);
-		return SMM_HIP_ERR_INVALID;
-	}
+// solverCheck on the n x k blocks, and k in range
+template <typename T, typename... V>
+int batchCheck(const char* who, const smm_hip_csr* a, int k, const V*... blocks) {
+	SMM_TRY(solverCheck<T>(who, a, blocks...));
 	if (k < 1 || k > SMM_HIP_MAX_RHS) {
 		setError("%s: k = %d, must be 1 .. %d", who, k, SMM_HIP_MAX_RHS);
 		return SMM_HIP_ERR_INVALID;
 	}
-	if (a->rows != a->cols) {
-		setError("%s: matrix must be square", who);
-		return SMM_HIP_ERR_INVALID;
-	}
-	return SMM_HIP_OK;
-}
-
-// the k Scal<T> of a finished solve -> the caller's three host arrays
-template <typename T>
-int readColumns(const Scal<T>* d_sc, int k, Scal<T>* h, hipStream_t s) {
-	SMM_HIP_TRY(hipMemcpyAsync(h, d_sc, sizeof(Scal<T>) * k, hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
 	return SMM_HIP_OK;
 }
 
 template <typename T>
 int bicgstabBatchDev(const smm_hip_csr* a, int k, const T* b, T* x, int maxIterations, T eps, const smm_hip_precond* M, hipStream_t s, int* status,
                      int* iterations, T* resnorm) {
-	SMM_TRY(batchCheck<T>("bicgstab_batch", a, k));
+	SMM_TRY(batchCheck<T>("bicgstab_batch", a, k, b, x));
 	const int n = a->rows;
-	if (n > 0 && (!b || !x)) {
-		setError("bicgstab_batch: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;  // ref:2209
 	if (precondition && M->kind != SMM_PRECOND_JACOBI) {
 		setError("bicgstab_batch: only no preconditioner or JACOBI is supported for several right-hand sides (SGS / ILU0 / IC0 / BLOCK_ kinds are not)");
@@ -404,28 +384,20 @@ int bicgstabBatchDev(const smm_hip_csr* a, int k, const T* b, T* x, int maxItera
 	SMM_BATCH_LAUNCH(batchDot, k, NPART, s, n, r, r0, parts);  // ref:2231
 	SMM_BATCH_LAUNCH(bicgBatchInit, k, 1, s, parts, sc, allDone);
 
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
 	const int* doneFlag = allDone;
 	const int planned = std::max(1, maxIterations);  // do { } while: the body always runs once (ref:2232, 2277)
 	const int spmmOp = diag ? SPMV_OP_DIV : SMM_OP_ASSIGN;
-	int nextCheck = 1;
-	for (int i = 0; i < planned; ++i) {
-		if (i == nextCheck) {
-			const int seen = poller.post(doneFlag);
-			if (seen < 0) return seen;
-			if (seen) break;
-			nextCheck = i + checkInterval(i);
-		}
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 1));
+	for (int i = 0; i < planned && !watch.leave(i); ++i) {
 		SMM_TRY(launchSpmm<T>(a, spmmOp, k, nullptr, p, ap, 1, r0, parts, doneFlag, s, diag));  // ref:2234-2235 + 2243 fused
-		SMM_BATCH_LAUNCH(bicgBatchS, k, gridFor(n), s, n, sc, i & 1, parts, ap, r, sv);
+		SMM_BATCH_LAUNCH(bicgBatchS, k, solverGrid(n), s, n, sc, i & 1, parts, ap, r, sv);
 		SMM_TRY(launchSpmm<T>(a, spmmOp, k, nullptr, sv, as, 2, sv, parts, doneFlag, s, diag));  // ref:2250-2251 + 2256-2261 fused
 		SMM_BATCH_LAUNCH(bicgBatchXR, k, NPART, s, n, sc, parts, p, sv, as, r0, x, r, parts2);
-		SMM_BATCH_LAUNCH(bicgBatchP, k, gridFor(n), s, n, sc, allDone, i & 1, parts2, eps, ap, r, p);
+		SMM_BATCH_LAUNCH(bicgBatchP, k, solverGrid(n), s, n, sc, allDone, i & 1, parts2, eps, ap, r, p);
 	}
-	SMM_HIP_TRY(hipGetLastError());
 	Scal<T> h[SMM_HIP_MAX_RHS];
-	SMM_TRY(readColumns<T>(sc, k, h, s));
+	SMM_TRY(loopFinish(watch, h, sc.p, sizeof(Scal<T>) * k, s));
 	for (int j = 0; j < k; ++j) {
 		if (status) status[j] = h[j].iters > maxIterations ? SMM_SOLVER_MAX_ITERATIONS_REACHED : SMM_SOLVER_SUCCESS;  // ref:2279-2282
 		if (iterations) iterations[j] = h[j].iters;
@@ -437,12 +409,8 @@ int bicgstabBatchDev(const smm_hip_csr* a, int k, const T* b, T* x, int maxItera
 template <typename T>
 int cgBatchDev(const smm_hip_csr* a, int k, const T* b, const T* x0, T* x, int maxIterations, T eps, hipStream_t s, int* status, int* iterations,
                T* resnorm2) {
-	SMM_TRY(batchCheck<T>("cg_batch", a, k));
+	SMM_TRY(batchCheck<T>("cg_batch", a, k, b, x0, x));
 	const int n = a->rows;
-	if (n > 0 && (!b || !x0 || !x)) {
-		setError("cg_batch: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
 	SMM_TRY(ensureCsrReady(a, s, true));
 	const size_t nk = static_cast<size_t>(n) * k;
 	DevBuf<T> r, p, Ap, parts, parts2;
@@ -462,25 +430,17 @@ int cgBatchDev(const smm_hip_csr* a, int k, const T* b, const T* x0, T* x, int m
 	SMM_BATCH_LAUNCH(cgBatchInit, k, 1, s, parts, sc, allDone, eps);
 	if (maxIterations == -1) maxIterations = n;  // ref:2345-2347 (no clamp otherwise)
 
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
 	const int* doneFlag = allDone;
-	int nextCheck = 0;
-	for (int i = 0; i < maxIterations; ++i) {
-		if (i == nextCheck) {
-			const int seen = poller.post(doneFlag);
-			if (seen < 0) return seen;
-			if (seen) break;
-			nextCheck = i + checkInterval(i);
-		}
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 0));
+	for (int i = 0; i < maxIterations && !watch.leave(i); ++i) {
 		SMM_TRY(launchSpmm<T>(a, SMM_OP_ASSIGN, k, nullptr, p, Ap, 1, p, parts, doneFlag, s));  // Ap = A p with p.Ap fused (ref:2353-2354)
 		const T* xcur = i == 0 ? x0 : x;  // ref:2351, 2395
 		SMM_BATCH_LAUNCH(cgBatchR, k, NPART, s, n, sc, i & 1, parts, Ap, r, parts2);
-		SMM_BATCH_LAUNCH(cgBatchXP, k, gridFor(n), s, n, sc, allDone, i & 1, parts2, eps, p, r, xcur, x);
+		SMM_BATCH_LAUNCH(cgBatchXP, k, solverGrid(n), s, n, sc, allDone, i & 1, parts2, eps, p, r, xcur, x);
 	}
-	SMM_HIP_TRY(hipGetLastError());
 	Scal<T> h[SMM_HIP_MAX_RHS];
-	SMM_TRY(readColumns<T>(sc, k, h, s));
+	SMM_TRY(loopFinish(watch, h, sc.p, sizeof(Scal<T>) * k, s));
 	for (int j = 0; j < k; ++j) {
 		if (status) status[j] = h[j].status;
 		if (iterations) iterations[j] = h[j].iters;
@@ -492,58 +452,20 @@ int cgBatchDev(const smm_hip_csr* a, int k, const T* b, const T* x0, T* x, int m
 // ---- host-pointer wrappers: blocks in caller-owned host memory, as the single forms take their vectors ---------------------------
 template <typename T>
 int bicgstabBatchHost(const smm_hip_csr* a, int k, T* b, T* x, int maxIterations, T eps, const smm_hip_precond* M, int* status, int* iterations, T* resnorm) {
-	SMM_TRY(batchCheck<T>("bicgstab_batch", a, k));
-	SMM_TRY(ensureInit());
-	const size_t nk = static_cast<size_t>(a->rows) * k;
-	if (nk > 0 && (!b || !x)) {
-		setError("bicgstab_batch: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx;
-	SMM_TRY(db.alloc(nk));
-	SMM_TRY(dx.alloc(nk));
-	if (nk) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * nk, s));
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * nk, s));
-	}
-	const int rc = bicgstabBatchDev<T>(a, k, db, dx, maxIterations, eps, M, s, status, iterations, resnorm);
-	if (rc != SMM_HIP_OK) {
-		hipStreamSynchronize(s);  // kernels of an abandoned loop may still be queued on buffers that are about to be released
-		return rc;
-	}
-	if (nk) SMM_TRY(devToHost(x, dx, sizeof(T) * nk, s));
-	return SMM_HIP_OK;
+	SMM_TRY(batchCheck<T>("bicgstab_batch", a, k, b, x));
+	return solveFromHost<T>(static_cast<size_t>(a->rows) * k, b, nullptr, x, [&](const T* db, const T*, T* dx, hipStream_t s) {
+		return bicgstabBatchDev<T>(a, k, db, dx, maxIterations, eps, M, s, status, iterations, resnorm);
+	});
 }
 
+// a column whose first residual already passes is never written (ref:2342-2344): the device block starts as the caller's x and comes back
+// whole, so such a column returns bit for bit
 template <typename T>
 int cgBatchHost(const smm_hip_csr* a, int k, const T* b, const T* x0, T* x, int maxIterations, T eps, int* status, int* iterations, T* resnorm2) {
-	SMM_TRY(batchCheck<T>("cg_batch", a, k));
-	SMM_TRY(ensureInit());
-	const size_t nk = static_cast<size_t>(a->rows) * k;
-	if (nk > 0 && (!b || !x0 || !x)) {
-		setError("cg_batch: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx0, dx;
-	SMM_TRY(db.alloc(nk));
-	SMM_TRY(dx0.alloc(nk));
-	SMM_TRY(dx.alloc(nk));
-	if (nk) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * nk, s));
-		SMM_TRY(hostToDev(dx0, x0, sizeof(T) * nk, s));
-		// a column whose first residual already passes is never written (ref:2342-2344): the device block starts as the caller's x and
-		// comes back whole, so such a column returns bit for bit
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * nk, s));
-	}
-	const int rc = cgBatchDev<T>(a, k, db, dx0, dx, maxIterations, eps, s, status, iterations, resnorm2);
-	if (rc != SMM_HIP_OK) {
-		hipStreamSynchronize(s);
-		return rc;
-	}
-	if (nk) SMM_TRY(devToHost(x, dx, sizeof(T) * nk, s));
-	return SMM_HIP_OK;
+	SMM_TRY(batchCheck<T>("cg_batch", a, k, b, x0, x));
+	return solveFromHost<T>(static_cast<size_t>(a->rows) * k, b, x0, x, [&](const T* db, const T* dx0, T* dx, hipStream_t s) {
+		return cgBatchDev<T>(a, k, db, dx0, dx, maxIterations, eps, s, status, iterations, resnorm2);
+	});
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_solver_host.h"
 #include "smm_solver_scal.h"
 
 namespace smm {
@@ -121,9 +122,6 @@ __global__ __launch_bounds__(TPB) void bicgUpdateP(int n, const Scal<T>* __restr
 	});
 }
 
-static int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, NPART))); }
-static int checkInterval(int it) { return std::max(4, std::min(64, it / 4)); }
-
 struct CsrOwner {  // the transpose a solve built for itself
 	smm_hip_csr* m = nullptr;
 	~CsrOwner() { smm_hip_csr_destroy(m); }
@@ -132,21 +130,18 @@ struct CsrOwner {  // the transpose a solve built for itself
 template <typename T>
 static int bicgDev(const smm_hip_csr* a, const smm_hip_csr* at, const T* b, T* x, int maxIterations, T eps, hipStream_t s, int* status, int* iterations,
                    T* resnorm2) {
-	if (!a || a->dtype != dtypeOf<T>() || (at && at->dtype != dtypeOf<T>())) {
+	SMM_TRY(solverCheck<T>("bicg", a, b, x));
+	if (at && at->dtype != dtypeOf<T>()) {
 		setError("bicg: null matrix or dtype mismatch");
 		return SMM_HIP_ERR_INVALID;
 	}
-	if (a->rows != a->cols) {
-		setError("bicg: matrix must be square");
-		return SMM_HIP_ERR_INVALID;
-	}
 	const int n = a->rows;
-	if (n > 0 && (!b || !x)) {
-		setError("bicg: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	SMM_TRY(ensureCsrReady(a, s, true));
+	// (in this order: an error return synchronises, then releases the vectors, then destroys the transpose -- never under queued kernels)
 	CsrOwner built;
+	DevBuf<T> r, rt, p, pt, ap, atp, partsD, partsU;
+	DevBuf<Scal<T>> sc;
+	SyncOnExit drain{s};
+	SMM_TRY(ensureCsrReady(a, s, true));
 	if (!at) {
 		SMM_TRY(csrTransposeCreate(a, s, &built.m));
 		at = built.m;
@@ -160,8 +155,6 @@ static int bicgDev(const smm_hip_csr* a, const smm_hip_csr* at, const T* b, T* x
 	if (maxIterations == -1) maxIterations = n;
 	SMM_TRY(adoptPatternForSolver(a, maxIterations, s));
 	if (at != a) SMM_TRY(adoptPatternForSolver(at, maxIterations, s));
-	DevBuf<T> r, rt, p, pt, ap, atp, partsD, partsU;
-	DevBuf<Scal<T>> sc;
 	SMM_TRY(r.alloc(n));
 	SMM_TRY(rt.alloc(n));
 	SMM_TRY(p.alloc(n));
@@ -176,42 +169,21 @@ static int bicgDev(const smm_hip_csr* a, const smm_hip_csr* at, const T* b, T* x
 	SMM_TRY(launchCopy2<T>(n, r, pt, nullptr, s));
 	SMM_TRY(launchDotPartials<T>(n, r, r, partsD, nullptr, s));
 	bicgInitRho<T><<<1, TPB, 0, s>>>(partsD, sc);
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);
-	int nextCheck = 1;
-	int rc = SMM_HIP_OK;
-	for (int i = 0; i < planned && rc == SMM_HIP_OK; ++i) {
-		if (i == nextCheck) {
-			const int seen = poller.post(doneFlag);
-			if (seen < 0) rc = seen;
-			if (seen) break;
-			nextCheck = i + checkInterval(i);
-		}
-		rc = launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, pt, partsD, doneFlag, s);  // ref:2048-2049
-		if (rc == SMM_HIP_OK) rc = launchSpmv<T>(at, SMM_OP_ASSIGN, nullptr, pt, atp, 0, nullptr, nullptr, doneFlag, s);
-		if (rc != SMM_HIP_OK) break;
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 1));
+	for (int i = 0; i < planned && !watch.leave(i); ++i) {
+		SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, pt, partsD, doneFlag, s));  // ref:2048-2049
+		SMM_TRY(launchSpmv<T>(at, SMM_OP_ASSIGN, nullptr, pt, atp, 0, nullptr, nullptr, doneFlag, s));
 		bicgAlphaScal<T><<<1, TPB, 0, s>>>(partsD, sc, eps);
 		bicgUpdateXRR<T><<<NPART, TPB, 0, s>>>(n, sc, p, ap, atp, x, r, rt, partsU);
 		bicgBetaScal<T><<<1, TPB, 0, s>>>(partsU, sc, eps);
-		bicgUpdateP<T><<<gridFor(n), TPB, 0, s>>>(n, sc, r, rt, p, pt);
-	}
-	if (rc == SMM_HIP_OK) {
-		const hipError_t e = hipGetLastError();
-		if (e != hipSuccess) rc = hipFail(e, "bicg: launch", __FILE__, __LINE__);
+		bicgUpdateP<T><<<solverGrid(n), TPB, 0, s>>>(n, sc, r, rt, p, pt);
 	}
 	Scal<T> h;
-	if (rc == SMM_HIP_OK) {
-		const hipError_t e = hipMemcpyAsync(&h, sc.p, sizeof(Scal<T>), hipMemcpyDeviceToHost, s);
-		if (e != hipSuccess) rc = hipFail(e, "bicg: read scalars", __FILE__, __LINE__);
-	}
-	{
-		// also on a failed launch: kernels of the abandoned loop may still be queued on buffers (and a transpose) that are about to be released
-		const hipError_t e = hipStreamSynchronize(s);
-		if (e != hipSuccess && rc == SMM_HIP_OK) rc = hipFail(e, "bicg: synchronize", __FILE__, __LINE__);
-	}
-	if (rc != SMM_HIP_OK) return rc;
+	SMM_TRY(loopFinish(watch, &h, sc.p, sizeof(h), s));
+	drain.armed = false;
 	int st = h.status;
 	if (st == SMM_SOLVER_SUCCESS && h.iters > maxIterations) st = SMM_SOLVER_MAX_ITERATIONS_REACHED;  // ref:2098-2100
 	if (status) *status = st;
@@ -223,33 +195,10 @@ static int bicgDev(const smm_hip_csr* a, const smm_hip_csr* at, const T* b, T* x
 // host vectors: the reference's calling convention (x in / out)
 template <typename T>
 static int bicgHost(const smm_hip_csr* a, const smm_hip_csr* at, T* b, T* x, int maxIterations, T eps, int* status, int* iterations, T* resnorm2) {
-	if (!a) {
-		setError("bicg: null matrix");
-		return SMM_HIP_ERR_INVALID;
-	}
-	SMM_TRY(ensureInit());
-	const int n = a->rows;
-	if (n > 0 && (!b || !x)) {
-		setError("bicg: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx;
-	SMM_TRY(db.alloc(n));
-	SMM_TRY(dx.alloc(n));
-	if (n) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * n, s));
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * n, s));
-	}
-	const int rc = bicgDev<T>(a, at, db, dx, maxIterations, eps, s, status, iterations, resnorm2);
-	if (rc != SMM_HIP_OK) {
-		hipStreamSynchronize(s);  // (the copies in may still be in flight on buffers that are about to be released)
-		return rc;
-	}
-	if (n) {
-		SMM_TRY(devToHost(x, dx, sizeof(T) * n, s));
-	}
-	return SMM_HIP_OK;
+	SMM_TRY(solverCheck<T>("bicg", a, b, x));
+	return solveFromHost<T>(a->rows, b, nullptr, x, [&](const T* db, const T*, T* dx, hipStream_t s) {
+		return bicgDev<T>(a, at, db, dx, maxIterations, eps, s, status, iterations, resnorm2);
+	});
 }
 
 }  // namespace smm

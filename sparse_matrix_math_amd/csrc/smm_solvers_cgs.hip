@@ -15,6 +15,7 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_solver_host.h"
 #include "smm_solver_scal.h"
 
 namespace smm {
@@ -27,21 +28,6 @@ __global__ __launch_bounds__(TPB) void cgsCopy3(int n, const T* r, T* p, T* u, T
 	const T* const in[1] = {r};
 	T* const out[3] = {p, u, r0};
 	streamMap<T, false, 1, 3>(n, in, out, [&](const T(&v)[1], T(&o)[3]) { o[0] = o[1] = o[2] = v[0]; });
-}
-
-// rr0 = r.r0 (ref:2128); iterations = 0
-template <typename T>
-__global__ __launch_bounds__(TPB) void cgsInitScal(const T* __restrict__ partials, Scal<T>* sc) {
-	__shared__ T red[4];
-	const T rr0 = sumParts(partials, red);
-	if (threadIdx.x == 0) {
-		sc->rr = rr0;
-		sc->rrPing[0] = rr0;
-		sc->res = T(0);
-		sc->iters = 0;
-		sc->done = 0;
-		sc->status = SMM_SOLVER_SUCCESS;
-	}
 }
 
 // alpha = rr0 / (ap.r0) ; q = -alpha ap + u ; alphaUQ = alpha (u + q) ; x = x + alphaUQ   (ref:2133-2149; no breakdown test, ref:2134)
@@ -93,24 +79,10 @@ __global__ __launch_bounds__(TPB) void cgsFusedUP(int n, Scal<T>* sc, int par, i
 	});
 }
 
-static int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, NPART))); }
-static int checkInterval(int it) { return std::max(4, std::min(64, it / 4)); }
-
 template <typename T>
 static int cgsDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T eps, hipStream_t s, int* status, int* iterations, T* resnorm2) {
-	if (!a || a->dtype != dtypeOf<T>()) {
-		setError("cgs: null matrix or dtype mismatch");
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (a->rows != a->cols) {
-		setError("cgs: matrix must be square");
-		return SMM_HIP_ERR_INVALID;
-	}
+	SMM_TRY(solverCheck<T>("cgs", a, b, x));
 	const int n = a->rows;
-	if (n > 0 && (!b || !x)) {
-		setError("cgs: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
 	maxIterations = std::min(maxIterations, n);  // ref:2111
 	if (maxIterations == -1) maxIterations = n;  // ref:2112-2114
 	SMM_TRY(ensureCsrReady(a, s, true));
@@ -129,31 +101,22 @@ static int cgsDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T e
 	SMM_TRY(sc.alloc(1));
 
 	SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, r, 0, nullptr, nullptr, nullptr, s));  // ref:2118
-	if (n > 0) cgsCopy3<T><<<gridFor(n), TPB, 0, s>>>(n, r, p, u, r0);               // ref:2124-2126
+	if (n > 0) cgsCopy3<T><<<solverGrid(n), TPB, 0, s>>>(n, r, p, u, r0);               // ref:2124-2126
 	SMM_TRY(launchDotPartials<T>(n, r, r0, parts, nullptr, s));                       // ref:2128
-	cgsInitScal<T><<<1, TPB, 0, s>>>(parts, sc);
+	rr0InitScal<T><<<1, TPB, 0, s>>>(parts, sc);                                       // ref:2128 (smm_solver_scal.h)
 
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);  // do { } while: the body always runs once (ref:2131, 2172)
-	int nextCheck = 1;
-	for (int i = 0; i < planned; ++i) {
-		if (i == nextCheck) {
-			const int seen = poller.post(doneFlag);
-			if (seen < 0) return seen;
-			if (seen) break;
-			nextCheck = i + checkInterval(i);
-		}
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 1));
+	for (int i = 0; i < planned && !watch.leave(i); ++i) {
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, r0, parts, doneFlag, s));  // ref:2132-2133
-		SMM_LAUNCH_UPDATE(cgsFusedQX, updateNT(n, sizeof(T), 6), gridFor(n), s, n, sc, i & 1, parts, ap, u, x, q, alphaUQ);
+		SMM_LAUNCH_UPDATE(cgsFusedQX, updateNT(n, sizeof(T), 6), solverGrid(n), s, n, sc, i & 1, parts, ap, u, x, q, alphaUQ);
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, r, alphaUQ, r, 2, r0, parts2, doneFlag, s));  // ref:2151-2152 + 2171
-		SMM_LAUNCH_UPDATE(cgsFusedUP, updateNT(n, sizeof(T), 5), gridFor(n), s, n, sc, i & 1, i, maxIterations, parts2, eps, q, r, u, p);
+		SMM_LAUNCH_UPDATE(cgsFusedUP, updateNT(n, sizeof(T), 5), solverGrid(n), s, n, sc, i & 1, i, maxIterations, parts2, eps, q, r, u, p);
 	}
-	SMM_HIP_TRY(hipGetLastError());
 	Scal<T> h;
-	SMM_HIP_TRY(hipMemcpyAsync(&h, sc.p, sizeof(Scal<T>), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
+	SMM_TRY(loopFinish(watch, &h, sc.p, sizeof(h), s));
 	if (status) *status = h.iters > maxIterations ? SMM_SOLVER_MAX_ITERATIONS_REACHED : SMM_SOLVER_SUCCESS;  // ref:2174-2177
 	if (iterations) *iterations = h.iters;
 	if (resnorm2) *resnorm2 = h.res;
@@ -163,35 +126,16 @@ static int cgsDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T e
 // host vectors: the reference's calling convention (x in / out)
 template <typename T>
 static int cgsHost(const smm_hip_csr* a, T* b, T* x, int maxIterations, T eps, int* status, int* iterations, T* resnorm2) {
-	if (!a) {
-		setError("cgs: null matrix");
-		return SMM_HIP_ERR_INVALID;
-	}
-	SMM_TRY(ensureInit());
-	const int n = a->rows;
-	if (n > 0 && (!b || !x)) {
-		setError("cgs: null vector");
-		return SMM_HIP_ERR_INVALID;
-	}
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx;
-	SMM_TRY(db.alloc(n));
-	SMM_TRY(dx.alloc(n));
-	if (n) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * n, s));
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * n, s));
-	}
-	SMM_TRY(cgsDev<T>(a, db, dx, maxIterations, eps, s, status, iterations, resnorm2));
-	if (n) {
-		SMM_TRY(devToHost(x, dx, sizeof(T) * n, s));
-	}
-	return SMM_HIP_OK;
+	SMM_TRY(solverCheck<T>("cgs", a, b, x));
+	return solveFromHost<T>(a->rows, b, nullptr, x, [&](const T* db, const T*, T* dx, hipStream_t s) {
+		return cgsDev<T>(a, db, dx, maxIterations, eps, s, status, iterations, resnorm2);
+	});
 }
 
 // (see preloadSolversUnit, smm_solvers.hip)
 void preloadCgsUnit() {
 	hipFuncAttributes attr;
-	(void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(cgsInitScal<float>));
+	(void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(cgsCopy3<float>));
 	(void)hipGetLastError();
 }
 

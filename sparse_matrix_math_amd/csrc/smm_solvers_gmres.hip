@@ -19,6 +19,7 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_solver_host.h"
 #include "smm_solver_scal.h"
 
 namespace smm {
@@ -310,24 +311,12 @@ static int gridMV(long long n, size_t elemBytes) {
 	const long long tile = static_cast<long long>(TPB) * MV_U * (16 / static_cast<long long>(elemBytes));
 	return static_cast<int>(std::max<long long>(1, std::min<long long>((n + tile - 1) / tile, NPART)));
 }
-static int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, NPART))); }
 
 template <typename T>
 static int gmresCheck(const smm_hip_csr* a, const T* b, const T* x, int restart) {
-	if (!a || a->dtype != dtypeOf<T>()) {
-		setError("gmres: null matrix or dtype mismatch");
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (a->rows != a->cols) {
-		setError("gmres: matrix must be square");
-		return SMM_HIP_ERR_INVALID;
-	}
+	SMM_TRY(solverCheck<T>("gmres", a, b, x));
 	if (restart < 1 || restart > MAXR) {
 		setError("gmres: restart must be 1 .. %d", MAXR);
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (a->rows > 0 && (!b || !x)) {
-		setError("gmres: null vector");
 		return SMM_HIP_ERR_INVALID;
 	}
 	return SMM_HIP_OK;
@@ -367,20 +356,15 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, col(0), 0, nullptr, nullptr, first ? nullptr : solveOver, s));
 		SMM_TRY(launchDotPartials<T>(n, col(0), col(0), parts1, first ? nullptr : solveOver, s));
 		gmresOuter<T><<<1, TPB, 0, s>>>(sp, parts1, first, maxIterations, eps);
-		if (n > 0) gmresScale<T><<<gridFor(n), TPB, 0, s>>>(n, &sp->beta, col(0), col(0), cycleOver);
+		if (n > 0) gmresScale<T><<<solverGrid(n), TPB, 0, s>>>(n, &sp->beta, col(0), col(0), cycleOver);
 		return SMM_HIP_OK;
 	};
 	SMM_TRY(residual(1));
 
-	static thread_local DonePoller poller;
-	SMM_TRY(poller.init(s));
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, solveOver, 1, 1));  // asked before every cycle but the first
 	// every cycle that does not end the solve takes at least one step, so cycle c starts with at most maxIterations - c steps left
-	for (int c = 0; c < maxIterations; ++c) {
-		if (c > 0) {
-			const int seen = poller.post(solveOver);
-			if (seen < 0) return seen;
-			if (seen) break;
-		}
+	for (int c = 0; c < maxIterations && !watch.leave(c); ++c) {
 		const int steps = std::min(restart, maxIterations - c);
 		for (int j = 0; j < steps; ++j) {
 			const T* z = col(j);
@@ -397,7 +381,7 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
 			multiDotFinish<T><<<j + 1, TPB, 0, s>>>(parts, gmv, sp->h2, sp->coef, cycleOver);
 			multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, j + 1, nullptr, V.p, ld, sp->coef, w, w, parts1, cycleOver);
 			gmresStep<T><<<1, TPB, 0, s>>>(sp, parts1, gmv, j, restart, maxIterations, eps);
-			if (n > 0) gmresScale<T><<<gridFor(n), TPB, 0, s>>>(n, &sp->hn, w, w, cycleOver);
+			if (n > 0) gmresScale<T><<<solverGrid(n), TPB, 0, s>>>(n, &sp->hn, w, w, cycleOver);
 		}
 		// the end of the cycle: y, t = sum y_i v_i, x = x + M^-1 t, the residual again
 		gmresBackSub<T><<<1, TPB, 0, s>>>(sp);
@@ -407,20 +391,21 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
 			SMM_TRY(precondApplyDev<T>(M, tv, zv, solveOver, s));
 			z = zv;
 		}
-		if (n > 0) gmresAddX<T><<<gridFor(n), TPB, 0, s>>>(n, sp, z, x);
+		if (n > 0) gmresAddX<T><<<solverGrid(n), TPB, 0, s>>>(n, sp, z, x);
 		SMM_TRY(residual(0));
 	}
-	SMM_HIP_TRY(hipGetLastError());
-	int tail[8];  // cycleOver, solveOver, k, iters, status, pad
-	T rr = T(0);
-	SMM_HIP_TRY(hipMemcpyAsync(tail, &sp->cycleOver, sizeof(tail), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipMemcpyAsync(&rr, &sp->rr, sizeof(T), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
+	struct {  // GmresState<T> from `rr` on
+		T rr, beta, hn;
+		int cycleOver, solveOver, k, iters, status, pad[3];
+	} tail;
+	static_assert(sizeof(tail) == sizeof(GmresState<T>) - offsetof(GmresState<T>, rr), "the tail of GmresState");
+	SMM_TRY(loopFinish(watch, &tail, &sp->rr, sizeof(tail), s));
+	const T rr = tail.rr;
 	int st_out = SMM_SOLVER_MAX_ITERATIONS_REACHED;
-	if (tail[4] == SMM_SOLVER_DIVERGED || !std::isfinite(rr)) st_out = SMM_SOLVER_DIVERGED;
+	if (tail.status == SMM_SOLVER_DIVERGED || !std::isfinite(rr)) st_out = SMM_SOLVER_DIVERGED;
 	else if (rr <= eps * eps) st_out = SMM_SOLVER_SUCCESS;
 	if (status) *status = st_out;
-	if (iterations) *iterations = tail[3];
+	if (iterations) *iterations = tail.iters;
 	if (resnorm2) *resnorm2 = rr;
 	return precondition ? precondTakeError(M, s) : SMM_HIP_OK;
 }
@@ -429,21 +414,9 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
 template <typename T>
 static int gmresHost(const smm_hip_csr* a, T* b, T* x, int maxIterations, T eps, int restart, const smm_hip_precond* M, int* status, int* iterations, T* resnorm2) {
 	SMM_TRY(gmresCheck<T>(a, b, x, restart));
-	SMM_TRY(ensureInit());
-	const int n = a->rows;
-	hipStream_t s = libStream();
-	DevBuf<T> db, dx;
-	SMM_TRY(db.alloc(n));
-	SMM_TRY(dx.alloc(n));
-	if (n) {
-		SMM_TRY(hostToDev(db, b, sizeof(T) * n, s));
-		SMM_TRY(hostToDev(dx, x, sizeof(T) * n, s));
-	}
-	SMM_TRY(gmresDev<T>(a, db, dx, maxIterations, eps, restart, M, s, status, iterations, resnorm2));
-	if (n) {
-		SMM_TRY(devToHost(x, dx, sizeof(T) * n, s));
-	}
-	return SMM_HIP_OK;
+	return solveFromHost<T>(a->rows, b, nullptr, x, [&](const T* db, const T*, T* dx, hipStream_t s) {
+		return gmresDev<T>(a, db, dx, maxIterations, eps, restart, M, s, status, iterations, resnorm2);
+	});
 }
 
 static int multiCheck(const char* what, int n, int k, long long ld, bool nullArray) {

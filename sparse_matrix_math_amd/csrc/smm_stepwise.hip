@@ -9,6 +9,7 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_solver_host.h"
 
 namespace smm {
 
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(TPB) void stepUpdateP(int n, const StepState<T>* __
 	streamMap<T, false, 3, 1>(n, in, out, [&](const T(&v)[3], T(&o)[1]) { o[0] = smmFma(beta, smmFma(-omega, v[0], v[1]), v[2]); });
 }
 
-static int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, NPART))); }
+static int gridFor(long long n) { return solverGrid(n); }  // (smm_solver_host.h)
 
 template <typename T>
 static int wsCreate(int n, smm_hip_bicgstab_ws** out) {
