@@ -342,6 +342,40 @@ int smm_hip_csr_transpose_refresh_f64(smm_hip_csr* at, const smm_hip_csr* a, smm
 int smm_hip_csr_is_symmetric(const smm_hip_csr* a, int* pattern_symmetric, int* values_symmetric);
 int smm_hip_csr_get_pattern(const smm_hip_csr* m, int* start, int* positions);
 
+/* ---- the PRODUCT C = A B of two matrices, built on the device (csrc/smm_spgemm.hip); additions with no counterpart in the reference --------
+ * `a` is m x k, `b` is k x n, same dtype; C is m x n.
+ * Pattern: entry (i, j) is stored in C iff some p has (i, p) stored in `a` and (p, j) stored in `b` -- the structural product.  Terms that
+ *   cancel to 0 and explicitly stored zeros keep their entry: nothing is dropped by value.  Rows ascend, columns ascend inside a row;
+ *   start[m + 1], positions[nnz] and what smm_hip_csr_info reports are those of smm_hip_csr_create_* for the same arrays built on the host.
+ *   Legal: rectangular matrices, empty rows in `a`, rows of `b` that are empty or never referenced, nnz == 0, any of m, k, n equal to 0,
+ *   and a == b (A A).
+ * Values: c = +0.0; then, for the stored entries (i, p) of `a`'s row i IN STORED ORDER that have (p, j) stored in `b`:
+ *   c = _smm_fma(a_ip, b_pj, c) -- the row sum of rMult (ref:1484-1489).  No floating-point atomics and no tree sums: the result does not
+ *   depend on the launch geometry, two runs give the same bits.  Consequence: for finite values, column j of C equals A.rMult of the dense
+ *   column j of B at one lane per row, bit for bit, in both rounding flavours.
+ * Bad input: a column of `a` outside [0, k), a column of `b` outside [0, n) or a start[] that does not ascend from 0 (caller-owned device
+ *   arrays) is found by a flag on the device before it is used as an address: SMM_HIP_ERR_INVALID, never a fault; nothing is created.
+ * Limits: a product of more than 2^31 - 1 stored entries returns SMM_HIP_ERR_INVALID (the count of scalar products, sum of ub_i, is kept
+ *   in 64 bits and may exceed 32).
+ * multiply_create: the symbolic phase followed by the numeric phase.  *out owns its three arrays and does not depend on `a` or `b` -- an
+ *   smm_hip_csr like any other (AUTO kernel choice, PATTERN analysis on first use, edits, preconditioners, smm_hip_csr_same_pattern,
+ *   transpose).  Synchronises `stream` (nnz is needed on the host).  SMM_HIP_ERR_INVALID: a null handle, a dtype mismatch,
+ *   a.cols != b.rows.  Distributed handles (smm_hip_dist_csr) are not covered.
+ * multiply_into_*: the numeric phase only, into the existing pattern of `c`: every stored entry of `c` gets the value defined above, an
+ *   entry no product lands on gets +0.0.  `c` may come from multiply_create of matrices with these patterns, of supersets of them, or
+ *   from anywhere: no bookkeeping ties it to `a` or `b`.  A product whose (i, j) is not stored in `c` returns SMM_HIP_ERR_INVALID: `c`
+ *   keeps its old bits (values, pattern, kernel choice) and smm_hip_last_error() names the first such row.  The values are computed into
+ *   scratch memory (nnz(c) sizeof(T) bytes), the device flag is read -- the call synchronises `stream` --, and only then the scratch
+ *   becomes c's values (arrays the handle owns) or is copied into them (caller-owned arrays, smm_hip_csr_create_dev_*).  On success it
+ *   is a value edit of `c` with exactly the rules of smm_hip_csr_set_values_dev_*: what was derived from the pattern stays, what was
+ *   derived from the values follows.  SMM_HIP_ERR_INVALID, nothing changed: c == a or c == b, a null handle, a shape or dtype mismatch,
+ *   bad input as above.
+ * Cost beside the set-up passes (bins, scan, one segmented sort of positions[] in create): `a` read once per phase, sum of ub_i (s + 4)
+ *   bytes gathered from `b` (s = sizeof(T); 4 in each of the two symbolic passes), nnz(C) (s + 4) written. */
+int smm_hip_csr_multiply_create(const smm_hip_csr* a, const smm_hip_csr* b, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_multiply_into_f32(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b, smm_hip_stream stream);
+int smm_hip_csr_multiply_into_f64(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b, smm_hip_stream stream);
+
 /* ---- SpMV: CSRMatrix<T>::rMult / rMultAdd / rMultSub (ref:1458-1515) -------------------------------------- */
 /* out[i] = op(lhs[i], sum_k values[k]*x[positions[k]]); empty rows give op(lhs[i],0) (ref:1479-1483);
  * out may alias lhs, x must not alias out (ref:1503).  lhs is ignored for SMM_OP_ASSIGN. */

@@ -6,7 +6,7 @@
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
 //     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::loadMatrix
-//     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric)
+//     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto)
 //
 // compiles against this header unchanged and runs those calls on an MI355X: same names, same argument order and meaning,
 // same return values (SolverStatus; int != 0 on failure for init / apply).  Matrix assembly (TripletMatrix, CSR arrays)
@@ -82,6 +82,7 @@ struct Abi<float> {
 	static int getValues(const smm_hip_csr* m, float* v) { return smm_hip_csr_get_values_f32(m, v); }
 	static int assembled(const smm_hip_assembly* p, const float* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f32(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const float* v, int mode) { return smm_hip_assembly_refill_f32(p, m, v, mode); }
+	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f32(c, a, b, nullptr); }
 	static int spmm(const smm_hip_csr* m, int op, int k, const float* l, const float* x, float* o) { return smm_hip_spmm_f32(m, op, k, l, x, o); }
 	static int bicgstabBatch(const smm_hip_csr* a, int k, float* b, float* x, int it, float eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_bicgstab_batch_f32(a, k, b, x, it, eps, M, st, nullptr, nullptr);
@@ -115,6 +116,7 @@ struct Abi<double> {
 	static int getValues(const smm_hip_csr* m, double* v) { return smm_hip_csr_get_values_f64(m, v); }
 	static int assembled(const smm_hip_assembly* p, const double* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f64(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const double* v, int mode) { return smm_hip_assembly_refill_f64(p, m, v, mode); }
+	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f64(c, a, b, nullptr); }
 	static int spmm(const smm_hip_csr* m, int op, int k, const double* l, const double* x, double* o) { return smm_hip_spmm_f64(m, op, k, l, x, o); }
 	static int bicgstabBatch(const smm_hip_csr* a, int k, double* b, double* x, int it, double eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_bicgstab_batch_f64(a, k, b, x, it, eps, M, st, nullptr, nullptr);
@@ -571,6 +573,57 @@ public:
 		dev = d;
 		return 0;
 	}
+	// addition: this matrix becomes the product a b, built on the GPU through the two device mirrors (smm_hip.h "the PRODUCT C = A B": the
+	// structural product, columns ascending, every entry the row sum of rMult in a's stored order); the host arrays are filled from the
+	// device result and the built handle becomes this matrix's mirror.  Returns 0, or the SMM_HIP_* status (also in lastHipStatus()) with
+	// the matrix left empty.  a and b may be one matrix; neither may be this one.  SMM::multiply(a, b, out) is this call.
+	int initProductOf(const CSRMatrix& a, const CSRMatrix& b) noexcept {
+		if (&a == this || &b == this) return detail::note(SMM_HIP_ERR_INVALID);
+		release();
+		values.reset();
+		positions.reset();
+		start.reset();
+		denseRowCount = denseColCount = firstActiveStart = 0;
+		const smm_hip_csr* da = a.device();
+		if (!da) return detail::note(a.start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const smm_hip_csr* db = b.device();
+		if (!db) return detail::note(b.start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(smm_hip_csr_multiply_create(da, db, nullptr, &d)) != SMM_HIP_OK) return lastHipStatus();
+		int rows = 0, cols = 0, nnz = 0;
+		int abi = smm_hip_csr_info(d, &rows, &cols, &nnz, nullptr, nullptr);
+		std::unique_ptr<T[]> v(new T[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> p(new int[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> s(new int[rows + 1]());
+		if (abi == SMM_HIP_OK) abi = smm_hip_csr_get_pattern(d, s.get(), p.get());
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(d, v.get());
+		if (detail::note(abi) != SMM_HIP_OK) {
+			smm_hip_csr_destroy(d);
+			return abi;
+		}
+		values = std::move(v);
+		positions = std::move(p);
+		start = std::move(s);
+		denseRowCount = rows;
+		denseColCount = cols;
+		computeFirstActive();
+		dev = d;
+		return 0;
+	}
+	// addition: the numeric phase alone -- this matrix's values become those of a b on ITS pattern (+0.0 where no product lands), a bulk
+	// edit on the device like operator*=.  Non-zero (the SMM_HIP_* status, nothing changed): a product falls on an entry this matrix does
+	// not store, the shapes do not fit, a or b is this matrix, no GPU.  SMM::multiplyInto(c, a, b) is this call.
+	int multiplyInto(const CSRMatrix& a, const CSRMatrix& b) {
+		if (&a == this || &b == this) return detail::note(SMM_HIP_ERR_INVALID);
+		(void)device();
+		if (!flushedMirror()) return detail::note(start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const smm_hip_csr* da = a.device();
+		const smm_hip_csr* db = b.device();
+		if (!da || !db) return detail::note((a.start && b.start) ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const int abi = detail::Abi<T>::multiplyInto(dev, da, db);
+		deviceEdited(abi);
+		return abi;
+	}
 	// addition: new values for a matrix made by init(plan, ...) from the same plan -- those of init(plan, valuesIn), or added to the present
 	// ones (add) -- in one device pass; the pattern and what the library derived from it stay.  Non-zero (the SMM_HIP_* status): not this
 	// plan's matrix, no GPU; nothing changed then.
@@ -986,6 +1039,16 @@ inline bool isSymmetric(const CSRMatrix<T>& a) noexcept {
 	int pattern = 0, vals = 0;
 	if (!d || detail::note(smm_hip_csr_is_symmetric(d, &pattern, &vals)) != SMM_HIP_OK) return false;
 	return pattern != 0 && vals != 0;
+}
+// out becomes the product a b, built on the GPU (CSRMatrix::initProductOf); 0, or the SMM_HIP_* status with out left empty
+template <typename T>
+inline int multiply(const CSRMatrix<T>& a, const CSRMatrix<T>& b, CSRMatrix<T>& out) noexcept {
+	return out.initProductOf(a, b);
+}
+// the values of c become those of a b on c's own pattern (CSRMatrix::multiplyInto); 0, or the SMM_HIP_* status with c unchanged
+template <typename T>
+inline int multiplyInto(CSRMatrix<T>& c, const CSRMatrix<T>& a, const CSRMatrix<T>& b) {
+	return c.multiplyInto(a, b);
 }
 // BiCGSymmetric's text (ref:2021-2102) with the shadow sequence on `at`, the transpose of `a` (SMM::transpose): for matrices that are not
 // symmetric.  That `at` is the transpose is the caller's contract; `a` itself as `at` asserts symmetry and gives BiCGSymmetric's bits.

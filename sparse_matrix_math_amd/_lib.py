@@ -100,6 +100,7 @@ _TYPED = {
     "smm_hip_assembly_refill": (c_int, [_P, _P, _P, c_int]),
     "smm_hip_assembly_refill_dev": (c_int, [_P, _P, _P, c_int, _P]),
     "smm_hip_csr_transpose_refresh": (c_int, [_P, _P, _P]),
+    "smm_hip_csr_multiply_into": (c_int, [_P, _P, _P, _P]),
 }
 
 
@@ -133,6 +134,7 @@ _PLAIN = {
     "smm_hip_csr_transpose_create": (c_int, [_P, _P, POINTER(_P)]),
     "smm_hip_csr_is_symmetric": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "smm_hip_csr_get_pattern": (c_int, [_P, _P, _P]),
+    "smm_hip_csr_multiply_create": (c_int, [_P, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_create": (c_int, [c_int, c_int, c_longlong, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_create_dev": (c_int, [c_int, c_int, c_longlong, _P, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_longlong), POINTER(c_int), POINTER(c_int)]),

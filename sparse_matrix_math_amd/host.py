@@ -502,6 +502,28 @@ class CSRMatrix:
         check(_lib.load().smm_hip_csr_get_pattern(self._h, _host(start, np.int32, "start"), _host(positions, np.int32, "positions")))
         return start, positions
 
+    # ---- the product of two matrices, built on the device (smm_hip.h "the PRODUCT C = A B") ----
+    def multiply(self, B, stream=None):
+        """self B as a new CSRMatrix that owns its arrays: the structural product (nothing dropped by value), columns ascending; every
+        entry is the row sum of rMult over this matrix's entries in stored order, bit for bit.  Synchronises `stream`."""
+        if not isinstance(B, CSRMatrix):
+            raise TypeError("multiply needs a CSRMatrix")
+        h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_csr_multiply_create(self._h, B._h, _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, self.dtype)
+
+    def __matmul__(self, B):
+        if not isinstance(B, CSRMatrix):
+            return NotImplemented
+        return self.multiply(B)
+
+    def multiply_into(self, A, B, stream=None):
+        """the numeric phase alone: this matrix's values become those of A B on ITS pattern (+0.0 where no product lands) -- a value edit
+        of this matrix.  SmmHipError (SMM_HIP_ERR_INVALID, nothing changed) when a product falls on an entry this matrix does not store.
+        Synchronises `stream`."""
+        check(_fn("smm_hip_csr_multiply_into", self._suf)(self._h, A._h, B._h, _dptr(stream)))
+        self._edited(stream)
+
     def spmv_fused_dev(self, op, d_lhs, d_x, d_out, dot_mode, d_w1, d_partials, stream=None, finish=False):
         """SpMV with the dot products of the fresh out[] in its epilogue (dot_mode 1: out.w1; 2: out.out and out.w1).  finish=False:
         d_partials receives 2 x partials_count() per-workgroup sums; finish=True: d_partials is a finishing buffer of finish_len()
