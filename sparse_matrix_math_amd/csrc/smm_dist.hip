@@ -74,7 +74,7 @@ static RcclApi* rccl() {
 	std::lock_guard<std::mutex> lock(mu);
 	if (api.handle) return &api;
 	// the copy PyTorch already mapped (same SONAME) wins, so one RCCL serves both; otherwise the system ROCm one
-	const char* candidates[] = {getenv("SMM_HIP_RCCL_PATH"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+	const char* candidates[] = {env::raw(env::RCCL_PATH), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
 	void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
 	for (const char* c : candidates) {
 		if (h) break;
@@ -164,12 +164,8 @@ static hipEvent_t takeEvent(smm_hip_comm* c) {
 // distributed call aborts the communicator too (guardComm), so that the peers run into THEIR bounded wait instead of hanging in the
 // next collective.  The process is expected to exit then (bench.py does, with a non-zero status).
 static double commTimeoutSeconds() {
-	static const double t = [] {
-		const char* env = getenv("SMM_HIP_COMM_TIMEOUT_S");
-		const double v = env ? atof(env) : 180.0;
-		return v > 0 ? v : 180.0;
-	}();
-	return t;
+	const double v = env::doubleOr(env::COMM_TIMEOUT_S, 180.0);
+	return v > 0 ? v : 180.0;
 }
 
 static void commAbort(smm_hip_comm* c) {
@@ -656,11 +652,7 @@ static void planHaloFirst(smm_hip_dist_csr* D) {
 	D->bulk.n = 1;
 	D->bulk.lo[0] = 0;
 	D->bulk.hi[0] = n;
-	static const bool allowed = [] {
-		const char* env = getenv("SMM_HIP_HALO_FIRST");
-		return env ? atoi(env) != 0 : true;
-	}();
-	if (!allowed || D->sends.empty() || n <= 0) return;
+	if (!env::flagOr(env::HALO_FIRST, true) || D->sends.empty() || n <= 0) return;
 	constexpr int VEC = 16 / sizeof(T);
 	std::vector<std::pair<int, int>> runs;
 	for (const Seg& g : D->sends) {
@@ -827,12 +819,8 @@ static void p2pTeardown(smm_hip_dist_csr* D) {
 }
 
 static long long p2pTicks() {
-	static const long long t = [] {
-		const char* env = getenv("SMM_HIP_P2P_TIMEOUT_S");
-		const double sec = env && atof(env) > 0 ? atof(env) : 20.0;
-		return static_cast<long long>(sec * 1.0e8);  // wall_clock64 counts at 100 MHz on gfx9
-	}();
-	return t;
+	const double sec = env::doubleOr(env::P2P_TIMEOUT_S, 20.0);
+	return static_cast<long long>((sec > 0 ? sec : 20.0) * 1.0e8);  // wall_clock64 counts at 100 MHz on gfx9
 }
 
 // sum of one 0 / 1 vote per rank == world?
@@ -858,13 +846,12 @@ static int p2pSetup(smm_hip_dist_csr* D) {
 	const int world = c->world, rank = c->rank;
 	// (SMM_HIP_LAB_SELF_P2P=1, single-rank communicator: the slots with ONE rank -- what a rank of a many-GPU run launches per iteration in this
 	// transport, measured on one GPU; tools/lab/rank_loop_streams.py)
-	const bool labSelf = world == 1 && c->kind == SMM_COMM_SELF && getenv("SMM_HIP_LAB_SELF_P2P") && atoi(getenv("SMM_HIP_LAB_SELF_P2P")) != 0;
+	const bool labSelf = world == 1 && c->kind == SMM_COMM_SELF && env::flagOr(env::LAB_SELF_P2P, false);
 	if ((world < 2 && !labSelf) || world > P2P_MAX_WORLD) return SMM_HIP_OK;
 	// r06: ON unless a rank says SMM_HIP_P2P=0 -- the transport is taken whenever EVERY rank can allocate, export and map the blocks and passes
 	// the self-test below; anything less leaves all ranks with the communicator's collectives (read at every create, like SMM_HIP_HALO_CHUNKS)
-	const char* env = getenv("SMM_HIP_P2P");
 	bool all = false;
-	SMM_TRY(p2pAllAgree(c, !(env && atoi(env) == 0) && D->chunks == 1, &all));
+	SMM_TRY(p2pAllAgree(c, env::flagOr(env::P2P, true) && D->chunks == 1, &all));
 	if (!all) return SMM_HIP_OK;
 	std::unique_ptr<P2PState> owner(new P2PState());
 	P2PState* P = owner.get();
@@ -872,12 +859,11 @@ static int p2pSetup(smm_hip_dist_csr* D) {
 	P->rank = rank;
 	P->ticks = p2pTicks();
 	{
-		const char* r = getenv("SMM_HIP_P2P_RELAYS");
-		P->relays = r ? atoi(r) : std::max(0, world - 4);  // 8 ranks: 4 relays per segment -- half of it direct, an eighth through each relay
+		P->relays = env::intOr(env::P2P_RELAYS, std::max(0, world - 4));  // 8 ranks: 4 relays per segment -- half of it direct, an eighth through each relay
 		P->relays = std::max(0, std::min(std::min(P->relays, world - 2), P2P_MAX_PATHS - 1));
 		// the direct link carries its share once; a relay's links carry up to two shares in each of the two stages: d = 4 rho, d + R rho = 1
 		P->directShare = 4.0 / (P->relays + 4.0);
-		if (const char* d = getenv("SMM_HIP_P2P_DIRECT_SHARE")) P->directShare = std::min(1.0, std::max(0.05, atof(d)));
+		if (env::isSet(env::P2P_DIRECT_SHARE)) P->directShare = std::min(1.0, std::max(0.05, env::doubleOr(env::P2P_DIRECT_SHARE, 1.0)));
 		if (P->relays == 0) P->directShare = 1.0;
 	}
 	// ---- the plan, from global knowledge: what I receive, what I send (directly / staged at a relay), what I forward
@@ -1116,8 +1102,8 @@ static int p2pSetup(smm_hip_dist_csr* D) {
 	// element of every rank must hold ITS column's number -- once through the areas of each vector kind, then twice more back to back through
 	// the last kind's (a push then waits for the acknowledgement of the exchange before).  A failure here leaves the HALO with the
 	// communicator's grouped send / receive and keeps the scalars in the slots (the hybrid: a reduction point costs ~3 us instead of ~23).
-	const char* haloEnv = getenv("SMM_HIP_P2P_HALO");  // 0: do not try (tests of the hybrid)
-	pass = !(haloEnv && atoi(haloEnv) == 0);
+	const bool haloWanted = env::flagOr(env::P2P_HALO, true);  // 0: do not try (tests of the hybrid)
+	pass = haloWanted;
 	{
 		T* xExt = static_cast<T*>(D->xExt);
 		std::vector<T> host(static_cast<size_t>(D->extLen), T(-1));
@@ -1146,7 +1132,7 @@ static int p2pSetup(smm_hip_dist_csr* D) {
 	}
 	SMM_TRY(p2pAllAgree(c, pass, &all));
 	if (!all) {
-		if (!pass && !(haloEnv && atoi(haloEnv) == 0)) {
+		if (!pass && haloWanted) {
 			fprintf(stderr, "libsmm_hip: rank %d: the peer-to-peer self-test (halo) failed; the halo stays with the communicator's send / receive on every rank\n", rank);
 		}
 		// every rank is past its own waits (each synchronised its stream above, and the vote was a collective): the error words of the halo part
@@ -1314,15 +1300,13 @@ static int distCreate(smm_hip_comm* comm, int nGlobal, const int* bounds, const 
 	int* startRem = cnt + nLocal + 1;
 	const int grid = std::max(1, std::min(8192, (nLocal + 256) / 256));
 	{
-		const char* env = getenv("SMM_HIP_SPLIT_SPMV");  // (read at every create, like SMM_HIP_HALO_CHUNKS: a property of the matrix)
-		D->splitAllowed = env ? atoi(env) != 0 : true;
-		D->splitForced = env && atoi(env) == 2;  // (2: also between ranks that share a GPU -- the tests, whose matrices leave the card half empty)
-		const char* lds = getenv("SMM_HIP_SPLIT_SUMS_LDS");
-		if (lds) D->splitSumsLdsMax = std::max(0, atoi(lds));
+		const int split = env::intOr(env::SPLIT_SPMV, 1);  // (read at every create, like SMM_HIP_HALO_CHUNKS: a property of the matrix)
+		D->splitAllowed = split != 0;
+		D->splitForced = split == 2;  // (2: also between ranks that share a GPU -- the tests, whose matrices leave the card half empty)
+		D->splitSumsLdsMax = std::max(0, env::intOr(env::SPLIT_SUMS_LDS, D->splitSumsLdsMax));
 	}
 	if (comm->kind == SMM_COMM_SELF) {
-		const char* env = getenv("SMM_HIP_LAB_SELF_SPLIT");  // (measurement hook: what a rank of a many-GPU run computes, on one GPU -- tools/lab/rank_loop_streams.py)
-		D->labWindow = env ? atoi(env) : 0;
+		D->labWindow = env::intOr(env::LAB_SELF_SPLIT, 0);  // (measurement hook: what a rank of a many-GPU run computes, on one GPU -- tools/lab/rank_loop_streams.py)
 	}
 	splitCountKernel<<<grid, 256, 0, s>>>(nLocal, d_start, d_positions, D->rowBegin, D->rowEnd, D->labWindow, startLoc, startRem);
 	SMM_HIP_TRY(hipGetLastError());
@@ -1355,8 +1339,7 @@ static int distCreate(smm_hip_comm* comm, int nGlobal, const int* bounds, const 
 	}
 	// ---- a thin remote block: the rows with a remote entry, listed (each rank for itself: nothing collective depends on it)
 	{
-		const char* env = getenv("SMM_HIP_THIN_REMOTE");  // (read at every create: a property of the matrix; 0: the general second launch)
-		const bool allowed = env ? atoi(env) != 0 : true;
+		const bool allowed = env::flagOr(env::THIN_REMOTE, true);  // (read at every create: a property of the matrix; 0: the general second launch)
 		if (allowed && nLocal > 0 && totals[1] > 0) {
 			DevBuf<int> flag;
 			SMM_TRY(flag.alloc(static_cast<size_t>(nLocal) + 1));
@@ -1379,8 +1362,7 @@ static int distCreate(smm_hip_comm* comm, int nGlobal, const int* bounds, const 
 	}
 	// ---- the halo in pieces (opt-in): every rank must cut alike, so the ranks agree on the smallest request
 	{
-		const char* env = getenv("SMM_HIP_HALO_CHUNKS");  // (read at every create: a property of the matrix, not of the process)
-		const int wanted = env ? std::max(1, std::min(MAX_HALO_CHUNKS, atoi(env))) : 1;
+		const int wanted = std::max(1, std::min(MAX_HALO_CHUNKS, env::intOr(env::HALO_CHUNKS, 1)));  // (read at every create: a property of the matrix, not of the process)
 		std::vector<long long> votes(static_cast<size_t>(world), 0);
 		// (a rank whose segments do not fit the cut's table asks for one piece)
 		votes[static_cast<size_t>(rank)] = D->recvs.size() > static_cast<size_t>(MAX_CHUNK_SEGS) ? 1 : wanted;
@@ -2430,7 +2412,7 @@ static int distCg(smm_hip_dist_csr* D, const T* b, const T* x0, T* x, int maxIte
 			SMM_HIP_TRY(hipMemsetAsync(D->rExt, 0, eb, s));
 		}
 	}
-	if (getenv("SMM_HIP_DIST_DEBUG")) {
+	if (env::isSet(env::DIST_DEBUG)) {
 		const smm_hip_csr* m = D->aLoc;
 		fprintf(stderr, "libsmm_hip: dist_cg rank %d: lazy %d, local block fusable %d (family %d lanes %d state %d encoding %d const %d const_off %d clusters %d), remote empty %d thin rows %d, candidate %d\n",
 		        D->comm->rank, lazy ? 1 : 0, m && constMarchFusable(m, sizeof(T)) ? 1 : 0, m ? m->family() : -1, m ? m->lanes() : -1, m ? static_cast<int>(m->pat_state.load()) : -1,

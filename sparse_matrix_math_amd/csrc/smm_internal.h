@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "../../include/smm_hip.h"
+#include "smm_env.h"
 
 namespace smm {
 
@@ -44,13 +46,7 @@ int hipFail(hipError_t e, const char* what, const char* file, int line);
 struct SetupTrace {
 	const char* what;
 	std::chrono::steady_clock::time_point t0;
-	static bool on() {
-		static const bool v = [] {
-			const char* env = getenv("SMM_HIP_TRACE_SETUP");
-			return env && atoi(env) != 0;
-		}();
-		return v;
-	}
+	static bool on() { return env::flagOr(env::TRACE_SETUP, false); }
 	explicit SetupTrace(const char* w) : what(w) {  // (null: this stage is not traced)
 		if (what && on()) t0 = std::chrono::steady_clock::now();
 	}
@@ -297,10 +293,7 @@ constexpr int PARTS_LEN = 2 * NPART + 2 + 2 * (PARTS_TICKETS + 1);  // elements 
 template <typename T>
 __host__ __device__ inline unsigned* partsTicket(T* partials) { return reinterpret_cast<unsigned*>(partials + PARTS_TOTALS + 2); }
 inline int spmvOutFlags(const smm_hip_csr* m, size_t elemBytes) {
-	static const int forced = [] {  // SMM_HIP_NT_OUT=0 / 1: A/B measurements of the store policy
-		const char* env = getenv("SMM_HIP_NT_OUT");
-		return env ? atoi(env) : -1;
-	}();
+	const int forced = env::intOr(env::NT_OUT, -1);  // SMM_HIP_NT_OUT=0 / 1: A/B measurements of the store policy
 	if (forced >= 0) return forced ? SPMV_NT_OUT : 0;
 	// (from 64 MiB per vector, inclusive: config 4's fp32 slab at 8 GPUs is exactly that -- CG there 139 -> 124 us per iteration with the non-temporal
 	// policy and the fused direction it brings, profiles/r06/dist_cg_timing_nt.txt)
@@ -384,12 +377,13 @@ inline bool ensureDynamicLds(std::atomic<int>& granted, K kernel, size_t lds) {
 	return true;
 }
 // SMM_HIP_STREAM_WGS_PER_CU (measurements): workgroups per CU of the persistent STREAM / PATTERN grids; 0: ask the runtime.  Read once.
-inline int forcedWgsPerCU() {
-	static const int forced = [] {
-		const char* env = getenv("SMM_HIP_STREAM_WGS_PER_CU");
-		return env ? (atoi(env) > 1 ? atoi(env) : 1) : 0;
-	}();
-	return forced;
+inline int forcedWgsPerCU() { return env::isSet(env::STREAM_WGS_PER_CU) ? std::max(1, env::intOr(env::STREAM_WGS_PER_CU, 0)) : 0; }
+// How a persistent SpMV grid deals its tiles to the 8 XCDs, from farTiles = how many tiles apart two uses of the same x[] line are: when
+// that is many tiles but a small part of the matrix (3-D stencils: one grid plane) the tiles are dealt one such span per XCD in turn, else
+// (0) one contiguous eighth each.  SMM_HIP_XCD_CHUNK_TILES overrides (tuning; read at every ask).
+inline int xcdChunkTiles(long long farTiles, int nTiles) {
+	const int chunk = farTiles >= 256 && farTiles * 32 <= nTiles ? static_cast<int>(farTiles) : 0;
+	return std::max(0, env::intOr(env::XCD_CHUNK_TILES, chunk));
 }
 
 bool cgHalfTiles(const smm_hip_csr* m, size_t elemBytes);  // (smm_spmv_march.hip)
@@ -399,6 +393,9 @@ long long cgLazyMinBytes();
 bool updateNT(long long n, size_t elemBytes, int vectors);
 bool masksMarchApplies(const smm_hip_csr* m);  // the masks kernels' march form serves this (analysed) matrix
 bool constMarchApplies(const smm_hip_csr* m);  // ... the constant-diagonal march
+// the two forms are not switched off (SMM_HIP_MASKS_MARCH=0 keeps the wave kernel, SMM_HIP_CONST_MARCH=0 the gather kernel: A/B measurements)
+inline bool masksMarchEnabled() { return env::flagOr(env::MASKS_MARCH, true); }
+inline bool constMarchEnabled() { return env::flagOr(env::CONST_MARCH, true); }
 template <typename T>
 bool launchPatMasksMarch(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                          const int* doneFlag, hipStream_t s);

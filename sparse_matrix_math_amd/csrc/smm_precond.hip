@@ -693,11 +693,10 @@ static int scratchFor(const smm_hip_precond* M, size_t elemBytes, hipStream_t s,
 // (measured: 108^3 stencil 1.8 / 2.7 / 4.7 ms per apply with 1024 / 2048 / 4096 wavefronts).  So the launch is sized to a few
 // levels' worth of rows, in one-wavefront workgroups so that they spread over the CUs.
 static int sweepWaves(int n, size_t levels, bool oneXcd = false) {
-	double perLevel = oneXcd ? 3.0 : 4.0;
-	if (const char* env = getenv("SMM_HIP_SWEEP_WAVES_PER_LEVEL")) perLevel = std::max(0.25, atof(env));
+	const double perLevel = std::max(0.25, env::doubleOr(env::SWEEP_WAVES_PER_LEVEL, oneXcd ? 3.0 : 4.0));
 	const double rowsPerLevel = static_cast<double>(n) / static_cast<double>(std::max<size_t>(1, levels));
 	long long waves = static_cast<long long>(perLevel * rowsPerLevel / WAVE) + 1;
-	if (const char* env = getenv("SMM_HIP_SWEEP_WAVES")) waves = std::max(1, atoi(env));
+	if (env::isSet(env::SWEEP_WAVES)) waves = std::max(1, env::intOr(env::SWEEP_WAVES, 1));
 	const long long all = (static_cast<long long>(n) + WAVE - 1) / WAVE;
 	const long long cap = oneXcd ? static_cast<long long>(numCUs() / 8) * 16 : static_cast<long long>(numCUs()) * 8;  // resident wavefronts
 	return static_cast<int>(std::max<long long>(1, std::min<long long>(std::min<long long>(waves, all), cap)));
@@ -754,8 +753,7 @@ static int sweepModeOf(const smm_hip_precond* M) {
 	int mode = plan->sweep;
 	if (mode == SMM_SWEEP_AUTO) {
 		const size_t levels = std::max<size_t>(1, std::min(M->lvl_ptr_lo.size(), M->lvl_ptr_up.size()) - 1);
-		mode = static_cast<size_t>(M->a->rows) / levels <= 2048 ? SMM_SWEEP_SYNCFREE_XCD : SMM_SWEEP_SYNCFREE;
-		if (const char* env = getenv("SMM_HIP_SWEEP")) mode = atoi(env);
+		mode = env::intOr(env::SWEEP, static_cast<size_t>(M->a->rows) / levels <= 2048 ? SMM_SWEEP_SYNCFREE_XCD : SMM_SWEEP_SYNCFREE);
 	}
 	return mode;
 }

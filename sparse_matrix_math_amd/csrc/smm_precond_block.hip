@@ -1091,13 +1091,7 @@ static bool brickGrid(const smm_hip_csr* a, int* nx, int* ny) {
 }
 
 // SMM_HIP_BLOCK_BRICKS=0: always the contiguous cut
-static bool bricksAllowed() {
-	static const bool on = [] {
-		const char* env = getenv("SMM_HIP_BLOCK_BRICKS");
-		return env ? atoi(env) != 0 : true;
-	}();
-	return on;
-}
+static bool bricksAllowed() { return env::flagOr(env::BLOCK_BRICKS, true); }
 
 // fills B->d_rowOrder / d_invOrder / d_bounds / nBlocks / brick[]; returns SMM_HIP_OK with B->d_rowOrder == nullptr when the matrix is
 // not a grid stencil (the caller then cuts contiguous blocks)
@@ -1233,14 +1227,12 @@ int blockCreateTyped(const smm_hip_csr* a, int kind, int blockRows, int levelCap
 	const int most = std::max(h[0], h[1]);
 	B->kreg = most <= 2 ? 2 : most <= 3 ? 3 : most <= 4 ? 4 : 8;  // (3: the rows of a 7-point stencil inside a brick)
 	B->overflow = most > 8;
-	if (const char* env = getenv("SMM_HIP_BLOCK_KREG")) {  // testing: force the overflow path on matrices with short rows
-		const int k = atoi(env);
-		if (k == 2 || k == 3 || k == 4 || k == 8) {
-			B->kreg = std::max(B->kreg, k);
-		} else if (k == -8) {
-			B->kreg = 8;
-			B->overflow = true;
-		}
+	const int k = env::intOr(env::BLOCK_KREG, 0);  // testing: force the overflow path on matrices with short rows
+	if (k == 2 || k == 3 || k == 4 || k == 8) {
+		B->kreg = std::max(B->kreg, k);
+	} else if (k == -8) {
+		B->kreg = 8;
+		B->overflow = true;
 	}
 	if (B->overflow) {
 		SMM_TRY(devAlloc(reinterpret_cast<void**>(&B->d_ovPtrLo), (nRec + 1) * sizeof(int)));
@@ -1306,10 +1298,7 @@ template <typename T, int KIND, int KREG, bool OV>
 static int launchBlkApply(const smm_hip_precond* M, const BlkApplyArgs<T>& args, hipStream_t s) {
 	const smm_precond_block* B = M->blk;
 	// chunks in flight per sweep (SMM_HIP_BLOCK_DEPTH = 1 / 2 / 4 / 8 overrides where compiled: measurements)
-	static const int depth = [] {
-		const char* env = getenv("SMM_HIP_BLOCK_DEPTH");
-		return env ? atoi(env) : 0;
-	}();
+	const int depth = env::intOr(env::BLOCK_DEPTH, 0);
 	const int grid = std::min(B->nBlocks, NPART);
 	const size_t lds = static_cast<size_t>(B->blockRows) * sizeof(T);
 	if (args.spmvX) {
@@ -1431,9 +1420,9 @@ int blockApplySpmvDev(const smm_hip_precond* M, const T* v, T* x, int dotMode, c
 bool blockFuseSpmv(const smm_hip_precond* M, bool asked) {
 	if (!M || !M->blk || M->blk->nBlocks > NPART) return false;  // (one workgroup per block: the helper wavefronts leave early)
 	if (M->blk->nBlocks == 0 || !M->a || M->a->nnz <= 0) return false;  // (nothing to multiply: the plain apply knows what to do)
-	const char* env = getenv("SMM_HIP_BLOCK_FUSE_SPMV");
-	if (env && env[0] == '0') return false;
-	if (asked || (env && env[0] == '1')) return true;
+	const char* forced = env::raw(env::BLOCK_FUSE_SPMV);
+	if (forced && forced[0] == '0') return false;
+	if (asked || (forced && forced[0] == '1')) return true;
 	return blkMaskForm(M->a) || M->blk->nBlocks <= 4 * numCUs();
 }
 
@@ -1466,14 +1455,12 @@ void blockLevels(const smm_precond_block* B, int* lo, int* up) {
 
 // SMM_HIP_BLOCK_LEVEL_CAP: the default level cut of a block preconditioner (0 = none)
 int blockDefaultLevelCap() {
-	int cap = BLK_DEFAULT_LEVEL_CAP;
-	if (const char* env = getenv("SMM_HIP_BLOCK_LEVEL_CAP")) cap = atoi(env);
+	const int cap = env::intOr(env::BLOCK_LEVEL_CAP, BLK_DEFAULT_LEVEL_CAP);
 	return cap < 2 ? 0 : std::min(cap, 4095);
 }
 
 int blockDefaultRows() {
-	int rows = BLK_DEFAULT_ROWS;
-	if (const char* env = getenv("SMM_HIP_BLOCK_ROWS")) rows = atoi(env);
+	const int rows = env::intOr(env::BLOCK_ROWS, BLK_DEFAULT_ROWS);
 	return std::max(BLK_MIN_ROWS, std::min(BLK_MAX_ROWS, rows));
 }
 

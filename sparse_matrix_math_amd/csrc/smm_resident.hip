@@ -335,8 +335,7 @@ static int maxRowLen(const smm_hip_csr* cm, hipStream_t s, int* out) {
 // SMM_CG_RESIDENT_OFF / AUTO / REQUIRE; the environment variable SMM_HIP_CG_RESIDENT sets the initial value
 static std::atomic<int>& residentModeRef() {
 	static std::atomic<int> mode{[] {
-		const char* e = getenv("SMM_HIP_CG_RESIDENT");
-		const int v = e ? atoi(e) : SMM_CG_RESIDENT_AUTO;
+		const int v = env::intOr(env::CG_RESIDENT, SMM_CG_RESIDENT_AUTO);
 		return v < SMM_CG_RESIDENT_OFF || v > SMM_CG_RESIDENT_REQUIRE ? SMM_CG_RESIDENT_AUTO : v;
 	}()};
 	return mode;
@@ -469,7 +468,7 @@ int cgResidentTry(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIt
 	// is to fall back quickly, and -- below -- to stop trying for the rest of the process.
 	args.waitTicks = mode == SMM_CG_RESIDENT_REQUIRE ? 1LL << 22 : 1LL << 19;
 #ifdef SMM_RESIDENT_LAB
-	args.lab = getenv("SMM_RESIDENT_LAB") ? atoi(getenv("SMM_RESIDENT_LAB")) : 0;
+	args.lab = env::intOr(env::RESIDENT_LAB, 0);
 	if (args.lab & 2) args.waitTicks = -1;
 #endif
 	ResidentOut<T> h;

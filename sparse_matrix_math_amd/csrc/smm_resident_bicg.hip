@@ -321,8 +321,7 @@ __global__ __launch_bounds__(256) void ellFromMasksKernel(int n, int k, const in
 // SMM_CG_RESIDENT_OFF / AUTO / REQUIRE (shared constants); the environment variable SMM_HIP_BICGSTAB_RESIDENT sets the initial value
 static std::atomic<int>& bicgResidentModeRef() {
 	static std::atomic<int> mode{[] {
-		const char* e = getenv("SMM_HIP_BICGSTAB_RESIDENT");
-		const int v = e ? atoi(e) : SMM_CG_RESIDENT_AUTO;
+		const int v = env::intOr(env::BICGSTAB_RESIDENT, SMM_CG_RESIDENT_AUTO);
 		return v < SMM_CG_RESIDENT_OFF || v > SMM_CG_RESIDENT_REQUIRE ? SMM_CG_RESIDENT_AUTO : v;
 	}()};
 	return mode;

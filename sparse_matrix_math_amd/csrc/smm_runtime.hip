@@ -58,11 +58,7 @@ static int initLocked(int device) {
 	SMM_HIP_TRY(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
 	g_device = device;
 	g_inited = true;
-	static const bool preload = [] {
-		const char* env = getenv("SMM_HIP_PRELOAD");
-		return env ? atoi(env) != 0 : true;
-	}();
-	if (preload) {
+	if (env::flagOr(env::PRELOAD, true)) {
 		SetupTrace trace("init: code objects of the hot path");
 		hipFuncAttributes attr;
 		(void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(countLeadingEmpty));
@@ -91,9 +87,7 @@ int ensureInit() {
 		if (e != hipSuccess) return hipFail(e, "hipSetDevice", __FILE__, __LINE__);
 		return SMM_HIP_OK;
 	}
-	int dev = 0;
-	if (const char* env = getenv("SMM_HIP_DEVICE")) dev = atoi(env);
-	return initLocked(dev);
+	return initLocked(env::intOr(env::DEVICE, 0));
 }
 
 hipStream_t libStream() { return g_stream; }
@@ -400,13 +394,7 @@ static CopyStage& copyStage() {
 	return st;
 }
 
-static bool stagedCopies() {
-	static const bool on = [] {
-		const char* env = getenv("SMM_HIP_STAGED_COPIES");  // 0: hand the caller's pointers to hipMemcpyAsync as before (measurements)
-		return env ? atoi(env) != 0 : true;
-	}();
-	return on;
-}
+static bool stagedCopies() { return env::flagOr(env::STAGED_COPIES, true); }  // 0: hand the caller's pointers to hipMemcpyAsync as before (measurements)
 
 int hostToDev(void* d_dst, const void* h_src, size_t bytes, hipStream_t s) {
 	if (!bytes) return SMM_HIP_OK;

@@ -469,10 +469,7 @@ __global__ __launch_bounds__(TPB) void bsymUpdateP(int n, const Scal<T>* __restr
 // Non-temporal loads / stores for an update kernel whose vectors cannot stay in the 256 MB Infinity Cache until the next kernel
 // reads them anyway; cache-resident problems keep the default policy.  SMM_HIP_UPDATE_NT=0/1 overrides (measurements).
 bool updateNT(long long n, size_t elemBytes, int vectors) {
-	static const int forced = [] {
-		const char* env = getenv("SMM_HIP_UPDATE_NT");
-		return env ? atoi(env) : -1;
-	}();
+	const int forced = env::intOr(env::UPDATE_NT, -1);
 	if (forced >= 0) return forced != 0;
 	return static_cast<double>(n) * static_cast<double>(elemBytes) * vectors > 192.0 * 1024 * 1024;
 }
@@ -483,11 +480,7 @@ static std::atomic<long long> g_lazyMinBytes{-1};
 long long cgLazyMinBytes() {
 	const long long forced = g_lazyMinBytes.load(std::memory_order_relaxed);
 	if (forced >= 0) return forced;
-	static const long long env = [] {
-		const char* e = getenv("SMM_HIP_CG_LAZY_X");
-		return e && atoi(e) == 0 ? (1LL << 62) : (64LL << 20);
-	}();
-	return env;
+	return env::flagOr(env::CG_LAZY_X, true) ? (64LL << 20) : (1LL << 62);
 }
 
 template <typename T>

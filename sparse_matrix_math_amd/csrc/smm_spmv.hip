@@ -824,12 +824,7 @@ int buildTileTable(const smm_hip_csr* m, int capNnz, int maxRows, hipStream_t s,
 	// the tiles are dealt one such span per XCD, round-robin, so the 8 XCDs sweep 8 adjacent planes together instead of 8 regions
 	// a gigabyte apart: measured -8 % on the 512^3 Laplacian (3.55 -> 3.28 ms), neutral on smaller grids; with far offsets that are
 	// a large fraction of the matrix (the banded-random benchmark matrix) contiguous eighths are best (tools/sweep_chunk.sh).
-	if (rows > 0 && nTiles > 0) {
-		const double rowsPerTile = static_cast<double>(rows) / nTiles;
-		const long long farTiles = static_cast<long long>(far / rowsPerTile);
-		if (farTiles >= 256 && farTiles * 32 <= nTiles) *chunkTiles = static_cast<int>(farTiles);
-	}
-	if (const char* env = getenv("SMM_HIP_XCD_CHUNK_TILES")) *chunkTiles = std::max(0, atoi(env));  // tuning override
+	*chunkTiles = xcdChunkTiles(rows > 0 && nTiles > 0 ? static_cast<long long>(far / (static_cast<double>(rows) / nTiles)) : 0, nTiles);
 	return SMM_HIP_OK;
 }
 
@@ -853,10 +848,7 @@ int buildRowBlocks(smm_hip_csr* m, int capNnz, int maxRows, hipStream_t s) {
 // the pipelined one is 1-2 % faster (512^3 fp64 3.28 vs 3.33 ms), so it stays.  SMM_HIP_STREAM_VARIANT = 0 / 1 forces the pipelined /
 // the TILE kernel wherever it exists (A/B measurements).
 static bool useTileKernel(int lanes) {
-	static const int forced = [] {
-		const char* env = getenv("SMM_HIP_STREAM_VARIANT");
-		return env ? atoi(env) : -1;
-	}();
+	const int forced = env::intOr(env::STREAM_VARIANT, -1);
 	if (forced == 0) return false;
 	if (forced == 1) return lanes == 1 || lanes == 2 || lanes == 4;
 	return lanes == 2 || lanes == 4;
@@ -869,8 +861,7 @@ static int tileBatch(const smm_hip_csr* m, int lanes) {
 	const double len = m->stream_mid_len > 0 ? m->stream_mid_len : (m->rows > 0 ? static_cast<double>(m->nnz) / m->rows : 1.0);
 	const int p = std::max(1, static_cast<int>(std::ceil(len / lanes)));
 	const int nb = (p + 15) / 16;
-	int g = (p + nb - 1) / nb;
-	if (const char* env = getenv("SMM_HIP_TILE_BATCH")) g = atoi(env);  // tuning override
+	const int g = env::intOr(env::TILE_BATCH, (p + nb - 1) / nb);  // (tuning override)
 	return std::max(4, std::min(16, g));
 }
 
@@ -883,15 +874,14 @@ static int streamCap(const smm_hip_csr* m, int lanes) {
 		const double avg = m->rows > 0 ? static_cast<double>(m->nnz) / m->rows : 1.0;
 		const double len = std::max(avg, static_cast<double>(m->stream_mid_len));
 		int cap = static_cast<int>(len * tileRows(lanes)) + 8;
-		if (const char* env = getenv("SMM_HIP_STREAM_NV")) cap = atoi(env) * TileCfg<T>::PIECE;
+		if (env::isSet(env::STREAM_NV)) cap = env::intOr(env::STREAM_NV, 0) * TileCfg<T>::PIECE;
 		cap = std::max(256, std::min(cap, TileCfg<T>::CAP_MAX));
 		return (cap + 3) & ~3;
 	}
 	const double avg = m->rows > 0 ? static_cast<double>(m->nnz) / m->rows : 1.0;
 	const int rowsPerTile = TPB / std::min(lanes, WAVE);
 	const double want = avg * rowsPerTile * 1.04 + 3;
-	int nv = static_cast<int>((want + StreamCfg<T>::PIECE - 1) / StreamCfg<T>::PIECE);
-	if (const char* env = getenv("SMM_HIP_STREAM_NV")) nv = atoi(env);  // tuning override (tools/spmv_sweep.py)
+	int nv = env::intOr(env::STREAM_NV, static_cast<int>((want + StreamCfg<T>::PIECE - 1) / StreamCfg<T>::PIECE));  // (tuning override: tools/spmv_sweep.py)
 	nv = std::max(1, std::min(nv, StreamCfg<T>::NVMAX));
 	return nv * StreamCfg<T>::PIECE;
 }
@@ -916,31 +906,19 @@ static int lanesForAvg(double avg, int family) {
 // AUTO considers the PATTERN family for matrices of at least 2^25 stored entries (below that an SpMV is a few tens of microseconds and
 // the one-off analysis -- a pass over positions[] -- would not pay for itself within a short solve) whose rows could fit 64 offsets
 static bool autoPatternWanted(const smm_hip_csr* m) {
-	static const int allowed = [] {
-		const char* env = getenv("SMM_HIP_AUTO_PATTERN");
-		return env ? atoi(env) : 1;
-	}();
-	static const long long minNnz = [] {
-		const char* env = getenv("SMM_HIP_AUTO_PATTERN_MIN_NNZ");
-		return env ? atoll(env) : (1LL << 25);
-	}();
-	if (!allowed || m->rows <= 0) return false;
-	return m->nnz >= minNnz && static_cast<double>(m->nnz) / m->rows <= 64.0;
+	if (!env::flagOr(env::AUTO_PATTERN, true) || m->rows <= 0) return false;
+	return m->nnz >= env::longOr(env::AUTO_PATTERN_MIN_NNZ, 1LL << 25) && static_cast<double>(m->nnz) / m->rows <= 64.0;
 }
 
 void chooseSpmvConfig(smm_hip_csr* m) {
 	const double avg = m->rows > 0 ? static_cast<double>(m->nnz) / m->rows : 0.0;
 	int family = SMM_SPMV_STREAM;
-	if (const char* env = getenv("SMM_HIP_SPMV_FAMILY")) {
-		const int f = atoi(env);
-		if (f == SMM_SPMV_VECTOR || f == SMM_SPMV_STREAM) family = f;
-	}
+	const int f = env::intOr(env::SPMV_FAMILY, family);
+	if (f == SMM_SPMV_VECTOR || f == SMM_SPMV_STREAM) family = f;
 	if (m->rows == 0 || m->nnz == 0) family = SMM_SPMV_VECTOR;
 	int lanes = lanesForAvg(avg, family);
-	if (const char* env = getenv("SMM_HIP_SPMV_LANES")) {
-		const int l = atoi(env);
-		if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes = l;
-	}
+	const int l = env::intOr(env::SPMV_LANES, lanes);
+	if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes = l;
 	m->setKernel(family, lanes);
 }
 

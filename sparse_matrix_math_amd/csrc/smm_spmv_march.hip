@@ -990,11 +990,8 @@ static std::atomic<long long> g_marchMinRowsConst{-1}, g_marchMinRowsMasks{-1};
 static long long marchMinRows(bool masksKernel, int dtype) {
 	const long long forced = (masksKernel ? g_marchMinRowsMasks : g_marchMinRowsConst).load(std::memory_order_relaxed);
 	if (forced >= 0) return forced;
-	static const long long env = [] {
-		const char* e = getenv("SMM_HIP_MARCH_MIN_ROWS");
-		return e ? atoll(e) : -1LL;
-	}();
-	if (env >= 0) return env;
+	const long long fromEnv = env::longOr(env::MARCH_MIN_ROWS, -1);
+	if (fromEnv >= 0) return fromEnv;
 	const bool f32 = dtype == SMM_DTYPE_F32;
 	if (masksKernel) return f32 ? 1LL << 24 : 6LL << 20;  // (r05, two sub-steps per tile: profiles/r05/masks_march_thresholds.txt; r04: 2^26 / 12 x 2^20)
 	return 1LL << 21;
@@ -1114,18 +1111,8 @@ struct MarchLaunchState {
 	std::atomic<long long> occ{0};     // (lds << 8) | perCU of the last occupancy query
 	std::mutex mu;
 };
-static int marchEnvInt(const char* name) {
-	const char* env = getenv(name);
-	return env ? atoi(env) : 0;
-}
-static int marchWgsPerCuOverride() {
-	static const int v = std::max(0, marchEnvInt("SMM_HIP_MARCH_WGS_PER_CU"));
-	return v;
-}
-static int marchZcOverride() {
-	static const int v = std::max(0, marchEnvInt("SMM_HIP_MARCH_ZC"));
-	return v;
-}
+static int marchWgsPerCuOverride() { return std::max(0, env::intOr(env::MARCH_WGS_PER_CU, 0)); }
+static int marchZcOverride() { return std::max(0, env::intOr(env::MARCH_ZC, 0)); }
 // false: this launch cannot have its LDS (the caller keeps the kernel that needs none)
 template <typename Kernel>
 static bool marchPrepare(MarchLaunchState& st, Kernel kernel, size_t lds, size_t staticLds, int* perCU) {
@@ -1228,23 +1215,14 @@ static bool launchMarch3(const smm_hip_csr* m, int op, const T* lhs, const T* di
 // (the size at which the direction is formed inside the SpMV: SPMV_HALF_TILES, smm_internal.h).  SMM_HIP_MARCH_FUSE_FULL_TILES=1: full tiles
 // everywhere (A/B measurements)
 bool cgHalfTiles(const smm_hip_csr* m, size_t elemBytes) {
-	static const bool fullTiles = [] {
-		const char* env = getenv("SMM_HIP_MARCH_FUSE_FULL_TILES");
-		return env && atoi(env) != 0;
-	}();
-	static const bool rowsForced = getenv("SMM_HIP_MARCH_R") != nullptr;
-	return !fullTiles && !rowsForced && !m->march_clusters && (spmvOutFlags(m, elemBytes) & SPMV_NT_OUT) != 0;
+	return !env::flagOr(env::MARCH_FUSE_FULL_TILES, false) && !env::isSet(env::MARCH_R) && !m->march_clusters && (spmvOutFlags(m, elemBytes) & SPMV_NT_OUT) != 0;
 }
 
 // true: the launch went to the march kernel.  SMM_HIP_CONST_MARCH=0 keeps the gather kernel (A/B measurements).
 template <typename T>
 bool launchPatConstMarch(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                          const int* doneFlag, hipStream_t s) {
-	static const bool enabled = [] {
-		const char* env = getenv("SMM_HIP_CONST_MARCH");
-		return env ? atoi(env) != 0 : true;
-	}();
-	if (!enabled || !constMarchApplies(m)) return false;
+	if (!constMarchEnabled() || !constMarchApplies(m)) return false;
 	const bool nt = (spmvOutFlags(m, sizeof(T)) & SPMV_NT_OUT) != 0;  // outputs too large to still be cached when the next kernel reads them
 	const bool halfTiles = (op & SPMV_HALF_TILES) != 0 && cgHalfTiles(m, sizeof(T));  // (ConjugateGradient's launches: smm_internal.h)
 	op &= ~SPMV_HALF_TILES;
@@ -1260,10 +1238,7 @@ bool launchPatConstMarch(const smm_hip_csr* m, int op, const T* lhs, const T* di
 	const int nNear = m->pat_k - m->march_lo - m->march_hi;
 	// rows per lane (profiles/r04/march_rows_per_lane.txt, 512^3): fp64 4 -- tiles of 1024 rows, 120 VGPRs, four workgroups per CU: 0.565 ms
 	// against 0.604 with 8 (185 VGPRs, two per CU); fp32 8 -- 0.318 against 0.335.  SMM_HIP_MARCH_R=4 / 8 forces one (A/B measurements).
-	static const int forcedRows = [] {
-		const char* env = getenv("SMM_HIP_MARCH_R");
-		return env ? atoi(env) : 0;
-	}();
+	const int forcedRows = env::intOr(env::MARCH_R, 0);
 	const int rowsPerLane = forcedRows == 4 || forcedRows == 8 ? forcedRows : (sizeof(T) == 8 || halfTiles ? 4 : 8);
 	const int vec = 16 / static_cast<int>(sizeof(T));
 	const bool r4 = rowsPerLane == 4;
@@ -1292,23 +1267,10 @@ bool launchPatConstMarch(const smm_hip_csr* m, int op, const T* lhs, const T* di
 
 static std::atomic<int> g_cgFuseP{1};  // smm_hip_set_cg_fuse_p (tests: A/B against the launch that forms p in cgLazyXP)
 
-static bool marchEnabled() {
-	static const bool enabled = [] {
-		const char* env = getenv("SMM_HIP_CONST_MARCH");
-		return env ? atoi(env) != 0 : true;
-	}();
-	return enabled;
-}
-
 // the form the fused launch exists in: the two-window kernel, default rows per lane, non-temporal outputs (i.e. vectors beyond 64 MB -- the
 // only size at which forming p in the SpMV pays), PATTERN family with constant diagonals at one lane per row
 bool constMarchFusable(const smm_hip_csr* m, size_t elemBytes) {
-	static const bool allowed = [] {
-		const char* env = getenv("SMM_HIP_CG_FUSE_P");
-		return env ? atoi(env) != 0 : true;
-	}();
-	static const bool rowsForced = getenv("SMM_HIP_MARCH_R") != nullptr;
-	return allowed && g_cgFuseP.load(std::memory_order_relaxed) != 0 && !rowsForced && marchEnabled() && m->family() == SMM_SPMV_PATTERN && m->lanes() == 1 && m->pat_state.load(std::memory_order_acquire) > 0 &&
+	return env::flagOr(env::CG_FUSE_P, true) && g_cgFuseP.load(std::memory_order_relaxed) != 0 && !env::isSet(env::MARCH_R) && constMarchEnabled() && m->family() == SMM_SPMV_PATTERN && m->lanes() == 1 && m->pat_state.load(std::memory_order_acquire) > 0 &&
 	       m->pat_encoding == 0 && m->pat_const && !m->pat_const_off && constMarchApplies(m) && !m->march_clusters && (spmvOutFlags(m, elemBytes) & SPMV_NT_OUT) != 0;
 }
 
@@ -1390,14 +1352,10 @@ bool constMarchApplies(const smm_hip_csr* m) {
 template <typename T>
 bool launchPatMasksMarch(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                          const int* doneFlag, hipStream_t s) {
-	static const bool enabled = [] {
-		const char* env = getenv("SMM_HIP_MASKS_MARCH");
-		return env ? atoi(env) != 0 : true;
-	}();
 	// rows of 9 .. 16 entries keep the wave kernel (four value sets of 16 would not fit the registers), and so do matrices of fewer than 8
 	// planes -- in ONE-plane mode (every offset near) a unit is a single step with nothing requested ahead, and the wave kernel wins:
 	// 7 random diagonals within +-1000, 8 M rows, fp64: 0.123 ms against 0.153 (profiles/r04/one_plane_mode.txt)
-	if (!enabled || !masksMarchApplies(m)) return false;
+	if (!masksMarchEnabled() || !masksMarchApplies(m)) return false;
 	const bool nt = (spmvOutFlags(m, sizeof(T)) & SPMV_NT_OUT) != 0;
 	const bool hp2 = 2 * m->march_H / (16 / static_cast<int>(sizeof(T))) <= 2 * TPB;
 #define SMM_MM_GO(KV, QV)                                                                                                   \
@@ -1405,10 +1363,7 @@ bool launchPatMasksMarch(const smm_hip_csr* m, int op, const T* lhs, const T* di
 	 : nt      ? launchMasksMarchK<T, KV, true, 4, QV>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s)      \
 	 : hp2     ? launchMasksMarchK<T, KV, false, 2, QV>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s)     \
 	           : launchMasksMarchK<T, KV, false, 4, QV>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s))
-	static const int forcedQ = [] {
-		const char* env = getenv("SMM_HIP_MASKS_MARCH_Q");  // 2 / 4: force the sub-steps per tile (A/B measurements)
-		return env ? atoi(env) : 0;
-	}();
+	const int forcedQ = env::intOr(env::MASKS_MARCH_Q, 0);  // 2 / 4: force the sub-steps per tile (A/B measurements)
 	const bool q2 = forcedQ == 2 || (forcedQ != 4 && (sizeof(T) == 4 || m->rows < 100000000LL));
 	const bool launched = q2 ? SMM_MM_GO(8, 2) : SMM_MM_GO(8, 4);
 #undef SMM_MM_GO

@@ -1226,13 +1226,7 @@ void preloadPatternUnit() {
 
 // SMM_HIP_AUTO_DICT=0: the automatic attempt (first SpMV of a large matrix) stops at the masks; the dictionary encoding then needs an
 // explicit smm_hip_csr_set_kernel(m, SMM_SPMV_PATTERN, lanes)
-static bool autoDictAllowed() {
-	static const bool on = [] {
-		const char* env = getenv("SMM_HIP_AUTO_DICT");
-		return env ? atoi(env) != 0 : true;
-	}();
-	return on;
-}
+static bool autoDictAllowed() { return env::flagOr(env::AUTO_DICT, true); }
 
 // the mask encoding: SMM_HIP_OK, SMM_HIP_ERR_INVALID (no such pattern: *why says which test failed) or a HIP failure
 static int tryMasks(smm_hip_csr* m, hipStream_t s, const char** why) {
@@ -1262,10 +1256,7 @@ static int tryMasks(smm_hip_csr* m, hipStream_t s, const char** why) {
 	patSortOffsets<<<1, WAVE, 0, s>>>(d_state, d_off, d_meta);
 	const int elemBytes = m->dtype == SMM_DTYPE_F32 ? 4 : 8;
 	// constant diagonals are looked for in matrices of stencil shape only (<= 32 offsets: the kernels check); SMM_HIP_PATTERN_CONST=0 turns the encoding off
-	static const bool constAllowed = [] {
-		const char* env = getenv("SMM_HIP_PATTERN_CONST");
-		return env ? atoi(env) != 0 : true;
-	}();
+	const bool constAllowed = env::flagOr(env::PATTERN_CONST, true);
 	if (constAllowed) {
 		const int sgrid = (samples + TPB - 1) / TPB;
 		patConstSample<<<sgrid, TPB, 0, s>>>(m->rows, samples, d_meta, d_off, m->d_start, m->d_positions, m->d_values, elemBytes, d_cval, d_flag, 0);
@@ -1436,22 +1427,21 @@ void adoptPatternQuietly(const smm_hip_csr* cm, hipStream_t s) {
 // 37.7; profiles/r03/solver_pattern_small.txt).  Same rules as the AUTO step of launchSpmv otherwise: never against a forced kernel,
 // never twice, SMM_HIP_AUTO_PATTERN=0 turns it off; SMM_HIP_SOLVER_PATTERN_MIN_NNZ moves the threshold (default 2^20).
 int adoptPatternForSolver(const smm_hip_csr* m, int plannedIterations, hipStream_t s) {
-	static const int allowed = [] {
-		const char* env = getenv("SMM_HIP_AUTO_PATTERN");
-		return env ? atoi(env) : 1;
-	}();
-	static const long long minNnz = [] {
-		const char* env = getenv("SMM_HIP_SOLVER_PATTERN_MIN_NNZ");
-		return env ? atoll(env) : (1LL << 20);
-	}();
-	if (!allowed || !m || m->rows <= 0 || m->kernelForced || m->family() != SMM_SPMV_STREAM) return SMM_HIP_OK;
+	if (!env::flagOr(env::AUTO_PATTERN, true) || !m || m->rows <= 0 || m->kernelForced || m->family() != SMM_SPMV_STREAM) return SMM_HIP_OK;
 	const int state = m->pat_state.load(std::memory_order_acquire);
 	if (state == -1 || state == -3) return SMM_HIP_OK;
 	if (plannedIterations >= 0 && plannedIterations < 16) return SMM_HIP_OK;  // (a few passes do not pay for a pass over positions[])
 	const double avg = static_cast<double>(m->nnz) / m->rows;
-	if (m->nnz < minNnz || avg > 64.0) return SMM_HIP_OK;
+	if (m->nnz < env::longOr(env::SOLVER_PATTERN_MIN_NNZ, 1LL << 20) || avg > 64.0) return SMM_HIP_OK;
 	adoptPatternQuietly(m, s);
 	return SMM_HIP_OK;  // "no pattern" / "no memory for the analysis" are not failures of the solve
+}
+
+// workgroups per CU of the wave-private form (0 = off: the tile kernels serve those matrices); measured best on the 512^3 Laplacian: 4 for
+// fp64 (2.29 ms against 2.38 at 8 and 2.99 for the tile kernel), 8 for fp32 (1.40 against 1.55 at 4 and 1.50).  SMM_HIP_PATTERN_WAVE overrides.
+static int patWaveWgs(size_t elemBytes) {
+	const int forced = env::intOr(env::PATTERN_WAVE, -1);
+	return forced >= 0 ? forced : (elemBytes == 8 ? 4 : 8);
 }
 
 template <typename T>
@@ -1465,33 +1455,19 @@ static int patCap(const smm_hip_csr* m, int lanes) {
 }
 
 // SMM_HIP_PATTERN_VARIANT=0 keeps the pipelined row-per-lane kernel for every L (A/B measurements)
-static bool patUseTile(int lanes) {
-	static const int forced = [] {
-		const char* env = getenv("SMM_HIP_PATTERN_VARIANT");
-		return env ? atoi(env) : -1;
-	}();
-	if (forced == 0) return false;
-	return lanes == 2 || lanes == 4;
-}
+static bool patUseTile(int lanes) { return env::intOr(env::PATTERN_VARIANT, -1) != 0 && (lanes == 2 || lanes == 4); }
 
 // gathers per batch: a piece of p entries is walked in ceil(p / 16) batches of equal size (26 -> 2 x 13), in the three compiled sizes
 static int patBatch(const smm_hip_csr* m, int lanes) {
 	const double len = m->stream_mid_len > 0 ? m->stream_mid_len : (m->rows > 0 ? static_cast<double>(m->nnz) / m->rows : 1.0);
 	const int p = std::max(1, static_cast<int>(std::ceil(len / lanes)));
 	const int nb = (p + 15) / 16;
-	int g = (p + nb - 1) / nb;
-	if (const char* env = getenv("SMM_HIP_TILE_BATCH")) g = atoi(env);
+	const int g = env::intOr(env::TILE_BATCH, (p + nb - 1) / nb);
 	return g <= 8 ? 8 : g <= 13 ? 13 : 16;
 }
 
 // SMM_HIP_FULL_ROWS=0: the tile kernel's general path for every row (A/B measurements of the fast path for wavefronts of uniform rows).  Read once.
-static int noFullRowsFlag() {
-	static const int flag = [] {
-		const char* env = getenv("SMM_HIP_FULL_ROWS");
-		return env && atoi(env) == 0 ? SPMV_NO_FULL_ROWS : 0;
-	}();
-	return flag;
-}
+static int noFullRowsFlag() { return env::flagOr(env::FULL_ROWS, true) ? 0 : SPMV_NO_FULL_ROWS; }
 
 template <typename T, int L, int G>
 static void launchPatTileG(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
@@ -1530,17 +1506,9 @@ static void launchPatConst(const smm_hip_csr* m, int op, const T* lhs, const T* 
 	const int cus = (op & SPMV_LEAVE_ROOM) ? std::max(8, numCUs() - 8) : numCUs();  // room for the RCCL kernel beside A_loc (smm_dist.hip)
 	op &= ~SPMV_LEAVE_ROOM;
 	const int nTiles = (m->rows + TPB - 1) / TPB;
-	static const int perCU = [] {
-		const char* env = getenv("SMM_HIP_CONST_WGS_PER_CU");
-		return env ? std::max(1, atoi(env)) : 8;
-	}();
+	const int perCU = std::max(1, env::intOr(env::CONST_WGS_PER_CU, 8));
 	const int grid = std::max(1, std::min(std::min(nTiles, cus * perCU), NPART));
-	// the tiles' deal to the XCDs: one span of the farthest diagonal (a grid plane) per XCD in turn when that is many tiles but a small
-	// part of the matrix -- the rule of buildRowBlocks (smm_spmv.hip) -- else one contiguous eighth each
-	int chunkTiles = 0;
-	const long long farTiles = m->pat_max_off / TPB;
-	if (farTiles >= 256 && farTiles * 32 <= nTiles) chunkTiles = static_cast<int>(farTiles);
-	if (const char* env = getenv("SMM_HIP_XCD_CHUNK_TILES")) chunkTiles = std::max(0, atoi(env));
+	const int chunkTiles = xcdChunkTiles(m->pat_max_off / TPB, nTiles);  // (a span of the farthest diagonal -- a grid plane -- per XCD in turn)
 	spmvPatternConstKernel<T><<<grid, TPB, 0, s>>>(m->rows, m->cols, m->pat_k, m->d_pat_off, m->d_pat_cval, m->d_pat_masks, chunkTiles, op | spmvOutFlags(m, sizeof(T)),
 	                                              lhs, divisor, x, out, dotMode, w1, partials, doneFlag);
 }
@@ -1580,23 +1548,14 @@ static void launchPat(const smm_hip_csr* m, int op, const T* lhs, const T* divis
 		}
 	}
 	if constexpr (L == 1) {
-		// workgroups per CU of the wave-private form (0 = off: the tile kernel below); measured best on the 512^3 Laplacian: 4 for fp64
-		// (2.29 ms against 2.38 at 8 and 2.99 for the tile kernel), 8 for fp32 (1.40 against 1.55 at 4 and 1.50)
-		static const int waveEnv = [] {
-			const char* env = getenv("SMM_HIP_PATTERN_WAVE");
-			return env ? atoi(env) : -1;
-		}();
-		const int waveForm = waveEnv >= 0 ? waveEnv : (sizeof(T) == 8 ? 4 : 8);
+		const int waveForm = patWaveWgs(sizeof(T));
 		// big grid-shaped matrices (masksMarchApplies): the march form (x through LDS windows and registers, smm_spmv_march.hip)
 		if (m->pat_encoding == 0 && launchPatMasksMarch<T>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s)) return;
 		if (waveForm && m->pat_encoding == 0 && m->pat_k <= 16) {
 			const int cus = (op & SPMV_LEAVE_ROOM) ? std::max(8, numCUs() - 8) : numCUs();
 			const int nTiles = (m->rows + TPB - 1) / TPB;
 			const int grid = std::max(1, std::min(std::min(nTiles, cus * waveForm), NPART));
-			int chunkTiles = 0;
-			const long long farTiles = m->pat_max_off / TPB;
-			if (farTiles >= 256 && farTiles * 32 <= nTiles) chunkTiles = static_cast<int>(farTiles);
-			if (const char* env = getenv("SMM_HIP_XCD_CHUNK_TILES")) chunkTiles = std::max(0, atoi(env));
+			const int chunkTiles = xcdChunkTiles(m->pat_max_off / TPB, nTiles);
 			const int flags = (op & ~SPMV_LEAVE_ROOM) | spmvOutFlags(m, sizeof(T));
 			if (m->pat_k <= 8) {
 				spmvPatternWaveKernel<T, 8><<<grid, TPB, 0, s>>>(m->rows, m->cols, m->pat_k, m->d_pat_off, m->d_start, static_cast<const T*>(m->d_values), m->d_pat_masks, chunkTiles,
@@ -1643,11 +1602,7 @@ const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes)
 		return "spmvDictKernel";
 	}
 	if (L == 1 && m->pat_const && !m->pat_const_off) {
-		static const bool marchOn = [] {
-			const char* env = getenv("SMM_HIP_CONST_MARCH");
-			return env ? atoi(env) != 0 : true;
-		}();
-		const bool march = marchOn && constMarchApplies(m);
+		const bool march = constMarchEnabled() && constMarchApplies(m);
 		// the row's mask (32 bits in the 2.5-D forms, 8 where the two-window kernel knows its five near offsets at compile time), x, out:
 		// neither values[] nor start[]
 		const bool bytesMasks = march && !m->march_clusters && m->d_pat_masks8 && m->pat_k - m->march_lo - m->march_hi == 5;
@@ -1655,23 +1610,11 @@ const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes)
 		return march ? (m->march_clusters ? "spmvPatternConstMarch3Kernel" : "spmvPatternConstMarchKernel") : "spmvPatternConstKernel";
 	}
 	*bytes = nnz * s + rows * 8 + startBytes + vectors;
-	if (L == 1 && masksMarchApplies(m)) {
-		static const bool masksMarchOn = [] {
-			const char* env = getenv("SMM_HIP_MASKS_MARCH");
-			return env ? atoi(env) != 0 : true;
-		}();
-		if (masksMarchOn) {
-			*bytes = nnz * s + rows + (rows / 64 + 1) * 4 + vectors;  // values, one byte of mask per row, one start[] per 64 rows, x, out
-			return "spmvPatternMasksMarchKernel";
-		}
+	if (L == 1 && masksMarchEnabled() && masksMarchApplies(m)) {
+		*bytes = nnz * s + rows + (rows / 64 + 1) * 4 + vectors;  // values, one byte of mask per row, one start[] per 64 rows, x, out
+		return "spmvPatternMasksMarchKernel";
 	}
-	if (L == 1) {
-		static const int waveEnv = [] {
-			const char* env = getenv("SMM_HIP_PATTERN_WAVE");
-			return env ? atoi(env) : -1;
-		}();
-		if (waveEnv != 0 && m->pat_k <= 16) return "spmvPatternWaveKernel";
-	}
+	if (L == 1 && patWaveWgs(s) != 0 && m->pat_k <= 16) return "spmvPatternWaveKernel";
 	if ((L == 2 || L == 4) && patUseTile(L)) {
 		if (patternSlotsChosen(m, L)) {  // (smm_spmv_slots.hip: the copy was built by an earlier launch)
 			*bytes = patternSlotsBytes(m);  // (the sweep kernel reads the same copy: the same bytes)
@@ -1686,11 +1629,7 @@ const char* patternKernelDesc(const smm_hip_csr* m, int lanes, long long* bytes)
 static bool patNeedsTiles(const smm_hip_csr* m, int L) {
 	if (L != 1 || m->pat_encoding != 0) return true;
 	if (m->pat_const && !m->pat_const_off) return false;  // the constant-diagonal kernels
-	static const int waveEnv = [] {
-		const char* env = getenv("SMM_HIP_PATTERN_WAVE");
-		return env ? atoi(env) : -1;
-	}();
-	return !(waveEnv != 0 && m->pat_k <= 16);  // the wave kernel and the masks march walk rows
+	return !(patWaveWgs(m->dtype == SMM_DTYPE_F32 ? 4 : 8) != 0 && m->pat_k <= 16);  // the wave kernel and the masks march walk rows
 }
 
 // tiles for this family are cut for its own LDS capacity (values only): kept beside the STREAM family's table

@@ -159,11 +159,9 @@ __global__ __launch_bounds__(TPB) void spmvPatternSlotsKernel(int rows, int nWav
 // waves); =3: the same, walked by the sweep kernel (smm_spmv_sweep.hip); unset: AUTO.  A handle's own smm_hip_csr_pattern_slots mode wins
 // over the variable.
 static int slotsEnvMode() {
-	static const int mode = [] {
-		const char* env = getenv("SMM_HIP_PATTERN_SLOTS");
-		return env ? (atoi(env) == 3 ? 3 : atoi(env) != 0 ? 1 : 0) : -1;
-	}();
-	return mode;
+	if (!env::isSet(env::PATTERN_SLOTS)) return -1;
+	const int mode = env::intOr(env::PATTERN_SLOTS, 0);
+	return mode == 3 ? 3 : mode != 0 ? 1 : 0;
 }
 
 static int slotsMode(const smm_hip_csr* m) { return m->pat_slots_mode >= 0 ? m->pat_slots_mode : slotsEnvMode(); }
@@ -172,12 +170,7 @@ static int slotsMode(const smm_hip_csr* m) { return m->pat_slots_mode >= 0 ? m->
 static bool slotsApplies(const smm_hip_csr* m, int lanes) {
 	if (lanes != 2 && lanes != 4) return false;
 	if (m->pat_encoding != 0 || (m->pat_const && !m->pat_const_off)) return false;
-	static const bool fullRows = [] {
-		const char* env = getenv("SMM_HIP_FULL_ROWS");
-		const char* variant = getenv("SMM_HIP_PATTERN_VARIANT");
-		return !(env && atoi(env) == 0) && !(variant && atoi(variant) == 0);
-	}();
-	return fullRows;
+	return env::flagOr(env::FULL_ROWS, true) && env::intOr(env::PATTERN_VARIANT, -1) != 0;
 }
 
 // AUTO: only where the family was adopted by the library itself, and only with >= 99 % uniform waves
@@ -204,12 +197,8 @@ static std::atomic<int> g_sweepRows{0};
 
 static int sweepRowsOpen() {
 	if (const int forced = g_sweepRows.load(std::memory_order_relaxed)) return forced;
-	static const int env = [] {
-		const char* e = getenv("SMM_HIP_PATTERN_SWEEP_ROWS");
-		const int r = e ? atoi(e) : 0;
-		return r == 8 || r == 16 || r == 32 ? r : 0;
-	}();
-	return env ? env : SWEEP_ROWS_DEFAULT;
+	const int r = env::intOr(env::PATTERN_SWEEP_ROWS, 0);
+	return r == 8 || r == 16 || r == 32 ? r : SWEEP_ROWS_DEFAULT;
 }
 
 // x lines fetched per line of x, from the sorted offsets: a row-major front re-fetches a line at every gap between two

@@ -196,13 +196,7 @@ __global__ __launch_bounds__(TPB) void spmvPatternSweepKernel(int rows, int nWav
 // workgroups per CU: as many as fit, up to three (r09: one wave per SIMD does not hide the latency of its own loads -- 611 us per launch
 // on the benchmark matrix at R = 16, 445 with two, 430 with three); the block of rows an XCD holds open is 32 CUs x that x 4 waves x R x 64
 // rows.  SMM_HIP_PATTERN_SWEEP_WGS=1..8 for lab runs.
-static int sweepWgsPerCU() {
-	static const int n = [] {
-		const char* env = getenv("SMM_HIP_PATTERN_SWEEP_WGS");
-		return env ? std::max(1, std::min(8, atoi(env))) : 3;
-	}();
-	return n;
-}
+static int sweepWgsPerCU() { return std::max(1, std::min(8, env::intOr(env::PATTERN_SWEEP_WGS, 3))); }
 
 // workgroups per CU the launch of one variant really gets: the knob, or fewer where the variant's registers allow fewer
 template <typename T, int L, int R>
