@@ -425,6 +425,10 @@ int smm_hip_axpy_dev_f64(int n, double a, const double* d_x, const double* d_y, 
  *   SUCCESS unless iterations > maxIterations (ref:2277-2282); M == NULL is the IDPreconditioner overload.
  * Additive outputs (may be NULL; the reference API has no equivalent): iterations = loop passes executed,
  * resnorm = last ||r||^2 (cg) or ||r|| (bicgstab) the loop computed.
+ * The zero start: smm_hip_cg_*, smm_hip_bicgstab_* and smm_hip_cgs_* read x0 once before their set-up; from an x0 of zeros (-0.0
+ * counts, a NaN does not) on a matrix whose values are all finite, r = b - A x0 is b bit for bit and no SpMV is launched for it.  The
+ * values are looked through once per version (every edit call above and smm_hip_csr_values_changed_* start a new one).  Same results;
+ * SMM_HIP_ZERO_START=0 in the environment (read at every call) launches the SpMV regardless.
  */
 int smm_hip_cg_f32(const smm_hip_csr* a, const float* b, const float* x0, float* x, int maxIterations, float eps,
                    const smm_hip_precond* M, int* solver_status, int* iterations, float* resnorm2);

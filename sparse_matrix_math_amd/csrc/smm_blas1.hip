@@ -59,6 +59,33 @@ __global__ __launch_bounds__(TPB) void copy2Kernel(int n, const T* src, T* d1, T
 	}
 }
 
+// src copied to D destinations in one pass over src: the set-up of a Krylov loop that starts from x0 = 0, where r = b and the loop's other
+// first vectors are copies of r
+template <typename T, int D>
+struct CopyDst {
+	T* d[D];
+};
+template <typename T, int D>
+__global__ __launch_bounds__(TPB) void copyManyKernel(int n, const T* src, CopyDst<T, D> dst) {
+	const T* const in[1] = {src};
+	streamMap<T, false, 1, D>(n, in, dst.d, [](const T(&v)[1], T(&r)[D]) {
+#pragma unroll
+		for (int k = 0; k < D; ++k) r[k] = v[0];
+	});
+}
+
+// The two tests behind the zero start of the Krylov drivers (zeroStart, smm_solver_host.h).  *flag was preset to 1; every lane that finds
+// an element of the other kind stores 0 there -- a plain vector store: all writers store the same value, so there is nothing to order.
+// FINITE false: an element that compares != 0 (-0.0 is zero; a NaN compares unequal, so a NaN start is not a zero start);
+// FINITE true: an Inf or a NaN.
+template <typename T, bool NT, bool FINITE>
+__global__ __launch_bounds__(TPB) void scanFlagKernel(long long n, const T* v, int* flag) {
+	bool found = false;
+	const T* const in[1] = {v};
+	streamMap<T, NT, 1, 0>(n, in, nullptr, [&](const T(&e)[1], T(&)[1]) { found |= FINITE ? !(e[0] - e[0] == T(0)) : e[0] != T(0); });
+	if (found) *flag = 0;
+}
+
 static int gridFor(long long n) { return static_cast<int>(std::max<long long>(1, std::min<long long>((n + TPB - 1) / TPB, numCUs() * 8LL))); }
 
 template <typename T>
@@ -96,11 +123,37 @@ int launchCopy2(int n, const T* src, T* dst1, T* dst2, hipStream_t s) {
 	return SMM_HIP_OK;
 }
 
+template <typename T>
+int launchCopyMany(int n, const T* src, T* d1, T* d2, T* d3, T* d4, hipStream_t s) {
+	if (n <= 0) return SMM_HIP_OK;
+	if (d4) copyManyKernel<T, 4><<<gridFor(n), TPB, 0, s>>>(n, src, CopyDst<T, 4>{{d1, d2, d3, d4}});
+	else if (d3) copyManyKernel<T, 3><<<gridFor(n), TPB, 0, s>>>(n, src, CopyDst<T, 3>{{d1, d2, d3}});
+	else return launchCopy2<T>(n, src, d1, d2, s);
+	SMM_HIP_TRY(hipGetLastError());
+	return SMM_HIP_OK;
+}
+
+template <typename T>
+int launchScanFlag(long long n, const T* v, bool finite, int* d_flag, hipStream_t s) {
+	SMM_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_flag), 1, 1, s));
+	if (n <= 0) return SMM_HIP_OK;
+	const int g = gridFor(n);
+	const bool nt = static_cast<double>(n) * sizeof(T) > 192.0 * 1024 * 1024;  // (as launchDotPartials: streamed from HBM anyway)
+	if (finite && nt) scanFlagKernel<T, true, true><<<g, TPB, 0, s>>>(n, v, d_flag);
+	else if (finite) scanFlagKernel<T, false, true><<<g, TPB, 0, s>>>(n, v, d_flag);
+	else if (nt) scanFlagKernel<T, true, false><<<g, TPB, 0, s>>>(n, v, d_flag);
+	else scanFlagKernel<T, false, false><<<g, TPB, 0, s>>>(n, v, d_flag);
+	SMM_HIP_TRY(hipGetLastError());
+	return SMM_HIP_OK;
+}
+
 #define SMM_INSTANTIATE(T)                                                                     \
 	template int launchDotPartials<T>(int, const T*, const T*, T*, const int*, hipStream_t);   \
 	template int launchSumPartials<T>(const T*, T*, hipStream_t);                              \
 	template int launchAxpy<T>(int, T, const T*, const T*, T*, hipStream_t);                   \
-	template int launchCopy2<T>(int, const T*, T*, T*, hipStream_t);
+	template int launchCopy2<T>(int, const T*, T*, T*, hipStream_t);                           \
+	template int launchCopyMany<T>(int, const T*, T*, T*, T*, T*, hipStream_t);                \
+	template int launchScanFlag<T>(long long, const T*, bool, int*, hipStream_t);
 SMM_INSTANTIATE(float)
 SMM_INSTANTIATE(double)
 #undef SMM_INSTANTIATE

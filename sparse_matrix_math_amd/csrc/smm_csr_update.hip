@@ -9,6 +9,7 @@
 //     is no longer constant.  A handle that was not constant is never promoted (same bits either way: a question of speed only);
 //   * the single-launch BiCGStab's slot-major copy of the values (d_res_ell) and the PATTERN slots kernel's wave-sliced copy
 //     (d_pat_slots, smm_spmv_slots.hip) are rewritten in place.
+//   * what the handle knows about the finiteness of its values (values_finite, the zero start of the Krylov drivers) is forgotten.
 // Preconditioners: SGS reads A's values at every apply; ILU0 / IC0 / JACOBI / BLOCK_* hold factors computed at create (snapshots).
 #include <algorithm>
 #include <cstring>
@@ -302,6 +303,7 @@ bool isConstForm(const smm_hip_csr* m) {
 // the value-dependent state after values[] changed on `s` (see the top of the file)
 template <typename T>
 int valuesEdited(smm_hip_csr* m, hipStream_t s, int edit, T alpha, const smm_hip_csr* other) {
+	m->values_finite.store(-1, std::memory_order_release);  // (every edit, whatever the family: the zero start of the solvers asks again)
 	if (m->pat_state.load(std::memory_order_acquire) != 1 || m->pat_encoding != 0) return SMM_HIP_OK;
 	std::lock_guard<std::mutex> lock(m->tileMutex);
 	if (isConstForm(m)) {

@@ -80,7 +80,8 @@ enum Effect { SPEED, ARITH, TRANSPORT, DIAG, LAB };
 	X(TILE_BATCH, "SMM_HIP_TILE_BATCH", EACH, ARITH, "gathers per batch of the TILE kernels (STREAM: 4 .. 16; PATTERN: 8, 13 or 16)") \
 	X(TRACE_SETUP, "SMM_HIP_TRACE_SETUP", ONCE, DIAG, "1: the host-side stages of one-off set-up work print their wall time on stderr") \
 	X(UPDATE_NT, "SMM_HIP_UPDATE_NT", ONCE, SPEED, "0 / 1: never / always use non-temporal loads and stores in the solvers' update kernels") \
-	X(XCD_CHUNK_TILES, "SMM_HIP_XCD_CHUNK_TILES", EACH, ARITH, "tiles dealt to one XCD in turn (0: one contiguous eighth each)")
+	X(XCD_CHUNK_TILES, "SMM_HIP_XCD_CHUNK_TILES", EACH, ARITH, "tiles dealt to one XCD in turn (0: one contiguous eighth each)") \
+	X(ZERO_START, "SMM_HIP_ZERO_START", EACH, SPEED, "0: BiCGStab, ConjugateGradient and ConjugateGradientSquared launch the set-up SpMV r = b - A x0 also from an all-zero x0")
 
 enum Id {
 #define SMM_ENV_ID(id, name, policy, effect, what) id,

@@ -214,6 +214,9 @@ struct smm_hip_csr {
 	// uid of the handle it was built from (0: not a transpose); smm_hip_csr_transpose_refresh_* gathers through d_tperm
 	int* d_tperm = nullptr;
 	unsigned long long transposeOf = 0;
+	// whether values[] holds finite numbers only: -1 not known, 1 yes, 0 an Inf or a NaN.  Found by one pass over values[] the first time a
+	// Krylov driver starts from x0 = 0 (zeroStart, smm_solver_host.h); back to -1 at every value edit (valuesEdited, smm_csr_update.hip)
+	mutable std::atomic<int> values_finite{-1};
 };
 
 struct smm_hip_precond {
@@ -465,6 +468,12 @@ template <typename T>
 int launchAxpy(int n, T a, const T* x, const T* y, T* out, hipStream_t s);
 template <typename T>
 int launchCopy2(int n, const T* src, T* dst1, T* dst2, hipStream_t s);
+// up to four copies of src in one pass over it (dst3, dst4 may be null; dst2 as in launchCopy2)
+template <typename T>
+int launchCopyMany(int n, const T* src, T* dst1, T* dst2, T* dst3, T* dst4, hipStream_t s);
+// *d_flag = 1, then 0 if v[0 .. n) holds an element that compares != 0 (finite false: -0.0 is zero, a NaN is not) or an Inf / NaN (finite true)
+template <typename T>
+int launchScanFlag(long long n, const T* v, bool finite, int* d_flag, hipStream_t s);
 
 // Polls the device `done` flag without stalling the queue: every `interval` iterations the flag is copied into a
 // pinned mailbox behind an event; the host reads mailboxes whose event has completed and waits only when more

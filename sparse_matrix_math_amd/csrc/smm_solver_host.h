@@ -56,6 +56,14 @@ struct LoopWatch {
 		every = fixedInterval;
 		return poller->init(s);
 	}
+	// one device word on the host, through the poller's pinned mailbox; synchronises the stream.  Between begin() and the first leave().
+	int fetch(const int* word, int* seen) {
+		SMM_HIP_TRY(hipMemcpyAsync(&poller->mailbox[0], word, sizeof(int), hipMemcpyDeviceToHost, poller->s));
+		SMM_HIP_TRY(hipStreamSynchronize(poller->s));
+		*seen = poller->mailbox[0];
+		poller->mailbox[0] = 0;
+		return SMM_HIP_OK;
+	}
 	// true: enqueue no iteration i -- the loop was seen done, or the look failed (rc)
 	bool leave(int i) {
 		if (i != next) return false;
@@ -65,6 +73,33 @@ struct LoopWatch {
 		return seen != 0;
 	}
 };
+
+// The zero start.  A driver's set-up residual r = b - A x0 from an x0 of zeros is b, bit for bit, when every stored value is finite: each
+// product is v * (+-0) = +-0, a row's sum starts at +0 and +0 + (-0) = +0 under round-to-nearest, so it -- and the sum of its pieces --
+// stays +0, and b[i] - (+0) = b[i], b[i] = -0 included.  (An Inf or a NaN among the values must still reach r: 0 * Inf = NaN.)  *skip:
+// the host knows both, so the driver launches no SpMV for the set-up and copies b instead.  x0 is read once (n elements); values[] is read
+// once per version of the values (smm_hip_csr::values_finite), the first time a start is found to be zero.  Each look is one word through
+// the watch's mailbox and a stream synchronise, before the set-up is enqueued.  SMM_HIP_ZERO_START=0: never (the SpMV runs).
+template <typename T>
+int zeroStart(const smm_hip_csr* a, const T* x0, LoopWatch& watch, hipStream_t s, bool* skip) {
+	*skip = false;
+	if (a->rows <= 0 || !env::flagOr(env::ZERO_START, true)) return SMM_HIP_OK;
+	int finite = a->values_finite.load(std::memory_order_acquire);
+	if (finite == 0) return SMM_HIP_OK;
+	DevBuf<int> word;
+	SMM_TRY(word.alloc(1));
+	int zero = 0;
+	SMM_TRY(launchScanFlag<T>(a->rows, x0, false, word, s));
+	SMM_TRY(watch.fetch(word, &zero));
+	if (!zero) return SMM_HIP_OK;
+	if (finite < 0) {
+		SMM_TRY(launchScanFlag<T>(a->nnz, static_cast<const T*>(a->d_values), true, word, s));
+		SMM_TRY(watch.fetch(word, &finite));
+		a->values_finite.store(finite ? 1 : 0, std::memory_order_release);
+	}
+	*skip = finite != 0;
+	return SMM_HIP_OK;
+}
 
 // The end of every loop: the watch's or a launch's error, else `bytes` of the loop's device scalars on the host; synchronises `s`.
 inline int loopFinish(const LoopWatch& watch, void* h, const void* d, size_t bytes, hipStream_t s) {

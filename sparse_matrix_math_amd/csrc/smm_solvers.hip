@@ -530,22 +530,26 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
 	SMM_TRY(sc.alloc(1));
 	const int g = solverGrid(n);
 
-	SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x0, r, 0, nullptr, nullptr, nullptr, s));  // r = b - A x0, ref:2337
+	const int* doneFlag = &sc.p->done;
+	LoopWatch watch;
+	SMM_TRY(watch.begin(s, doneFlag, 0));
+	bool fromZero = false;  // x0 = 0 and finite values: r = b without an SpMV (zeroStart, smm_solver_host.h)
+	SMM_TRY(zeroStart<T>(a, x0, watch, s, &fromZero));
+	if (!fromZero) SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x0, r, 0, nullptr, nullptr, nullptr, s));  // r = b - A x0, ref:2337
 	if (pcg) {
+		if (fromZero) SMM_TRY(launchCopy2<T>(n, b, r, nullptr, s));
 		SMM_TRY(precondApplyDev<T>(M, r, z, nullptr, s));           // z = M^-1 r, ref:2441
 		SMM_TRY(launchCopy2<T>(n, z, p, nullptr, s));               // p = z, ref:2447
 		SMM_TRY(launchDotPartials<T>(n, r, r, parts, nullptr, s));  // ||r||^2
 		SMM_TRY(launchDotPartials<T>(n, r, z, parts2, nullptr, s)); // r.z
 	} else {
-		SMM_TRY(launchCopy2<T>(n, r, p, nullptr, s));               // p = r, ref:2340
+		if (fromZero) SMM_TRY(launchCopy2<T>(n, b, r, p, s));       // r = p = b in one pass over b
+		else SMM_TRY(launchCopy2<T>(n, r, p, nullptr, s));          // p = r, ref:2340
 		SMM_TRY(launchDotPartials<T>(n, r, r, parts, nullptr, s));  // ref:2341
 	}
 	cgInitScal<T><<<1, TPB, 0, s>>>(parts, sc, eps, pcg, parts2);
 	if (maxIterations == -1) maxIterations = n;  // ref:2345-2347 (no clamp otherwise)
 
-	const int* doneFlag = &sc.p->done;
-	LoopWatch watch;
-	SMM_TRY(watch.begin(s, doneFlag, 0));
 	for (int i = 0; i < maxIterations && !watch.leave(i); ++i) {
 		if (lazy && fuseP) {
 			// the direction is formed INSIDE the SpMV (2.5-D constant-diagonal kernel): SpMV' (bookkeeping of iteration i - 1, p_i, A p_i, p.Ap),
@@ -672,20 +676,24 @@ static int bicgstabLoop(const smm_hip_csr* a, const T* b, T* x, int maxIteration
 	// block preconditioner of THIS matrix: A p and A s are formed inside the apply's launch, row by row in the order of the stored entries
 	const bool fuseBlk = blockM && blockM->a == a && blockFuseSpmv(blockM, false);
 
-	if (precondition) {
-		SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, scratch, 0, nullptr, nullptr, nullptr, s));  // ref:2215
-		SMM_TRY(apply(scratch, r, nullptr, s));                                                  // ref:2217-2224
-	} else {
-		SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, r, 0, nullptr, nullptr, nullptr, s));
-	}
-	SMM_TRY(launchCopy2<T>(n, r, r0, p, s));                     // ref:2225-2226
-	SMM_TRY(launchDotPartials<T>(n, r, r0, parts, nullptr, s));  // ref:2231
-	rr0InitScal<T><<<1, TPB, 0, s>>>(parts, sc);  // (smm_solver_scal.h)
-
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);  // do { } while: the body always runs once (ref:2232, 2277)
 	LoopWatch watch;
 	SMM_TRY(watch.begin(s, doneFlag, 1));
+	bool fromZero = false;  // x = 0 and finite values: b - A x is b, no SpMV is launched for it (zeroStart, smm_solver_host.h)
+	SMM_TRY(zeroStart<T>(a, x, watch, s, &fromZero));
+	if (precondition) {
+		if (fromZero) SMM_TRY(launchCopy2<T>(n, b, scratch, nullptr, s));
+		else SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, scratch, 0, nullptr, nullptr, nullptr, s));  // ref:2215
+		SMM_TRY(apply(scratch, r, nullptr, s));                                                       // ref:2217-2224
+	} else if (!fromZero) {
+		SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, r, 0, nullptr, nullptr, nullptr, s));
+	}
+	if (fromZero && !precondition) SMM_TRY(launchCopyMany<T>(n, b, r, r0, p, nullptr, s));  // r = r0 = p = b in one pass over b
+	else SMM_TRY(launchCopy2<T>(n, r, r0, p, s));                                           // ref:2225-2226
+	SMM_TRY(launchDotPartials<T>(n, r, r0, parts, nullptr, s));  // ref:2231
+	rr0InitScal<T><<<1, TPB, 0, s>>>(parts, sc);  // (smm_solver_scal.h)
+
 	for (int i = 0; i < planned; ++i) {
 		if (Applier::hostSide && i > 0) {
 			// a host functor drains the stream at every apply anyway: test the flag directly so that it is never called for an

@@ -100,15 +100,21 @@ static int cgsDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T e
 	SMM_TRY(parts2.alloc(2 * NPART));  // [r.r | r.r0]
 	SMM_TRY(sc.alloc(1));
 
-	SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, r, 0, nullptr, nullptr, nullptr, s));  // ref:2118
-	if (n > 0) cgsCopy3<T><<<solverGrid(n), TPB, 0, s>>>(n, r, p, u, r0);               // ref:2124-2126
-	SMM_TRY(launchDotPartials<T>(n, r, r0, parts, nullptr, s));                       // ref:2128
-	rr0InitScal<T><<<1, TPB, 0, s>>>(parts, sc);                                       // ref:2128 (smm_solver_scal.h)
-
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);  // do { } while: the body always runs once (ref:2131, 2172)
 	LoopWatch watch;
 	SMM_TRY(watch.begin(s, doneFlag, 1));
+	bool fromZero = false;  // x = 0 and finite values: r = b without an SpMV (zeroStart, smm_solver_host.h)
+	SMM_TRY(zeroStart<T>(a, x, watch, s, &fromZero));
+	if (fromZero) {
+		SMM_TRY(launchCopyMany<T>(n, b, r, p, u, r0, s));  // r = p = u = r0 = b in one pass over b
+	} else {
+		SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, r, 0, nullptr, nullptr, nullptr, s));  // ref:2118
+		if (n > 0) cgsCopy3<T><<<solverGrid(n), TPB, 0, s>>>(n, r, p, u, r0);               // ref:2124-2126
+	}
+	SMM_TRY(launchDotPartials<T>(n, r, r0, parts, nullptr, s));                       // ref:2128
+	rr0InitScal<T><<<1, TPB, 0, s>>>(parts, sc);                                       // ref:2128 (smm_solver_scal.h)
+
 	for (int i = 0; i < planned && !watch.leave(i); ++i) {
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, r0, parts, doneFlag, s));  // ref:2132-2133
 		SMM_LAUNCH_UPDATE(cgsFusedQX, updateNT(n, sizeof(T), 6), solverGrid(n), s, n, sc, i & 1, parts, ap, u, x, q, alphaUQ);
