@@ -77,6 +77,18 @@ extern "C" {
  * once, one launch per apply -- no dependency chain across the chip (csrc/smm_precond_block.hip). */
 #define SMM_PRECOND_BLOCK_ILU0 5
 #define SMM_PRECOND_BLOCK_SGS 6
+/* Chebyshev polynomial in D^-1 A, D the stored diagonal taken with its sign (an addition; csrc/smm_precond_cheb.hip, the definition line
+ * by line is tests/chebyshev_restatement.py).  With bounds 0 < lambda_min < lambda_max on the spectrum of D^-1 A and a degree d >= 0:
+ *   theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta, rho_0 = 1 / sigma
+ *   rho_k = 1 / (2 sigma - rho_{k-1}), c1_k = rho_k rho_{k-1}, c2_k = 2 rho_k / delta      (double, on the host, each cast to T once)
+ *   z = M^-1 r:  d = (r / diag) * T(1 / theta);  z = d                                              (degree 0: a scaled Jacobi)
+ *                k = 1 .. d:  q = r - A z;  t = q / diag;  u = c2_k * t;  d = _smm_fma(c1_k, d, u);  z = z + d
+ * q = r - A z is the library's SpMV in whatever kernel family the matrix runs; every element-wise operation rounds once in T.  I - M^-1 A
+ * has the eigenvalues T_{d+1}((theta - lambda) / delta) / T_{d+1}(sigma): the spectrum inside [lmin, lmax] is damped uniformly.  d SpMVs
+ * and d + 1 element-wise passes per apply, no dependency chain between rows, no inner product.  M^-1 is symmetric positive definite
+ * when A is (and lambda_min > 0): ConjugateGradient accepts it, as do BiCGStab and GMRES.  smm_hip_precond_create(a, 7, &M) means
+ * degree 3, GERSHGORIN, eig_ratio 30; smm_hip_precond_create_chebyshev below takes every parameter. */
+#define SMM_PRECOND_CHEBYSHEV 7
 
 #define SMM_DTYPE_F32 0
 #define SMM_DTYPE_F64 1
@@ -220,7 +232,7 @@ int smm_hip_csr_autotune(smm_hip_csr* m);
  *   SGS     reads A's values at every apply: after an edit it applies the EDITED A (bit for bit an SGS created after the edit), as the
  *           reference's SGSPreconditioner, which holds a reference to A (ref:1185).  Nothing of A's values is kept at create (the
  *           diagonal is only checked there).
- *   ILU0, IC0, JACOBI, BLOCK_ILU0, BLOCK_SGS  are snapshots taken at create (the reference's ilu0Val / ic0Val members): their factors
+ *   ILU0, IC0, JACOBI, BLOCK_ILU0, BLOCK_SGS, CHEBYSHEV  are snapshots taken at create (the reference's ilu0Val / ic0Val members): their factors
  *           do not follow the edit -- create a new one to follow it.  The A v half of smm_hip_precond_apply_spmv always uses the
  *           current A, in the encoding A is in at apply time.
  * Distributed handles (smm_hip_dist_csr) cannot be edited. */
@@ -418,7 +430,8 @@ int smm_hip_axpy_dev_f64(int n, double a, const double* d_x, const double* d_y, 
  *                                                      int maxIterations, T eps)            (ref:2316-2398)
  *   maxIterations == -1 means rows (not clamped otherwise); convergence test eps*eps > ||r||^2; when the
  *   initial residual already passes, x is NOT written (ref:2342-2344).  x may alias x0.
- *   With M != NULL (kind SMM_PRECOND_IC0) it replaces the IC0 overload (ref:2414-2505).
+ *   With M != NULL (kind SMM_PRECOND_IC0) it replaces the IC0 overload (ref:2414-2505); kind SMM_PRECOND_CHEBYSHEV runs the same loop
+ *   (every other kind: SMM_HIP_ERR_INVALID).
  * smm_hip_bicgstab_*  replaces  SolverStatus BiCGStab(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps
  *                                                   [, const Preconditioner& M])          (ref:2191-2303)
  *   x is in/out; maxIterations is clamped to rows, -1 means rows; the loop body always runs once; status is
@@ -599,7 +612,7 @@ int smm_hip_cgs_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, in
  *   status: DIVERGED if a column was dropped or rr is not finite; else SUCCESS if rr <= eps*eps; else MAX_ITERATIONS_REACHED
  * A solve that starts with rr <= eps*eps (an exact x included) returns x untouched, 0 iterations, SUCCESS.  rows == 0: SUCCESS, 0
  * iterations, nothing is read or written through b / x.  A matrix whose stored values are all zero: DIVERGED after 1 step, x untouched.
- * M: NULL, or any kind smm_hip_bicgstab_* accepts (JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS created for `a`).
+ * M: NULL, or any kind smm_hip_bicgstab_* accepts (JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV created for `a`).
  * Memory: (restart + 1) * rows elements for the basis (leading dimension rounded up to 64) plus two vectors.
  * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one solve give the same bits.
  * SMM_HIP_ERR_INVALID: restart outside 1 .. SMM_GMRES_MAX_RESTART, a null or dtype-mismatched matrix, a matrix that is not square,
@@ -662,6 +675,35 @@ int smm_hip_precond_block_record_bytes(const smm_hip_precond* M, int* lower, int
 int smm_hip_precond_block_level_cap(const smm_hip_precond* M, int* level_cap);
 int smm_hip_precond_block_count(const smm_hip_precond* M, int* nblocks);
 int smm_hip_precond_block_bounds(const smm_hip_precond* M, int* bounds, size_t count);
+/* The Chebyshev preconditioner (SMM_PRECOND_CHEBYSHEV) with every parameter.  degree 0 .. SMM_CHEB_MAX_DEGREE.  The bounds on the spectrum
+ * of D^-1 A are fixed at create time, on the device, and kept in the handle:
+ *   GERSHGORIN  lambda_max = max_i (sum_j |a_ij|) / |a_ii|: each row summed in DOUBLE, sequentially, in stored order, divided in double,
+ *               the maximum taken over the rows -- independent of the launch geometry, the same bits in both dtypes as that sentence
+ *               evaluated on the host.  A true upper bound.  One kernel and one 8-byte read-back.
+ *   POWER       power_steps (1 .. 1000; 10 is the usual choice) steps of the power method on D^-1 A from the fixed start
+ *               v[i] = 1 + (i mod 7) / 8: w = (A v) / diag, rq = (v.w) / (v.v), v = w / sqrt(w.w) (dot products in T, quotient and root in
+ *               double); lambda_max = min(GERSHGORIN, 1.1 * the last rq).  A HEURISTIC, NOT A BOUND: the Rayleigh quotient approaches the
+ *               largest eigenvalue from below, and 1.1 is a customary safety factor, not a proof.  An eigenvalue above lambda_max is
+ *               amplified by the polynomial instead of damped; a solver then stalls or diverges.
+ *   USER        lambda_min and lambda_max are the caller's, returned unchanged by smm_hip_precond_chebyshev_info.
+ * Outside USER lambda_min = lambda_max / eig_ratio (lambda_min, lambda_max arguments ignored).  30 is the customary smoother setting
+ * and what smm_hip_precond_create uses; it has NOT been tuned or measured on this hardware.
+ * SMM_HIP_ERR_PRECOND: a missing diagonal or one with |d| < 1e-5 (the Jacobi rule), an empty row, a bound that is not finite or not
+ * positive, lambda_min >= lambda_max, eig_ratio <= 1.  SMM_HIP_ERR_INVALID: degree outside 0 .. 64, an unknown bound_mode, power_steps
+ * outside 1 .. 1000 with POWER, a matrix that is not square.  A matrix with no rows gives a handle whose apply does nothing (bounds
+ * reported: 1 / eig_ratio and 1, or the caller's).
+ * The handle owns the two scratch vectors of an apply (allocated here; an apply allocates nothing), so ONE HANDLE MUST NOT BE APPLIED
+ * FROM TWO STREAMS AT ONCE -- create one handle per stream.  Like every snapshot kind it does not follow a value edit of `a` (the
+ * diagonal copy and the bounds are taken here; the SpMVs inside an apply would use the edited A): create a new one after an edit.
+ * smm_hip_precond_values_* returns the diagonal copy (rows values).  Batched and row-partitioned solvers refuse the kind. */
+#define SMM_CHEB_BOUND_GERSHGORIN 0
+#define SMM_CHEB_BOUND_POWER 1
+#define SMM_CHEB_BOUND_USER 2
+#define SMM_CHEB_MAX_DEGREE 64
+int smm_hip_precond_create_chebyshev(const smm_hip_csr* a, int degree, int bound_mode, double eig_ratio, int power_steps, double lambda_min,
+                                     double lambda_max, smm_hip_precond** out);
+/* degree, bound mode and the two bounds (as doubles) of a Chebyshev handle; any pointer may be NULL.  SMM_HIP_ERR_INVALID for other kinds. */
+int smm_hip_precond_chebyshev_info(const smm_hip_precond* M, int* degree, int* bound_mode, double* lambda_min, double* lambda_max);
 int smm_hip_precond_destroy(smm_hip_precond* M);
 int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower, int* levels_upper);
 /* How the two triangular sweeps of SGS / ILU0 / IC0 run (same numbers bit for bit either way):
@@ -691,7 +733,7 @@ int smm_hip_precond_apply_spmv_dev_f64(const smm_hip_precond* M, const double* d
  * since the last call tripped the bound, and clears the flag.  The solver entry points call it themselves before they return. */
 int smm_hip_precond_take_error(const smm_hip_precond* M, smm_hip_stream stream);
 /* copies the factor values (ILU0 / IC0 / BLOCK_ILU0: nnz values on A's pattern -- for BLOCK_ILU0 the entries that couple two blocks
- * keep A's value; JACOBI: rows diagonal entries) to the host */
+ * keep A's value; JACOBI, CHEBYSHEV: rows diagonal entries) to the host */
 int smm_hip_precond_values_f32(const smm_hip_precond* M, float* out, size_t count);
 int smm_hip_precond_values_f64(const smm_hip_precond* M, double* out, size_t count);
 

@@ -302,7 +302,7 @@ private:
 };
 
 // ref:1002-1006; JACOBI and the BLOCK_ forms (ILU0 / SGS of the block-diagonal part of A, smm_hip.h) are additions
-enum class SolverPreconditioner { NONE, SYMMETRIC_GAUS_SEIDEL, ILU0, JACOBI, BLOCK_ILU0, BLOCK_SGS };
+enum class SolverPreconditioner { NONE, SYMMETRIC_GAUS_SEIDEL, ILU0, JACOBI, BLOCK_ILU0, BLOCK_SGS, CHEBYSHEV };
 enum class SolverStatus { SUCCESS = 0, DIVERGED, MAX_ITERATIONS_REACHED };                       // ref:2010-2014
 
 // ---- CSRMatrix<T> (ref:1010-1641) -------------------------------------------------------------------------------------------
@@ -388,7 +388,7 @@ public:
 	public:
 		PreconditionerBase(const PreconditionerBase&) = delete;
 		PreconditionerBase& operator=(const PreconditionerBase&) = delete;
-		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h) { o.h = nullptr; }
+		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h), cheb(o.cheb) { o.h = nullptr; }
 		~PreconditionerBase() { smm_hip_precond_destroy(h); }
 		// non-zero on structural failure (missing / tiny diagonal, empty row, non-SPD pivot), like ref:1668-1693
 		// (every init / apply / handle goes through m->device(): entries queued by updateEntry / addEntry / setValue reach the matrix's
@@ -397,6 +397,9 @@ public:
 			const smm_hip_csr* dev = m->device();
 			if (!dev) return 1;
 			if (h) return 0;
+			if (kind == SMM_PRECOND_CHEBYSHEV) {
+				return detail::note(smm_hip_precond_create_chebyshev(dev, cheb.degree, cheb.boundMode, cheb.eigRatio, cheb.powerSteps, cheb.lambdaMin, cheb.lambdaMax, &h)) == SMM_HIP_OK ? 0 : 1;
+			}
 			return detail::note(smm_hip_precond_create(dev, kind, &h)) == SMM_HIP_OK ? 0 : 1;
 		}
 		int apply(const T* rhs, T* x) const noexcept {
@@ -410,6 +413,12 @@ public:
 		const CSRMatrix* m;
 		int kind;
 		mutable smm_hip_precond* h = nullptr;
+		struct ChebyshevParameters {  // what smm_hip_precond_create_chebyshev takes (kind CHEBYSHEV only); the defaults of smm_hip_precond_create
+			int degree = 3, boundMode = SMM_CHEB_BOUND_GERSHGORIN;
+			double eigRatio = 30.0;
+			int powerSteps = 10;
+			double lambdaMin = 0.0, lambdaMax = 0.0;
+		} cheb;
 	};
 	class IDPreconditioner {  // ref:1166-1170
 	public:
@@ -450,6 +459,30 @@ public:
 	public:
 		BlockSGSPreconditioner(const CSRMatrix& m) noexcept : PreconditionerBase(m, SMM_PRECOND_BLOCK_SGS) {}
 		BlockSGSPreconditioner(BlockSGSPreconditioner&&) noexcept = default;
+	};
+
+	// addition: a Chebyshev polynomial in D^-1 A (smm_hip.h, SMM_PRECOND_CHEBYSHEV): SpMVs and element-wise passes only, symmetric positive
+	// definite for such a matrix -- taken by ConjugateGradient, BiCGStab and GMRES.  boundMode: SMM_CHEB_BOUND_GERSHGORIN / _POWER (a heuristic,
+	// not a bound) / _USER (lambdaMin, lambdaMax are the caller's).  One object serves one stream at a time (it owns its scratch vectors).
+	class ChebyshevPreconditioner : public PreconditionerBase {
+	public:
+		ChebyshevPreconditioner(const CSRMatrix& m, int degree = 3, int boundMode = SMM_CHEB_BOUND_GERSHGORIN, double eigRatio = 30.0, int powerSteps = 10,
+		                        double lambdaMin = 0.0, double lambdaMax = 0.0) noexcept
+		    : PreconditionerBase(m, SMM_PRECOND_CHEBYSHEV) {
+			this->cheb.degree = degree;
+			this->cheb.boundMode = boundMode;
+			this->cheb.eigRatio = eigRatio;
+			this->cheb.powerSteps = powerSteps;
+			this->cheb.lambdaMin = lambdaMin;
+			this->cheb.lambdaMax = lambdaMax;
+		}
+		ChebyshevPreconditioner(ChebyshevPreconditioner&&) noexcept = default;
+		int validate() noexcept { return this->init(); }
+		// degree, bound mode and bounds as the handle keeps them; non-zero when the preconditioner could not be made
+		int info(int* degree, int* boundMode, double* lambdaMin, double* lambdaMax) const noexcept {
+			if (this->init()) return 1;
+			return detail::note(smm_hip_precond_chebyshev_info(this->h, degree, boundMode, lambdaMin, lambdaMax)) == SMM_HIP_OK ? 0 : 1;
+		}
 	};
 
 	CSRMatrix() noexcept = default;
@@ -744,9 +777,17 @@ public:
 			return BlockILU0Preconditioner(*this);
 		} else if constexpr (precond == SolverPreconditioner::BLOCK_SGS) {
 			return BlockSGSPreconditioner(*this);
+		} else if constexpr (precond == SolverPreconditioner::CHEBYSHEV) {
+			return ChebyshevPreconditioner(*this);  // degree 3, Gershgorin bound, ratio 30
 		} else {
 			return JacobiPreconditioner(*this);
 		}
+	}
+
+	// the Chebyshev preconditioner with chosen parameters (the arguments of smm_hip_precond_create_chebyshev)
+	ChebyshevPreconditioner getChebyshevPreconditioner(int degree = 3, int boundMode = SMM_CHEB_BOUND_GERSHGORIN, double eigRatio = 30.0, int powerSteps = 10,
+	                                                   double lambdaMin = 0.0, double lambdaMax = 0.0) const noexcept {
+		return ChebyshevPreconditioner(*this, degree, boundMode, eigRatio, powerSteps, lambdaMin, lambdaMax);
 	}
 
 	// device mirror of the three arrays, created on first use; nullptr when there is no GPU
@@ -915,6 +956,19 @@ inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, c
 template <typename T>
 inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
                                       const typename CSRMatrix<T>::IC0Preconditioner& M) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = M.handle();
+	const int rc = d && h ? detail::Abi<T>::cg(d, b, x0, x, maxIterations, eps, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// addition: the same preconditioned loop with the Chebyshev polynomial preconditioner (symmetric positive definite for such a matrix)
+template <typename T>
+using ChebyshevPreconditioner = typename CSRMatrix<T>::ChebyshevPreconditioner;
+template <typename T>
+inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
+                                      const typename CSRMatrix<T>::ChebyshevPreconditioner& M) {
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const smm_hip_precond* h = M.handle();

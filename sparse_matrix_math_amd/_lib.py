@@ -149,6 +149,8 @@ _PLAIN = {
     "smm_hip_precond_block_record_bytes": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "smm_hip_precond_block_count": (c_int, [_P, POINTER(c_int)]),
     "smm_hip_precond_block_bounds": (c_int, [_P, _P, c_size_t]),
+    "smm_hip_precond_create_chebyshev": (c_int, [_P, c_int, c_int, c_double, c_int, c_double, c_double, POINTER(_P)]),
+    "smm_hip_precond_chebyshev_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_double)]),
     "smm_hip_precond_destroy": (c_int, [_P]),
     "smm_hip_precond_set_sweep": (c_int, [_P, c_int]),
     "smm_hip_precond_take_error": (c_int, [_P, _P]),

@@ -223,7 +223,7 @@ struct smm_hip_precond {
 	int kind = SMM_PRECOND_NONE;
 	int dtype = 0;
 	const smm_hip_csr* a = nullptr;
-	void* d_values = nullptr;  // JACOBI: diag[rows]; ILU0 / IC0: factor values on A's pattern [nnz]; SGS: null (uses A)
+	void* d_values = nullptr;  // JACOBI, CHEBYSHEV: diag[rows]; ILU0 / IC0: factor values on A's pattern [nnz]; SGS: null (uses A)
 	size_t n_values = 0;
 	// level schedules of the lower / upper triangular sweeps: rows sorted by level
 	int* d_order_lo = nullptr;
@@ -231,6 +231,7 @@ struct smm_hip_precond {
 	std::vector<int> lvl_ptr_lo, lvl_ptr_up;  // host: level l covers order[lvl_ptr[l] .. lvl_ptr[l+1])
 	struct smm_precond_plan* plan = nullptr;  // launch groups of the two sweeps (smm_precond.hip)
 	struct smm_precond_block* blk = nullptr;  // BLOCK_ILU0 / BLOCK_SGS: row blocks + packed sweep records (smm_precond_block.hip)
+	struct smm_precond_cheb* cheb = nullptr;  // CHEBYSHEV: degree, bounds, coefficients and the two scratch vectors (smm_precond_cheb.hip)
 };
 
 namespace smm {
@@ -571,5 +572,12 @@ void blockDestroy(struct smm_precond_block* B);
 void blockLevels(const struct smm_precond_block* B, int* lo, int* up);
 int blockDefaultRows();
 int blockDefaultLevelCap();
+
+// Chebyshev polynomial preconditioner (smm_precond_cheb.hip); the handle's kind, dtype and matrix are set by the caller
+template <typename T>
+int chebCreateTyped(const smm_hip_csr* a, int degree, int boundMode, double eigRatio, int powerSteps, double lmin, double lmax, smm_hip_precond* M);
+template <typename T>
+int chebApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
+void chebDestroy(struct smm_precond_cheb* C);
 
 }  // namespace smm

@@ -27,7 +27,8 @@ class SolverStatus(enum.IntEnum):  # ref:2010-2014
 
 class SolverPreconditioner(enum.IntEnum):
     """ref:1002-1006 has NONE, SYMMETRIC_GAUS_SEIDEL (sic) and ILU0; JACOBI, IC0 and the BLOCK_ forms (ILU0 / SGS of the
-    block-diagonal part of A, one wavefront per block) are additions.  Values are the SMM_PRECOND_* codes of the C ABI."""
+    block-diagonal part of A, one wavefront per block) are additions, and so is CHEBYSHEV (a polynomial in D^-1 A: SpMVs and
+    element-wise passes only).  Values are the SMM_PRECOND_* codes of the C ABI."""
     NONE = 0
     JACOBI = 1
     ILU0 = 2
@@ -35,12 +36,15 @@ class SolverPreconditioner(enum.IntEnum):
     IC0 = 4
     BLOCK_ILU0 = 5
     BLOCK_SGS = 6
+    CHEBYSHEV = 7
 
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
 MAX_RHS = 8  # SMM_HIP_MAX_RHS: the most right-hand sides one block holds
 SPMV_AUTO, SPMV_VECTOR, SPMV_STREAM, SPMV_PATTERN = 0, 1, 2, 3
 SWEEP_AUTO, SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD = 0, 1, 2, 3
+CHEB_BOUND_GERSHGORIN, CHEB_BOUND_POWER, CHEB_BOUND_USER = 0, 1, 2  # SMM_CHEB_BOUND_*: where a Chebyshev preconditioner's bounds come from
+_CHEB_BOUNDS = {"GERSHGORIN": CHEB_BOUND_GERSHGORIN, "POWER": CHEB_BOUND_POWER, "USER": CHEB_BOUND_USER}
 
 _SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
 _CT = {"f32": ctypes.c_float, "f64": ctypes.c_double}
@@ -155,11 +159,15 @@ def profile_read_waits(reset=True):
 class Preconditioner:
     """`int apply(const T* rhs, T* x) const` (ref:1173-1235).  Created by CSRMatrix.getPreconditioner."""
 
-    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None):
+    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None):
         self.matrix = matrix  # keeps the matrix alive (the reference holds a const CSRMatrix&)
         self.kind = SolverPreconditioner(kind)
         self._h = ctypes.c_void_p()
-        if block_rows is None and level_cap is None and partition is None:
+        if chebyshev is not None:  # (degree, bound mode, eig_ratio, power_steps, lambda_min, lambda_max): CHEBYSHEV with chosen parameters
+            degree, bound, ratio, steps, lmin, lmax = chebyshev
+            check(_lib.load().smm_hip_precond_create_chebyshev(matrix._h, int(degree), int(bound), float(ratio), int(steps), float(lmin), float(lmax),
+                                                               ctypes.byref(self._h)))
+        elif block_rows is None and level_cap is None and partition is None:
             check(_lib.load().smm_hip_precond_create(matrix._h, int(kind), ctypes.byref(self._h)))
         elif level_cap is None and partition is None:  # BLOCK_ILU0 / BLOCK_SGS with a chosen block size
             check(_lib.load().smm_hip_precond_create_block(matrix._h, int(kind), int(block_rows), ctypes.byref(self._h)))
@@ -219,9 +227,15 @@ class Preconditioner:
         """synchronises `stream`; raises when a triangular sweep applied on it failed to finish (apply_dev cannot report it)"""
         check(_lib.load().smm_hip_precond_take_error(self._h, _dptr(stream)))
 
+    def chebyshev_info(self):
+        """CHEBYSHEV: {degree, bound (CHEB_BOUND_*), lambda_min, lambda_max} as the handle keeps them"""
+        degree, bound, lmin, lmax = ctypes.c_int(), ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+        check(_lib.load().smm_hip_precond_chebyshev_info(self._h, ctypes.byref(degree), ctypes.byref(bound), ctypes.byref(lmin), ctypes.byref(lmax)))
+        return {"degree": degree.value, "bound": bound.value, "lambda_min": lmin.value, "lambda_max": lmax.value}
+
     def values(self):
-        """factor values: diag (JACOBI) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern"""
-        count = self.matrix.rows if self.kind == SolverPreconditioner.JACOBI else self.matrix.nnz
+        """factor values: diag (JACOBI, CHEBYSHEV) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern"""
+        count = self.matrix.rows if self.kind in (SolverPreconditioner.JACOBI, SolverPreconditioner.CHEBYSHEV) else self.matrix.nnz
         out = np.empty(count, dtype=self.matrix.dtype)
         check(_fn("smm_hip_precond_values", self.matrix._suf)(self._h, _host(out, self.matrix.dtype, "out"), count))
         return out
@@ -531,7 +545,22 @@ class CSRMatrix:
         name = "smm_hip_spmv_fused_finish_dev" if finish else "smm_hip_spmv_fused_dev"
         check(_fn(name, self._suf)(self._h, int(op), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), int(dot_mode), _dptr(d_w1), _dptr(d_partials), _dptr(stream)))
 
-    def getPreconditioner(self, kind, block_rows=None, level_cap=None, partition=None):  # ref:1643-1651; the keyword arguments: BLOCK_ kinds only (None = default)
+    def getPreconditioner(self, kind, block_rows=None, level_cap=None, partition=None, degree=None, bound=None, eig_ratio=None, power_steps=None,
+                          lambda_min=None, lambda_max=None):
+        """ref:1643-1651.  kind: a SolverPreconditioner or its name ("CHEBYSHEV").  block_rows / level_cap / partition: BLOCK_ kinds only;
+        degree (3) / bound ("GERSHGORIN", "POWER", "USER" or a CHEB_BOUND_* code) / eig_ratio (30) / power_steps (10) / lambda_min /
+        lambda_max (USER): CHEBYSHEV only.  None = the default."""
+        if isinstance(kind, str):
+            kind = SolverPreconditioner[kind]
+        cheb = (degree, bound, eig_ratio, power_steps, lambda_min, lambda_max)
+        if any(v is not None for v in cheb):
+            if SolverPreconditioner(kind) != SolverPreconditioner.CHEBYSHEV:
+                raise ValueError("degree / bound / eig_ratio / power_steps / lambda_min / lambda_max belong to the CHEBYSHEV preconditioner")
+            if isinstance(bound, str):
+                bound = _CHEB_BOUNDS[bound.upper()]
+            cheb = (3 if degree is None else degree, CHEB_BOUND_GERSHGORIN if bound is None else bound, 30.0 if eig_ratio is None else eig_ratio,
+                    10 if power_steps is None else power_steps, 0.0 if lambda_min is None else lambda_min, 0.0 if lambda_max is None else lambda_max)
+            return Preconditioner(self, kind, chebyshev=cheb)
         return Preconditioner(self, kind, block_rows, level_cap, partition)
 
     def close(self):
@@ -647,7 +676,7 @@ def _mh(M):
 
 
 def ConjugateGradient(a, b, x0, x, maxIterations, eps, M=None, info=None):
-    """ref:2316-2398 (M = IC0 preconditioner: ref:2414-2505).  x may be x0.  Returns SolverStatus; `info`, when a
+    """ref:2316-2398 (M = IC0 preconditioner: ref:2414-2505; a CHEBYSHEV preconditioner runs the same loop).  x may be x0.  Returns SolverStatus; `info`, when a
     dict, receives iterations and resnorm2."""
     suf = a._suf
     st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
