@@ -89,6 +89,40 @@ extern "C" {
  * when A is (and lambda_min > 0): ConjugateGradient accepts it, as do BiCGStab and GMRES.  smm_hip_precond_create(a, 7, &M) means
  * degree 3, GERSHGORIN, eig_ratio 30; smm_hip_precond_create_chebyshev below takes every parameter. */
 #define SMM_PRECOND_CHEBYSHEV 7
+/* Smoothed-aggregation multigrid with a symmetric V-cycle (an addition; csrc/smm_precond_amg.hip, the definition line by line is
+ * tests/amg_restatement.py).  Integer results are exact; values are bit for bit wherever the parts they come from are.
+ * Per level l, from A_l with n rows (A_0 = a); every row needs a stored diagonal with |d| >= 1e-5 (else SMM_HIP_ERR_PRECOND):
+ *   strength   a stored entry (i, j), j != i, is strong iff a_ij^2 >= ((theta_l^2 |a_ii|) |a_jj|) in double, theta_l = theta 0.5^l.
+ *              N(i) = the columns of row i's strong entries, as stored, not symmetrised.
+ *   roots      a distance-2 maximal independent set in synchronous rounds.  Every row starts undecided (state 1; 2 = root, 0 = not a root).
+ *              The key of row i is (state, h(i), i), compared lexicographically, h = the 32-bit murmur3 finaliser of i + 1
+ *              (h ^= h>>16; h *= 0x85ebca6b; h ^= h>>13; h *= 0xc2b2ae35; h ^= h>>16).  In a round K1_i = max(K_i, max_{j in N(i)} K_j), then
+ *              K2_i = max(K1_i, max_{j in N(i)} K1_j), each from the previous array as a whole.  An undecided row whose K2 carries its own
+ *              index becomes a root; otherwise an undecided row whose K2 has state 2 becomes a non-root.  Rounds repeat until no row is
+ *              undecided.  Roots are numbered in ascending row order.
+ *   aggregates phase 1: a non-root with a root in N(i) joins the root with the smallest number.  Phase 2: a row still unassigned joins the
+ *              smallest aggregate number among the assigned members of N(i); each pass works from the previous assignment as a whole and
+ *              passes repeat until one assigns nothing.  Rows still unassigned become aggregates of their own, numbered after the roots
+ *              in ascending row order.  n_c = the number of aggregates.
+ *   operators  T is n x n_c with one entry 1 per row.  S = I - omega D^-1 A_l on A_l's pattern, omega = 4 / (3 lambda), lambda the
+ *              Gershgorin bound of D^-1 A_l as the Chebyshev kind computes it: s = T(omega) / d_i, an off-diagonal entry is -(s a_ij), the
+ *              diagonal entry 1 - s a_ii, every operation rounding once.  P_l = S T, R_l = P_l^T, A_{l+1} = R_l (A_l P_l) by
+ *              smm_hip_csr_multiply_create and smm_hip_csr_transpose_create; each is an ordinary smm_hip_csr.
+ *   smoother   M_l = the Chebyshev preconditioner of A_l: degree smooth_degree, GERSHGORIN, eig_ratio.
+ * Level l is the coarsest when n <= coarse_rows, or l + 1 == max_levels, or the level would not shrink (10 n_c >= 9 n).  A coarsest level
+ * of more than 1024 rows: SMM_HIP_ERR_PRECOND, the message names the level sizes.  With max_levels 1 or rows <= coarse_rows the
+ * preconditioner is the dense solve alone.  Coarsest level: A_L is copied to the host once, inverted in double by Gauss-Jordan with
+ * partial pivoting (a pivot that is zero or not finite: SMM_HIP_ERR_PRECOND), rounded to T once and kept dense on the device; an apply is
+ * one launch, one wavefront per row: lane k sums columns k, k + 64, ... in ascending order from +0.0 with _smm_fma, the 64 partial sums
+ * are combined by the xor butterfly (32, 16, ... 1) of the dot kernels.
+ * The cycle V_l(b), every step a device operation:
+ *   x = M_l b;  r = b - A_l x;  r_c = R_l r;  e_c = V_{l+1}(r_c);  x = x + P_l e_c;  r = b - A_l x;  d = M_l r;  x = x + d
+ * (the SpMVs with OP_SUB, OP_ASSIGN, OP_ADD in whatever kernel family the level's matrix runs).  z = M^-1 r is V_0(r): a fixed linear
+ * operator, symmetric positive definite when A is (the Gershgorin bound keeps the Chebyshev residual polynomial below 1 on (0, lambda]).
+ * Launches only: no host round trip, no allocation; every launch honours the solver's done flag.  ConjugateGradient (symmetric positive
+ * definite matrices only), BiCGStab and GMRES accept it; the batched, row-partitioned and single-launch paths refuse it or are not
+ * taken.  smm_hip_precond_create(a, 8, &M) means theta 0.08, max_levels 10, coarse_rows 256, smooth_degree 2, eig_ratio 30. */
+#define SMM_PRECOND_AMG 8
 
 #define SMM_DTYPE_F32 0
 #define SMM_DTYPE_F64 1
@@ -232,7 +266,7 @@ int smm_hip_csr_autotune(smm_hip_csr* m);
  *   SGS     reads A's values at every apply: after an edit it applies the EDITED A (bit for bit an SGS created after the edit), as the
  *           reference's SGSPreconditioner, which holds a reference to A (ref:1185).  Nothing of A's values is kept at create (the
  *           diagonal is only checked there).
- *   ILU0, IC0, JACOBI, BLOCK_ILU0, BLOCK_SGS, CHEBYSHEV  are snapshots taken at create (the reference's ilu0Val / ic0Val members): their factors
+ *   ILU0, IC0, JACOBI, BLOCK_ILU0, BLOCK_SGS, CHEBYSHEV, AMG  are snapshots taken at create (the reference's ilu0Val / ic0Val members): their factors
  *           do not follow the edit -- create a new one to follow it.  The A v half of smm_hip_precond_apply_spmv always uses the
  *           current A, in the encoding A is in at apply time.
  * Distributed handles (smm_hip_dist_csr) cannot be edited. */
@@ -430,7 +464,7 @@ int smm_hip_axpy_dev_f64(int n, double a, const double* d_x, const double* d_y, 
  *                                                      int maxIterations, T eps)            (ref:2316-2398)
  *   maxIterations == -1 means rows (not clamped otherwise); convergence test eps*eps > ||r||^2; when the
  *   initial residual already passes, x is NOT written (ref:2342-2344).  x may alias x0.
- *   With M != NULL (kind SMM_PRECOND_IC0) it replaces the IC0 overload (ref:2414-2505); kind SMM_PRECOND_CHEBYSHEV runs the same loop
+ *   With M != NULL (kind SMM_PRECOND_IC0) it replaces the IC0 overload (ref:2414-2505); kinds SMM_PRECOND_CHEBYSHEV and SMM_PRECOND_AMG run the same loop
  *   (every other kind: SMM_HIP_ERR_INVALID).
  * smm_hip_bicgstab_*  replaces  SolverStatus BiCGStab(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps
  *                                                   [, const Preconditioner& M])          (ref:2191-2303)
@@ -612,7 +646,7 @@ int smm_hip_cgs_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, in
  *   status: DIVERGED if a column was dropped or rr is not finite; else SUCCESS if rr <= eps*eps; else MAX_ITERATIONS_REACHED
  * A solve that starts with rr <= eps*eps (an exact x included) returns x untouched, 0 iterations, SUCCESS.  rows == 0: SUCCESS, 0
  * iterations, nothing is read or written through b / x.  A matrix whose stored values are all zero: DIVERGED after 1 step, x untouched.
- * M: NULL, or any kind smm_hip_bicgstab_* accepts (JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV created for `a`).
+ * M: NULL, or any kind smm_hip_bicgstab_* accepts (JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG created for `a`).
  * Memory: (restart + 1) * rows elements for the basis (leading dimension rounded up to 64) plus two vectors.
  * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one solve give the same bits.
  * SMM_HIP_ERR_INVALID: restart outside 1 .. SMM_GMRES_MAX_RESTART, a null or dtype-mismatched matrix, a matrix that is not square,
@@ -704,6 +738,37 @@ int smm_hip_precond_create_chebyshev(const smm_hip_csr* a, int degree, int bound
                                      double lambda_max, smm_hip_precond** out);
 /* degree, bound mode and the two bounds (as doubles) of a Chebyshev handle; any pointer may be NULL.  SMM_HIP_ERR_INVALID for other kinds. */
 int smm_hip_precond_chebyshev_info(const smm_hip_precond* M, int* degree, int* bound_mode, double* lambda_min, double* lambda_max);
+/* The multigrid preconditioner (SMM_PRECOND_AMG, defined above) with every parameter.
+ * SMM_HIP_ERR_INVALID: a matrix that is not square; theta outside [0, 1) or not finite; max_levels outside 1 .. 16; coarse_rows outside
+ * 1 .. 1024; smooth_degree outside 0 .. 64.  SMM_HIP_ERR_PRECOND: eig_ratio not finite or <= 1; on any level an empty row, a missing
+ * diagonal or |d| < 1e-5; a coarsest level of more than 1024 rows; a singular coarsest matrix.  A matrix with no rows gives a handle
+ * whose apply does nothing.
+ * Set-up cost: per level three sparse products (S T, A P, R (A P)) and one transpose, a handful of one-lane-per-row passes per round of
+ * the root selection with ONE 4-byte read-back per round, two scans, and the host inversion of the coarsest matrix (n_L^3 operations).
+ * The handle owns every level's matrices, smoothers and vectors (allocated here; an apply allocates nothing), so ONE HANDLE MUST NOT BE
+ * APPLIED FROM TWO STREAMS AT ONCE.  It is a SNAPSHOT: it does not follow a value edit of `a` -- call smm_hip_precond_amg_refresh, or
+ * create a new one.
+ * amg_refresh: keeps every aggregate and every pattern and redoes the values from the present values of `a`: S is refilled, P, A P and
+ *   A_{l+1} are recomputed by smm_hip_csr_multiply_into_*, R by smm_hip_csr_transpose_refresh_*, the smoothers are re-made and the coarse
+ *   inverse recomputed.  Afterwards the values equal those of a fresh create on a matrix whose aggregates come out the same.
+ *   Synchronous.  On an error the handle must not be applied any more (destroy it).
+ * amg_info: the number of levels, rows[l] and nnz[l] of A_l for l < count (either array may be NULL), and the operator complexity
+ *   sum_l nnz(A_l) / nnz(A_0).
+ * amg_level: BORROWED handles owned by M (do not destroy them; they die with M): A_l, P_l, R_l; P_l and R_l are NULL on the coarsest
+ *   level.  They may be read (smm_hip_csr_get_pattern / _get_values_*) and their kernel choice set (smm_hip_csr_set_kernel).
+ * amg_aggregates: the aggregate number of the first `count` rows of level l (count <= rows of that level); the coarsest level has none
+ *   (SMM_HIP_ERR_INVALID).
+ * amg_coarse_inverse_*: the first `count` values of the dense inverse of the coarsest matrix, row-major, n_L x n_L. */
+#define SMM_AMG_MAX_LEVELS 16
+#define SMM_AMG_MAX_COARSE_ROWS 1024
+int smm_hip_precond_create_amg(const smm_hip_csr* a, double theta, int max_levels, int coarse_rows, int smooth_degree, double eig_ratio,
+                               smm_hip_precond** out);
+int smm_hip_precond_amg_refresh(smm_hip_precond* M);
+int smm_hip_precond_amg_info(const smm_hip_precond* M, int* levels, int* rows, int* nnz, size_t count, double* operator_complexity);
+int smm_hip_precond_amg_level(const smm_hip_precond* M, int level, smm_hip_csr** a_l, smm_hip_csr** p_l, smm_hip_csr** r_l);
+int smm_hip_precond_amg_aggregates(const smm_hip_precond* M, int level, int* agg, size_t count);
+int smm_hip_precond_amg_coarse_inverse_f32(const smm_hip_precond* M, float* out, size_t count);
+int smm_hip_precond_amg_coarse_inverse_f64(const smm_hip_precond* M, double* out, size_t count);
 int smm_hip_precond_destroy(smm_hip_precond* M);
 int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower, int* levels_upper);
 /* How the two triangular sweeps of SGS / ILU0 / IC0 run (same numbers bit for bit either way):
@@ -733,7 +798,7 @@ int smm_hip_precond_apply_spmv_dev_f64(const smm_hip_precond* M, const double* d
  * since the last call tripped the bound, and clears the flag.  The solver entry points call it themselves before they return. */
 int smm_hip_precond_take_error(const smm_hip_precond* M, smm_hip_stream stream);
 /* copies the factor values (ILU0 / IC0 / BLOCK_ILU0: nnz values on A's pattern -- for BLOCK_ILU0 the entries that couple two blocks
- * keep A's value; JACOBI, CHEBYSHEV: rows diagonal entries) to the host */
+ * keep A's value; JACOBI, CHEBYSHEV, AMG: rows diagonal entries of (level 0 of) the matrix) to the host */
 int smm_hip_precond_values_f32(const smm_hip_precond* M, float* out, size_t count);
 int smm_hip_precond_values_f64(const smm_hip_precond* M, double* out, size_t count);
 

@@ -302,7 +302,7 @@ private:
 };
 
 // ref:1002-1006; JACOBI and the BLOCK_ forms (ILU0 / SGS of the block-diagonal part of A, smm_hip.h) are additions
-enum class SolverPreconditioner { NONE, SYMMETRIC_GAUS_SEIDEL, ILU0, JACOBI, BLOCK_ILU0, BLOCK_SGS, CHEBYSHEV };
+enum class SolverPreconditioner { NONE, SYMMETRIC_GAUS_SEIDEL, ILU0, JACOBI, BLOCK_ILU0, BLOCK_SGS, CHEBYSHEV, AMG };
 enum class SolverStatus { SUCCESS = 0, DIVERGED, MAX_ITERATIONS_REACHED };                       // ref:2010-2014
 
 // ---- CSRMatrix<T> (ref:1010-1641) -------------------------------------------------------------------------------------------
@@ -388,7 +388,7 @@ public:
 	public:
 		PreconditionerBase(const PreconditionerBase&) = delete;
 		PreconditionerBase& operator=(const PreconditionerBase&) = delete;
-		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h), cheb(o.cheb) { o.h = nullptr; }
+		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h), cheb(o.cheb), amg(o.amg) { o.h = nullptr; }
 		~PreconditionerBase() { smm_hip_precond_destroy(h); }
 		// non-zero on structural failure (missing / tiny diagonal, empty row, non-SPD pivot), like ref:1668-1693
 		// (every init / apply / handle goes through m->device(): entries queued by updateEntry / addEntry / setValue reach the matrix's
@@ -399,6 +399,9 @@ public:
 			if (h) return 0;
 			if (kind == SMM_PRECOND_CHEBYSHEV) {
 				return detail::note(smm_hip_precond_create_chebyshev(dev, cheb.degree, cheb.boundMode, cheb.eigRatio, cheb.powerSteps, cheb.lambdaMin, cheb.lambdaMax, &h)) == SMM_HIP_OK ? 0 : 1;
+			}
+			if (kind == SMM_PRECOND_AMG) {
+				return detail::note(smm_hip_precond_create_amg(dev, amg.theta, amg.maxLevels, amg.coarseRows, amg.smoothDegree, amg.eigRatio, &h)) == SMM_HIP_OK ? 0 : 1;
 			}
 			return detail::note(smm_hip_precond_create(dev, kind, &h)) == SMM_HIP_OK ? 0 : 1;
 		}
@@ -419,6 +422,11 @@ public:
 			int powerSteps = 10;
 			double lambdaMin = 0.0, lambdaMax = 0.0;
 		} cheb;
+		struct AMGParameters {  // what smm_hip_precond_create_amg takes (kind AMG only); the defaults of smm_hip_precond_create
+			double theta = 0.08;
+			int maxLevels = 10, coarseRows = 256, smoothDegree = 2;
+			double eigRatio = 30.0;
+		} amg;
 	};
 	class IDPreconditioner {  // ref:1166-1170
 	public:
@@ -482,6 +490,35 @@ public:
 		int info(int* degree, int* boundMode, double* lambdaMin, double* lambdaMax) const noexcept {
 			if (this->init()) return 1;
 			return detail::note(smm_hip_precond_chebyshev_info(this->h, degree, boundMode, lambdaMin, lambdaMax)) == SMM_HIP_OK ? 0 : 1;
+		}
+	};
+
+	// addition: smoothed-aggregation multigrid with a symmetric V-cycle (smm_hip.h, SMM_PRECOND_AMG): the one kind whose iteration count does
+	// not grow with the grid; symmetric positive definite for such a matrix -- taken by ConjugateGradient, BiCGStab and GMRES (matrices that
+	// are not symmetric: the last two only).  A snapshot of the matrix's values: refresh() follows a value edit with the aggregates kept.
+	// One object serves one stream at a time (it owns its level vectors).
+	class AMGPreconditioner : public PreconditionerBase {
+	public:
+		AMGPreconditioner(const CSRMatrix& m, double theta = 0.08, int maxLevels = 10, int coarseRows = 256, int smoothDegree = 2, double eigRatio = 30.0) noexcept
+		    : PreconditionerBase(m, SMM_PRECOND_AMG) {
+			this->amg.theta = theta;
+			this->amg.maxLevels = maxLevels;
+			this->amg.coarseRows = coarseRows;
+			this->amg.smoothDegree = smoothDegree;
+			this->amg.eigRatio = eigRatio;
+		}
+		AMGPreconditioner(AMGPreconditioner&&) noexcept = default;
+		int validate() noexcept { return this->init(); }
+		// levels, rows / nnz of the first `count` levels (either may be null) and the operator complexity; non-zero when it could not be made
+		int info(int* levels, int* rows, int* nnz, size_t count, double* operatorComplexity) const noexcept {
+			if (this->init()) return 1;
+			return detail::note(smm_hip_precond_amg_info(this->h, levels, rows, nnz, count, operatorComplexity)) == SMM_HIP_OK ? 0 : 1;
+		}
+		// the values again from the matrix's present values, aggregates and patterns kept
+		int refresh() noexcept {
+			if (this->init()) return 1;
+			if (!this->m->device()) return 1;  // (queued entry edits reach the device first)
+			return detail::note(smm_hip_precond_amg_refresh(this->h)) == SMM_HIP_OK ? 0 : 1;
 		}
 	};
 
@@ -779,6 +816,8 @@ public:
 			return BlockSGSPreconditioner(*this);
 		} else if constexpr (precond == SolverPreconditioner::CHEBYSHEV) {
 			return ChebyshevPreconditioner(*this);  // degree 3, Gershgorin bound, ratio 30
+		} else if constexpr (precond == SolverPreconditioner::AMG) {
+			return AMGPreconditioner(*this);  // theta 0.08, 10 levels, 256 coarse rows, degree-2 smoother, ratio 30
 		} else {
 			return JacobiPreconditioner(*this);
 		}
@@ -788,6 +827,11 @@ public:
 	ChebyshevPreconditioner getChebyshevPreconditioner(int degree = 3, int boundMode = SMM_CHEB_BOUND_GERSHGORIN, double eigRatio = 30.0, int powerSteps = 10,
 	                                                   double lambdaMin = 0.0, double lambdaMax = 0.0) const noexcept {
 		return ChebyshevPreconditioner(*this, degree, boundMode, eigRatio, powerSteps, lambdaMin, lambdaMax);
+	}
+
+	// the multigrid preconditioner with chosen parameters (the arguments of smm_hip_precond_create_amg)
+	AMGPreconditioner getAMGPreconditioner(double theta = 0.08, int maxLevels = 10, int coarseRows = 256, int smoothDegree = 2, double eigRatio = 30.0) const noexcept {
+		return AMGPreconditioner(*this, theta, maxLevels, coarseRows, smoothDegree, eigRatio);
 	}
 
 	// device mirror of the three arrays, created on first use; nullptr when there is no GPU
@@ -969,6 +1013,19 @@ using ChebyshevPreconditioner = typename CSRMatrix<T>::ChebyshevPreconditioner;
 template <typename T>
 inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
                                       const typename CSRMatrix<T>::ChebyshevPreconditioner& M) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = M.handle();
+	const int rc = d && h ? detail::Abi<T>::cg(d, b, x0, x, maxIterations, eps, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// addition: ... and with the multigrid V-cycle
+template <typename T>
+using AMGPreconditioner = typename CSRMatrix<T>::AMGPreconditioner;
+template <typename T>
+inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
+                                      const typename CSRMatrix<T>::AMGPreconditioner& M) {
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const smm_hip_precond* h = M.handle();

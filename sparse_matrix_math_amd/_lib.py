@@ -72,6 +72,7 @@ _TYPED = {
     "smm_hip_precond_apply_spmv": (c_int, [_P, _P, _P]),
     "smm_hip_precond_apply_spmv_dev": (c_int, [_P, _P, _P, _P]),
     "smm_hip_precond_values": (c_int, [_P, _P, c_size_t]),
+    "smm_hip_precond_amg_coarse_inverse": (c_int, [_P, _P, c_size_t]),
     "smm_hip_gen_poisson2d_dev": (c_int, [c_int, c_int, _P, _P, _P, _P]),
     "smm_hip_gen_stencil3d_dev": (c_int, [c_int, c_int, c_int, "T", "T", "T", _P, _P, _P, _P]),
     "smm_hip_gen_banded_dev": (c_int, [c_int, c_int, c_ulonglong, c_int, "T", _P, _P, _P, _P]),
@@ -151,6 +152,11 @@ _PLAIN = {
     "smm_hip_precond_block_bounds": (c_int, [_P, _P, c_size_t]),
     "smm_hip_precond_create_chebyshev": (c_int, [_P, c_int, c_int, c_double, c_int, c_double, c_double, POINTER(_P)]),
     "smm_hip_precond_chebyshev_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_double)]),
+    "smm_hip_precond_create_amg": (c_int, [_P, c_double, c_int, c_int, c_int, c_double, POINTER(_P)]),
+    "smm_hip_precond_amg_refresh": (c_int, [_P]),
+    "smm_hip_precond_amg_info": (c_int, [_P, POINTER(c_int), _P, _P, c_size_t, POINTER(c_double)]),
+    "smm_hip_precond_amg_level": (c_int, [_P, c_int, POINTER(_P), POINTER(_P), POINTER(_P)]),
+    "smm_hip_precond_amg_aggregates": (c_int, [_P, c_int, _P, c_size_t]),
     "smm_hip_precond_destroy": (c_int, [_P]),
     "smm_hip_precond_set_sweep": (c_int, [_P, c_int]),
     "smm_hip_precond_take_error": (c_int, [_P, _P]),

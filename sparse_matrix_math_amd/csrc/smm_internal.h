@@ -232,6 +232,7 @@ struct smm_hip_precond {
 	struct smm_precond_plan* plan = nullptr;  // launch groups of the two sweeps (smm_precond.hip)
 	struct smm_precond_block* blk = nullptr;  // BLOCK_ILU0 / BLOCK_SGS: row blocks + packed sweep records (smm_precond_block.hip)
 	struct smm_precond_cheb* cheb = nullptr;  // CHEBYSHEV: degree, bounds, coefficients and the two scratch vectors (smm_precond_cheb.hip)
+	struct smm_precond_amg* amg = nullptr;    // AMG: the levels, their operators, smoothers and vectors, the dense coarse inverse (smm_precond_amg.hip); d_values: level 0's diag[rows]
 };
 
 namespace smm {
@@ -579,5 +580,10 @@ int chebCreateTyped(const smm_hip_csr* a, int degree, int boundMode, double eigR
 template <typename T>
 int chebApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
 void chebDestroy(struct smm_precond_cheb* C);
+
+// aggregation multigrid preconditioner (smm_precond_amg.hip): one V-cycle, launches only
+template <typename T>
+int amgApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
+void amgDestroy(struct smm_precond_amg* G);
 
 }  // namespace smm

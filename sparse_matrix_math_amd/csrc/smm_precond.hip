@@ -772,6 +772,7 @@ int precondApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* don
 	}
 	if (isBlockKind(M->kind)) return blockApplyDev<T>(M, rhs, x, 0, nullptr, nullptr, doneFlag, s);
 	if (M->kind == SMM_PRECOND_CHEBYSHEV) return chebApplyDev<T>(M, rhs, x, doneFlag, s);
+	if (M->kind == SMM_PRECOND_AMG) return amgApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_JACOBI) {
 		const int grid = static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL));
 		jacobiApplyKernel<T><<<grid, TPB, 0, s>>>(n, static_cast<const T*>(M->d_values), rhs, x, doneFlag);
@@ -1082,6 +1083,7 @@ static int precondCreate(const smm_hip_csr* a, int kind, int blockRows, int leve
 	}
 	*out = nullptr;
 	if (kind == SMM_PRECOND_CHEBYSHEV) return smm_hip_precond_create_chebyshev(a, 3, SMM_CHEB_BOUND_GERSHGORIN, 30.0, 10, 0.0, 0.0, out);  // the defaults
+	if (kind == SMM_PRECOND_AMG) return smm_hip_precond_create_amg(a, 0.08, 10, 256, 2, 30.0, out);  // the defaults
 	if (kind < SMM_PRECOND_NONE || kind > SMM_PRECOND_BLOCK_SGS) {
 		setError("precond_create: unknown kind %d", kind);
 		return SMM_HIP_ERR_INVALID;
@@ -1152,6 +1154,7 @@ int smm_hip_precond_destroy(smm_hip_precond* M) {
 	if (!M) return SMM_HIP_OK;
 	blockDestroy(M->blk);
 	chebDestroy(M->cheb);
+	amgDestroy(M->amg);
 	smm_precond_plan* plan = M->plan;
 	if (plan) {
 		devFree(plan->lo.d_lvlPtr);

@@ -488,9 +488,9 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
           int* iterations, T* resnorm2) {
 	SMM_TRY(solverCheck<T>("cg", a, b, x0, x));
 	const int pcg = M != nullptr;
-	if (pcg && ((M->kind != SMM_PRECOND_IC0 && M->kind != SMM_PRECOND_CHEBYSHEV) || M->a != a)) {
-		// the reference only has the IC0 overload (ref:2414-2422); the Chebyshev polynomial is symmetric positive definite for such a matrix too
-		setError("cg: preconditioner must be an IC0 preconditioner created for this matrix");
+	if (pcg && ((M->kind != SMM_PRECOND_IC0 && M->kind != SMM_PRECOND_CHEBYSHEV && M->kind != SMM_PRECOND_AMG) || M->a != a)) {
+		// the reference only has the IC0 overload (ref:2414-2422); the Chebyshev polynomial and the multigrid V-cycle are symmetric positive definite for such a matrix too
+		setError("cg: preconditioner must be IC0 / CHEBYSHEV / AMG created for this matrix");
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int n = a->rows;
@@ -757,7 +757,7 @@ int bicgstabDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T eps
 	SMM_TRY(solverCheck<T>("bicgstab", a, b, x));
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;  // ref:2209
 	if (precondition && (M->a != a || M->kind == SMM_PRECOND_IC0)) {
-		setError("bicgstab: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV created for this matrix");
+		setError("bicgstab: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG created for this matrix");
 		return SMM_HIP_ERR_INVALID;
 	}
 	const DevApplier<T> apply{M};

@@ -328,7 +328,7 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
 	SMM_TRY(gmresCheck<T>(a, b, x, restart));
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;
 	if (precondition && (M->a != a || M->kind == SMM_PRECOND_IC0 || M->dtype != dtypeOf<T>())) {
-		setError("gmres: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV created for this matrix");
+		setError("gmres: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG created for this matrix");
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int n = a->rows;

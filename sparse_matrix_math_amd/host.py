@@ -28,7 +28,7 @@ class SolverStatus(enum.IntEnum):  # ref:2010-2014
 class SolverPreconditioner(enum.IntEnum):
     """ref:1002-1006 has NONE, SYMMETRIC_GAUS_SEIDEL (sic) and ILU0; JACOBI, IC0 and the BLOCK_ forms (ILU0 / SGS of the
     block-diagonal part of A, one wavefront per block) are additions, and so is CHEBYSHEV (a polynomial in D^-1 A: SpMVs and
-    element-wise passes only).  Values are the SMM_PRECOND_* codes of the C ABI."""
+    element-wise passes only) and AMG (smoothed-aggregation multigrid, a symmetric V-cycle).  Values are the SMM_PRECOND_* codes of the C ABI."""
     NONE = 0
     JACOBI = 1
     ILU0 = 2
@@ -37,6 +37,7 @@ class SolverPreconditioner(enum.IntEnum):
     BLOCK_ILU0 = 5
     BLOCK_SGS = 6
     CHEBYSHEV = 7
+    AMG = 8
 
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
@@ -159,7 +160,7 @@ def profile_read_waits(reset=True):
 class Preconditioner:
     """`int apply(const T* rhs, T* x) const` (ref:1173-1235).  Created by CSRMatrix.getPreconditioner."""
 
-    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None):
+    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None):
         self.matrix = matrix  # keeps the matrix alive (the reference holds a const CSRMatrix&)
         self.kind = SolverPreconditioner(kind)
         self._h = ctypes.c_void_p()
@@ -167,6 +168,9 @@ class Preconditioner:
             degree, bound, ratio, steps, lmin, lmax = chebyshev
             check(_lib.load().smm_hip_precond_create_chebyshev(matrix._h, int(degree), int(bound), float(ratio), int(steps), float(lmin), float(lmax),
                                                                ctypes.byref(self._h)))
+        elif amg is not None:  # (theta, max_levels, coarse_rows, smooth_degree, eig_ratio): AMG with chosen parameters
+            theta, max_levels, coarse_rows, smooth_degree, ratio = amg
+            check(_lib.load().smm_hip_precond_create_amg(matrix._h, float(theta), int(max_levels), int(coarse_rows), int(smooth_degree), float(ratio), ctypes.byref(self._h)))
         elif block_rows is None and level_cap is None and partition is None:
             check(_lib.load().smm_hip_precond_create(matrix._h, int(kind), ctypes.byref(self._h)))
         elif level_cap is None and partition is None:  # BLOCK_ILU0 / BLOCK_SGS with a chosen block size
@@ -233,9 +237,52 @@ class Preconditioner:
         check(_lib.load().smm_hip_precond_chebyshev_info(self._h, ctypes.byref(degree), ctypes.byref(bound), ctypes.byref(lmin), ctypes.byref(lmax)))
         return {"degree": degree.value, "bound": bound.value, "lambda_min": lmin.value, "lambda_max": lmax.value}
 
+    def amg_info(self):
+        """AMG: {levels, rows (per level), nnz (per level), operator_complexity = sum nnz(A_l) / nnz(A_0)}"""
+        levels, oc = ctypes.c_int(), ctypes.c_double()
+        rows, nnz = np.zeros(16, dtype=np.int32), np.zeros(16, dtype=np.int32)
+        check(_lib.load().smm_hip_precond_amg_info(self._h, ctypes.byref(levels), _host(rows, np.int32, "rows"), _host(nnz, np.int32, "nnz"), 16, ctypes.byref(oc)))
+        return {"levels": levels.value, "rows": [int(v) for v in rows[:levels.value]], "nnz": [int(v) for v in nnz[:levels.value]], "operator_complexity": oc.value}
+
+    def amg_level(self, level):
+        """AMG: (A_l, P_l, R_l) as CSRMatrix objects around handles this preconditioner OWNS (they live as long as it does and closing them
+        does nothing); P_l and R_l are None on the coarsest level"""
+        hs = [ctypes.c_void_p() for _ in range(3)]
+        check(_lib.load().smm_hip_precond_amg_level(self._h, int(level), *(ctypes.byref(h) for h in hs)))
+        out = []
+        for h in hs:
+            if not h:
+                out.append(None)
+                continue
+            m = CSRMatrix._adopt(h, self.matrix.dtype)
+            m._borrowed = True
+            m._keep = self
+            out.append(m)
+        return tuple(out)
+
+    def amg_aggregates(self, level):
+        """AMG: the aggregate number of every row of level `level` (the coarsest level has none: SmmHipError)"""
+        info = self.amg_info()
+        if not 0 <= int(level) < info["levels"]:
+            raise ValueError(f"level {level} of {info['levels']}")
+        agg = np.empty(info["rows"][int(level)], dtype=np.int32)
+        check(_lib.load().smm_hip_precond_amg_aggregates(self._h, int(level), _host(agg, np.int32, "agg"), len(agg)))
+        return agg
+
+    def amg_coarse_inverse(self):
+        """AMG: the dense inverse of the coarsest matrix, n_L x n_L in the matrix dtype"""
+        n = self.amg_info()["rows"][-1]
+        out = np.empty((n, n), dtype=self.matrix.dtype)
+        check(_fn("smm_hip_precond_amg_coarse_inverse", self.matrix._suf)(self._h, _host(out, self.matrix.dtype, "out"), n * n))
+        return out
+
+    def amg_refresh(self):
+        """AMG: keep every aggregate and pattern, redo the values from the matrix's present values (after a value edit).  Synchronous."""
+        check(_lib.load().smm_hip_precond_amg_refresh(self._h))
+
     def values(self):
-        """factor values: diag (JACOBI, CHEBYSHEV) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern"""
-        count = self.matrix.rows if self.kind in (SolverPreconditioner.JACOBI, SolverPreconditioner.CHEBYSHEV) else self.matrix.nnz
+        """factor values: diag (JACOBI, CHEBYSHEV, AMG) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern"""
+        count = self.matrix.rows if self.kind in (SolverPreconditioner.JACOBI, SolverPreconditioner.CHEBYSHEV, SolverPreconditioner.AMG) else self.matrix.nnz
         out = np.empty(count, dtype=self.matrix.dtype)
         check(_fn("smm_hip_precond_values", self.matrix._suf)(self._h, _host(out, self.matrix.dtype, "out"), count))
         return out
@@ -546,12 +593,21 @@ class CSRMatrix:
         check(_fn(name, self._suf)(self._h, int(op), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), int(dot_mode), _dptr(d_w1), _dptr(d_partials), _dptr(stream)))
 
     def getPreconditioner(self, kind, block_rows=None, level_cap=None, partition=None, degree=None, bound=None, eig_ratio=None, power_steps=None,
-                          lambda_min=None, lambda_max=None):
+                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None):
         """ref:1643-1651.  kind: a SolverPreconditioner or its name ("CHEBYSHEV").  block_rows / level_cap / partition: BLOCK_ kinds only;
         degree (3) / bound ("GERSHGORIN", "POWER", "USER" or a CHEB_BOUND_* code) / eig_ratio (30) / power_steps (10) / lambda_min /
-        lambda_max (USER): CHEBYSHEV only.  None = the default."""
+        lambda_max (USER): CHEBYSHEV only; theta (0.08) / max_levels (10) / coarse_rows (256) / smooth_degree (2) and eig_ratio (30): AMG only.
+        None = the default."""
         if isinstance(kind, str):
             kind = SolverPreconditioner[kind]
+        amg = (theta, max_levels, coarse_rows, smooth_degree)
+        if any(v is not None for v in amg) or (eig_ratio is not None and SolverPreconditioner(kind) == SolverPreconditioner.AMG):
+            if SolverPreconditioner(kind) != SolverPreconditioner.AMG:
+                raise ValueError("theta / max_levels / coarse_rows / smooth_degree belong to the AMG preconditioner")
+            if any(v is not None for v in (degree, bound, power_steps, lambda_min, lambda_max)):
+                raise ValueError("degree / bound / power_steps / lambda_min / lambda_max belong to the CHEBYSHEV preconditioner")
+            return Preconditioner(self, kind, amg=(0.08 if theta is None else theta, 10 if max_levels is None else max_levels, 256 if coarse_rows is None else coarse_rows,
+                                                   2 if smooth_degree is None else smooth_degree, 30.0 if eig_ratio is None else eig_ratio))
         cheb = (degree, bound, eig_ratio, power_steps, lambda_min, lambda_max)
         if any(v is not None for v in cheb):
             if SolverPreconditioner(kind) != SolverPreconditioner.CHEBYSHEV:
@@ -564,6 +620,8 @@ class CSRMatrix:
         return Preconditioner(self, kind, block_rows, level_cap, partition)
 
     def close(self):
+        if self._h and getattr(self, "_borrowed", False):  # a level of a multigrid preconditioner: that handle owns it
+            self._h = ctypes.c_void_p()
         if self._h:
             _lib.load().smm_hip_csr_destroy(self._h)
             self._h = ctypes.c_void_p()
