@@ -422,6 +422,33 @@ int smm_hip_csr_multiply_create(const smm_hip_csr* a, const smm_hip_csr* b, smm_
 int smm_hip_csr_multiply_into_f32(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b, smm_hip_stream stream);
 int smm_hip_csr_multiply_into_f64(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b, smm_hip_stream stream);
 
+/* ---- a matrix in the OTHER PRECISION, converted on the device (csrc/smm_convert.hip); additions with no counterpart in the reference -------
+ * convert_create: *out is `a`'s matrix with values of `dtype` (SMM_DTYPE_F32 or SMM_DTYPE_F64).  It owns its three device arrays -- start[]
+ *   and positions[] are copies -- and does not depend on `a`'s lifetime: an smm_hip_csr like any other (AUTO kernel choice, PATTERN analysis
+ *   on first use, edits, preconditioners, smm_hip_csr_same_pattern, transpose, product).  Nothing travels through the host.  Rectangular
+ *   matrices, empty rows, nnz == 0 and rows == 0 are legal.  Synchronises `stream` (the range flag and nnz are read before the handle is
+ *   handed out).
+ * Values: f64 -> f32 rounds to nearest, ties to even: every element carries the bits of static_cast<float>(v).  f32 -> f64 is exact.
+ *   `dtype` equal to a's own: a copy, bit for bit.  NaN converts to NaN, +-Inf to +-Inf, -0.0 keeps its sign.  UNDERFLOW IS ALLOWED: a
+ *   value too small for fp32 becomes a subnormal or a signed zero without notice.
+ * Range: a FINITE fp64 value whose fp32 rounding is not finite (|v| >= 2^128 - 2^103) returns SMM_HIP_ERR_INVALID; smm_hip_last_error()
+ *   names the first such entry (its index in values[]) and nothing is created.  Found by a word raised on the device.
+ * convert_refresh: `src`'s present values converted into `dst` (either precision on either side): the counterpart of
+ *   smm_hip_csr_transpose_refresh_* for a value edit of `src`.  dst must have src's rows, cols and nnz, else SMM_HIP_ERR_INVALID; that the
+ *   two PATTERNS agree is the caller's contract, as for multiply_into (smm_hip_csr_same_pattern tells).  On success it is a value edit of
+ *   `dst` with exactly the rules of smm_hip_csr_set_values_dev_*: what was derived from the pattern stays (no analysis on the next SpMV),
+ *   what was derived from the values follows (constant diagonals re-verified, the slots / sweep / single-launch copies, the finiteness
+ *   record; preconditioners by their own rules).  A narrowing refresh converts into scratch memory (nnz * 4 bytes), reads the range word --
+ *   it synchronises `stream` -- and only then installs the values: on a range failure `dst` keeps all its old bits (values, kernel
+ *   choice).  A widening or same-type refresh cannot fail that way and is asynchronous on `stream`.
+ *   SMM_HIP_ERR_INVALID, nothing changed: a null handle, dst == src, a shape or entry-count mismatch, a value out of fp32's range.
+ * Cost: one pass over values[], nnz (sizeof(src T) + sizeof(dst T)) bytes, 16-byte loads and stores when both arrays allow it after a
+ *   common element-wise head (arrays the library owns always do; caller-owned arrays of smm_hip_csr_create_dev_* may be element-aligned and
+ *   then take one element per lane); create adds the copy of the pattern, (rows + 1 + nnz) 8 bytes.
+ * Distributed handles are not covered. */
+int smm_hip_csr_convert_create(const smm_hip_csr* a, int dtype, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_convert_refresh(smm_hip_csr* dst, const smm_hip_csr* src, smm_hip_stream stream);
+
 /* ---- SpMV: CSRMatrix<T>::rMult / rMultAdd / rMultSub (ref:1458-1515) -------------------------------------- */
 /* out[i] = op(lhs[i], sum_k values[k]*x[positions[k]]); empty rows give op(lhs[i],0) (ref:1479-1483);
  * out may alias lhs, x must not alias out (ref:1503).  lhs is ignored for SMM_OP_ASSIGN. */
@@ -661,6 +688,49 @@ int smm_hip_gmres_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, in
                           smm_hip_stream stream, int* solver_status, int* iterations, float* resnorm2);
 int smm_hip_gmres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, int restart, const smm_hip_precond* M,
                           smm_hip_stream stream, int* solver_status, int* iterations, double* resnorm2);
+
+/* smm_hip_refine_*: MIXED-PRECISION ITERATIVE REFINEMENT -- an fp64 answer from fp32 solves; an addition, the reference has none
+ * (csrc/smm_solvers_refine.hip; the definition, line by line, is tests/refine_restatement.py).
+ * `a` is the fp64 matrix, `a32` an fp32 matrix of the same rows, cols and nnz: a's values rounded (smm_hip_csr_convert_create(a,
+ * SMM_DTYPE_F32, ...)) -- that it holds them is the caller's contract: another matrix of that shape is no error, it gives steps that the
+ * acceptance rule below rejects.  a32 == NULL: the library converts `a` for the duration of the call (M32 must be NULL then); callers
+ * solving more than once should keep an a32 -- and with it the PATTERN analysis, the preconditioner and the conversion pass itself.
+ * Semantics (x in/out):
+ *   r = b - A x (fp64);  rr = r.r;  outer = 0;  inner_total = 0
+ *   while (rr > eps*eps && outer < maxOuter) {
+ *     (m, e) = frexp(sqrt(rr))                     -- sqrt(rr) = m 2^e, m in [0.5, 1)
+ *     r32[i] = (float)(r[i] * 2^-e)                -- exact scaling, one rounding: ||r32|| is in about [0.5, 1) whatever ||b|| is
+ *     d32 = 0;  the inner solve of A32 d32 = r32 by smm_hip_cg_dev_f32 / smm_hip_bicgstab_dev_f32 / smm_hip_gmres_dev_f32 with
+ *               (maxInner, innerEps[, restart], M32) unchanged: its own -1 rule and convergence test, AUTO kernel choice, the resident
+ *               forms and the zero start apply as they do for any fp32 solve
+ *     inner_total += the inner driver's iterations
+ *     xc[i] = fma(2^e, (double)d32[i], x[i])       -- a candidate, in a vector of its own (the product is exact: one rounding)
+ *     rc = b - A xc;  rrc = rc.rc
+ *     if (!(rrc < rr)) { rejected; break }         -- a NaN included: x keeps its bits
+ *     x = xc;  r = rc;  rr = rrc;  outer++
+ *   }
+ *   status: DIVERGED if a step was rejected or rr is not finite; else SUCCESS if !(rr > eps*eps); else MAX_ITERATIONS_REACHED
+ * Guarantees: the true fp64 residual of the returned x is never larger than that of the given x.  A rejected step or a failed call leaves
+ * x bit for bit.  resnorm2 is the true ||b - A x||^2 of the returned x, computed in fp64 by the handle's SpMV and a dot product -- not a
+ * recurrence.  A start with rr <= eps*eps returns x untouched, 0 outer and 0 inner iterations, SUCCESS.  rows == 0: SUCCESS with zeros,
+ * nothing is read or written through b / x.  Whatever status the inner solve reports, the candidate is judged by its true residual alone.
+ * A negative return of the inner driver (a preconditioner of another matrix or of a kind that solver does not take, a restart out of
+ * range) is handed on and x keeps its bits.
+ * Refinement contracts only while cond(A) 2^-24 is well below 1; beyond that the first step is rejected: DIVERGED, x intact.
+ * M32: NULL, or a preconditioner created for a32 of a kind the chosen inner solver accepts.  restart is read for GMRES only.
+ * Host: rr comes to the host once per outer step (it decides the loop and e); the call synchronises `stream`.  Workspace: two fp64 and two
+ * fp32 vectors.  Per outer step beside the inner solve: two element-wise passes (12 bytes per row each) and one fp64 SpMV with its sum.
+ * SMM_HIP_ERR_INVALID: maxOuter < 0, an unknown `inner`, a null `a`, a handle of the wrong dtype, an a32 of another shape or entry count,
+ * a matrix that is not square, null vectors with rows > 0, a32 == NULL with M32 != NULL.
+ * Outputs (each may be NULL): solver_status, outer_iterations, inner_iterations (summed over the outer steps), resnorm2. */
+#define SMM_REFINE_INNER_CG 0
+#define SMM_REFINE_INNER_BICGSTAB 1
+#define SMM_REFINE_INNER_GMRES 2
+int smm_hip_refine_f64(const smm_hip_csr* a, const smm_hip_csr* a32, double* b, double* x, int inner, int maxOuter, int maxInner, double eps, float innerEps,
+                       int restart, const smm_hip_precond* M32, int* solver_status, int* outer_iterations, int* inner_iterations, double* resnorm2);
+int smm_hip_refine_dev_f64(const smm_hip_csr* a, const smm_hip_csr* a32, const double* d_b, double* d_x, int inner, int maxOuter, int maxInner, double eps,
+                           float innerEps, int restart, const smm_hip_precond* M32, smm_hip_stream stream, int* solver_status, int* outer_iterations,
+                           int* inner_iterations, double* resnorm2);
 
 /* The two dense kernels of GMRES's Gram-Schmidt on device pointers: d_V holds k columns of n elements, column i at d_V + i * ld (ld >= n;
  * what lies between n and ld is never read), 1 <= k <= SMM_GMRES_MAX_RESTART + 1.  Asynchronous on `stream`.

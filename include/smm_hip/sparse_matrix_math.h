@@ -6,7 +6,8 @@
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
 //     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::loadMatrix
-//     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto)
+//     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
+//     SMM::convert, SMM::IterativeRefinement)
 //
 // compiles against this header unchanged and runs those calls on an MI355X: same names, same argument order and meaning,
 // same return values (SolverStatus; int != 0 on failure for init / apply).  Matrix assembly (TripletMatrix, CSR arrays)
@@ -643,6 +644,40 @@ public:
 		dev = d;
 		return 0;
 	}
+	// addition: this matrix becomes `a` in THIS matrix's precision, converted on the GPU through a's device mirror (smm_hip.h "a matrix in the
+	// OTHER PRECISION": double -> float rounds to nearest even, float -> double is exact, underflow is allowed); the host arrays are filled
+	// from the device result and the built handle becomes this matrix's mirror.  Returns 0, or the SMM_HIP_* status (also in lastHipStatus())
+	// with the matrix left empty: SMM_HIP_ERR_INVALID for a finite value outside float's range.  SMM::convert<U>(a) is this call.
+	template <typename S>
+	int initConvertOf(const CSRMatrix<S>& a) noexcept {
+		release();
+		values.reset();
+		positions.reset();
+		start.reset();
+		denseRowCount = denseColCount = firstActiveStart = 0;
+		const smm_hip_csr* src = a.device();
+		if (!src) return detail::note(a.rawStart() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(smm_hip_csr_convert_create(src, std::is_same<T, float>::value ? SMM_DTYPE_F32 : SMM_DTYPE_F64, nullptr, &d)) != SMM_HIP_OK) return lastHipStatus();
+		const int rows = a.getDenseRowCount(), nnz = a.getNonZeroCount();
+		std::unique_ptr<T[]> v(new T[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> p(new int[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> s(new int[rows + 1]());
+		int abi = smm_hip_csr_get_pattern(d, s.get(), p.get());
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(d, v.get());
+		if (detail::note(abi) != SMM_HIP_OK) {
+			smm_hip_csr_destroy(d);
+			return abi;
+		}
+		values = std::move(v);
+		positions = std::move(p);
+		start = std::move(s);
+		denseRowCount = rows;
+		denseColCount = a.getDenseColCount();
+		computeFirstActive();
+		dev = d;
+		return 0;
+	}
 	// addition: this matrix becomes the product a b, built on the GPU through the two device mirrors (smm_hip.h "the PRODUCT C = A B": the
 	// structural product, columns ascending, every entry the row sum of rMult in a's stored order); the host arrays are filled from the
 	// device result and the built handle becomes this matrix's mirror.  Returns 0, or the SMM_HIP_* status (also in lastHipStatus()) with
@@ -1177,6 +1212,65 @@ inline SolverStatus BiCG(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const int rc = d ? detail::Abi<T>::bicg(d, nullptr, b, x, maxIterations, eps, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// ---- additions with no counterpart in the reference: the other precision and mixed-precision iterative refinement (smm_hip.h) ----
+// out becomes `a` with values of type U, converted on the GPU (CSRMatrix::initConvertOf); 0, or the SMM_HIP_* status with out left empty
+template <typename U, typename T>
+inline int convert(const CSRMatrix<T>& a, CSRMatrix<U>& out) noexcept {
+	return out.initConvertOf(a);
+}
+// ... returned by value: an empty matrix, with lastHipStatus() != 0, when it could not be made
+template <typename U, typename T>
+inline CSRMatrix<U> convert(const CSRMatrix<T>& a) noexcept {
+	CSRMatrix<U> out;
+	out.initConvertOf(a);
+	return out;
+}
+enum class RefinementSolver { CG = SMM_REFINE_INNER_CG, BICGSTAB = SMM_REFINE_INNER_BICGSTAB, GMRES = SMM_REFINE_INNER_GMRES };
+struct RefinementInfo {  // what smm_hip_refine_f64 reports beside the status
+	int outerIterations = 0, innerIterations = 0;
+	double residualNormSquared = 0.0;  // the true ||b - A x||^2 of the returned x, in double
+};
+// A double answer from float solves (smm_hip.h states the loop): every outer step takes the true residual in double, solves for a correction
+// in float with `inner` on a32 -- SMM::convert<float>(a), kept by callers that solve more than once -- and accepts it only if the true
+// residual falls: a rejected step (DIVERGED) or a failed call leaves x as it was.  x is the initial guess and receives the result.
+// `preconditioner`: the IDPreconditioner or one of a32's own preconditioner objects of a kind the inner solver takes.
+template <typename Preconditioner>
+inline SolverStatus IterativeRefinement(const CSRMatrix<double>& a, const CSRMatrix<float>& a32, double* b, double* x, double eps, const Preconditioner& preconditioner,
+                                        RefinementSolver inner = RefinementSolver::CG, int maxOuter = 20, int maxInner = -1, float innerEps = 1e-4f, int restart = 30,
+                                        RefinementInfo* info = nullptr) {
+	static_assert(std::is_same<Preconditioner, CSRMatrix<float>::IDPreconditioner>::value || std::is_base_of<CSRMatrix<float>::PreconditionerBase, Preconditioner>::value,
+	              "IterativeRefinement runs the library's own preconditioners only");
+	int st = 0;
+	RefinementInfo out;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_csr* d32 = a32.device();
+	const smm_hip_precond* h = preconditioner.handle();
+	constexpr bool precondition = !std::is_same<Preconditioner, CSRMatrix<float>::IDPreconditioner>::value;
+	if (d && d32 && precondition && !h) return SolverStatus::DIVERGED;  // (the preconditioner could not be built: lastHipStatus() says why)
+	const int rc = d && d32 ? smm_hip_refine_f64(d, d32, b, x, static_cast<int>(inner), maxOuter, maxInner, eps, innerEps, restart, h, &st, &out.outerIterations,
+	                                             &out.innerIterations, &out.residualNormSquared)
+	                        : SMM_HIP_ERR_NO_DEVICE;
+	if (info) *info = out;
+	return detail::toStatus(rc, st);
+}
+inline SolverStatus IterativeRefinement(const CSRMatrix<double>& a, const CSRMatrix<float>& a32, double* b, double* x, double eps,
+                                        RefinementSolver inner = RefinementSolver::CG, int maxOuter = 20, int maxInner = -1, float innerEps = 1e-4f, int restart = 30,
+                                        RefinementInfo* info = nullptr) {
+	return IterativeRefinement(a, a32, b, x, eps, CSRMatrix<float>::IDPreconditioner(), inner, maxOuter, maxInner, innerEps, restart, info);
+}
+// ... with a float matrix the library converts for the duration of the solve (a pass over the values per call: keep one when solving more than once)
+inline SolverStatus IterativeRefinement(const CSRMatrix<double>& a, double* b, double* x, double eps, RefinementSolver inner = RefinementSolver::CG, int maxOuter = 20,
+                                        int maxInner = -1, float innerEps = 1e-4f, int restart = 30, RefinementInfo* info = nullptr) {
+	int st = 0;
+	RefinementInfo out;
+	const smm_hip_csr* d = a.device();
+	const int rc = d ? smm_hip_refine_f64(d, nullptr, b, x, static_cast<int>(inner), maxOuter, maxInner, eps, innerEps, restart, nullptr, &st, &out.outerIterations,
+	                                      &out.innerIterations, &out.residualNormSquared)
+	                 : SMM_HIP_ERR_NO_DEVICE;
+	if (info) *info = out;
 	return detail::toStatus(rc, st);
 }
 

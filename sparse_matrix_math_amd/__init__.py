@@ -24,6 +24,7 @@ from .host import (  # noqa: F401
     BiCG,
     ConjugateGradientSquared,
     GMRES,
+    IterativeRefinement,
     CSRMatrix,
     Preconditioner,
     SolverPreconditioner,
@@ -35,6 +36,7 @@ from .host import (  # noqa: F401
     bicg_dev,
     cgs_dev,
     gmres_dev,
+    refine_dev,
     multi_axpy_dev,
     multi_dot_dev,
     device_info,

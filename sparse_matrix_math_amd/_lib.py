@@ -136,6 +136,12 @@ _PLAIN = {
     "smm_hip_csr_is_symmetric": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "smm_hip_csr_get_pattern": (c_int, [_P, _P, _P]),
     "smm_hip_csr_multiply_create": (c_int, [_P, _P, _P, POINTER(_P)]),
+    "smm_hip_csr_convert_create": (c_int, [_P, c_int, _P, POINTER(_P)]),
+    "smm_hip_csr_convert_refresh": (c_int, [_P, _P, _P]),
+    "smm_hip_refine_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, c_float, c_int, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                   POINTER(c_double)]),
+    "smm_hip_refine_dev_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, c_float, c_int, _P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                       POINTER(c_double)]),
     "smm_hip_assembly_create": (c_int, [c_int, c_int, c_longlong, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_create_dev": (c_int, [c_int, c_int, c_longlong, _P, _P, _P, POINTER(_P)]),
     "smm_hip_assembly_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_longlong), POINTER(c_int), POINTER(c_int)]),

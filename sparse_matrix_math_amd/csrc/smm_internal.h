@@ -337,6 +337,8 @@ int csrPatternVerdict(const smm_hip_csr* a, unsigned long long uid);
 void csrPatternRecord(const smm_hip_csr* a, unsigned long long uid, bool same);
 // Aᵀ as a handle of its own (smm_transpose.hip); may synchronise `s`
 int csrTransposeCreate(const smm_hip_csr* a, hipStream_t s, smm_hip_csr** out);
+// `a` with values of `dtype` as a handle of its own (smm_convert.hip); synchronises `s`
+int csrConvertCreate(const smm_hip_csr* a, int dtype, hipStream_t s, smm_hip_csr** out);
 // the wave-sliced value copy of the PATTERN slots kernel (smm_spmv_slots.hip).  ensurePatternSlots: build it if this launch would use it
 // (caller holds tileMutex; false: stay on the tile kernel); refreshPatternSlots: rewrite it in place after an edit (asynchronous, under
 // tileMutex); patternSlotsChosen / patternSlotsBytes: the launch's choice and its bytes, for smm_hip_csr_kernel_desc

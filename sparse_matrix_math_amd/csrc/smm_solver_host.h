@@ -64,6 +64,14 @@ struct LoopWatch {
 		poller->mailbox[0] = 0;
 		return SMM_HIP_OK;
 	}
+	// ... and one fp64 device word the same way (two of the mailbox's four ints)
+	int fetch(const double* word, double* seen) {
+		SMM_HIP_TRY(hipMemcpyAsync(&poller->mailbox[0], word, sizeof(double), hipMemcpyDeviceToHost, poller->s));
+		SMM_HIP_TRY(hipStreamSynchronize(poller->s));
+		memcpy(seen, &poller->mailbox[0], sizeof(double));
+		poller->mailbox[0] = poller->mailbox[1] = 0;
+		return SMM_HIP_OK;
+	}
 	// true: enqueue no iteration i -- the loop was seen done, or the look failed (rc)
 	bool leave(int i) {
 		if (i != next) return false;

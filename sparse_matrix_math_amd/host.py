@@ -585,6 +585,24 @@ class CSRMatrix:
         check(_fn("smm_hip_csr_multiply_into", self._suf)(self._h, A._h, B._h, _dptr(stream)))
         self._edited(stream)
 
+    # ---- the other precision, converted on the device (smm_hip.h "a matrix in the OTHER PRECISION") ----
+    def astype(self, dtype, stream=None):
+        """this matrix with values of `dtype` (float32 / float64) as a new CSRMatrix that owns its arrays: float64 -> float32 rounds to
+        nearest even (the bits of numpy's astype), float32 -> float64 is exact, the same dtype is a copy.  A finite value outside fp32's
+        range raises SmmHipError (SMM_HIP_ERR_INVALID) naming the entry; underflow is allowed.  Synchronises `stream`."""
+        dtype = np.dtype(dtype)
+        code = 0 if _suffix(dtype) == "f32" else 1  # SMM_DTYPE_F32 / SMM_DTYPE_F64
+        h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_csr_convert_create(self._h, code, _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, dtype)
+
+    def convert_refresh(self, src, stream=None):
+        """take over the present values of `src` (same rows, cols and nnz; that the patterns agree is the caller's contract), converted to
+        this matrix's dtype -- a value edit of this matrix.  SmmHipError (SMM_HIP_ERR_INVALID, nothing changed) for another shape, for
+        src being this matrix, or for a value outside fp32's range."""
+        check(_lib.load().smm_hip_csr_convert_refresh(self._h, src._h, _dptr(stream)))
+        self._edited(stream)
+
     def spmv_fused_dev(self, op, d_lhs, d_x, d_out, dot_mode, d_w1, d_partials, stream=None, finish=False):
         """SpMV with the dot products of the fresh out[] in its epilogue (dot_mode 1: out.w1; 2: out.out and out.w1).  finish=False:
         d_partials receives 2 x partials_count() per-workgroup sums; finish=True: d_partials is a finishing buffer of finish_len()
@@ -863,6 +881,39 @@ def gmres_dev(a, d_b, d_x, maxIterations, eps, restart=30, M=None, stream=None):
     check(_fn("smm_hip_gmres_dev", suf)(a._h, _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), int(restart), _mh(M), _dptr(stream),
                                         ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
     return SolverStatus(st.value), it.value, res.value
+
+
+REFINE_INNER_CG, REFINE_INNER_BICGSTAB, REFINE_INNER_GMRES = 0, 1, 2
+_REFINE_INNER = {"CG": REFINE_INNER_CG, "BICGSTAB": REFINE_INNER_BICGSTAB, "GMRES": REFINE_INNER_GMRES}
+
+
+def _refine_inner(inner):
+    return _REFINE_INNER[inner.upper()] if isinstance(inner, str) else int(inner)
+
+
+def IterativeRefinement(a, b, x, eps, inner="CG", a32=None, M=None, maxOuter=20, maxInner=-1, innerEps=1e-4, restart=30, info=None):
+    """Mixed-precision iterative refinement -- an addition (include/smm_hip.h states the loop): an fp64 answer from fp32 solves.  `a` is a
+    float64 CSRMatrix, b and x float64 vectors (x is the initial guess and receives the result); every outer step takes the true fp64
+    residual, solves for a correction in fp32 with `inner` ("CG", "BICGSTAB", "GMRES" or a REFINE_INNER_* code) on a32 and accepts it only
+    if the true residual falls.  a32: a.astype(np.float32), kept by callers that solve more than once; None converts for this call (M
+    must be None then).  M: None or a preconditioner of a32 of a kind the inner solver takes.  A rejected step or an error leaves x bit
+    for bit.  Returns SolverStatus; `info`, when a dict, receives outer_iterations, inner_iterations and resnorm2 (the true ||b - A x||^2)."""
+    st, outer, it, res = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+    check(_lib.load().smm_hip_refine_f64(a._h, _mh(a32), _host(b, np.float64, "b", a.rows), _host(x, np.float64, "x", a.rows, True), _refine_inner(inner),
+                                         int(maxOuter), int(maxInner), float(eps), float(innerEps), int(restart), _mh(M), ctypes.byref(st), ctypes.byref(outer),
+                                         ctypes.byref(it), ctypes.byref(res)))
+    if info is not None:
+        info.update(outer_iterations=outer.value, inner_iterations=it.value, resnorm2=res.value)
+    return SolverStatus(st.value)
+
+
+def refine_dev(a, d_b, d_x, eps, inner="CG", a32=None, M=None, maxOuter=20, maxInner=-1, innerEps=1e-4, restart=30, stream=None):
+    """device-pointer IterativeRefinement; returns (SolverStatus, outer_iterations, inner_iterations, resnorm2).  Synchronises `stream`."""
+    st, outer, it, res = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+    check(_lib.load().smm_hip_refine_dev_f64(a._h, _mh(a32), _dptr(d_b), _dptr(d_x), _refine_inner(inner), int(maxOuter), int(maxInner), float(eps),
+                                             float(innerEps), int(restart), _mh(M), _dptr(stream), ctypes.byref(st), ctypes.byref(outer), ctypes.byref(it),
+                                             ctypes.byref(res)))
+    return SolverStatus(st.value), outer.value, it.value, res.value
 
 
 def multi_dot_dev(n, k, d_V, ld, d_w, d_out, dtype, stream=None):
