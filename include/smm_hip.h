@@ -123,6 +123,24 @@ extern "C" {
  * definite matrices only), BiCGStab and GMRES accept it; the batched, row-partitioned and single-launch paths refuse it or are not
  * taken.  smm_hip_precond_create(a, 8, &M) means theta 0.08, max_levels 10, coarse_rows 256, smooth_degree 2, eig_ratio 30. */
 #define SMM_PRECOND_AMG 8
+/* MULTICOLOR_SGS / _ILU0 / _IC0 -- additions: the exact kind on a MULTICOLOUR REORDERING of the matrix (csrc/smm_precond_mc.hip; the
+ * definition, line by line, is tests/multicolor_restatement.py).
+ *   colours = smm_hip_csr_color(a) (or the caller's, smm_hip_precond_create_multicolor); perm = the rows sorted by colour, stably (the
+ *   original index ascends inside a colour); B = P A Pᵀ (smm_hip_csr_permute_create); for ILU0 / IC0 the factor of B;
+ *   M^-1 r = Pᵀ sweeps_B(P r), sweeps_B being the two sweeps of SGS / ILU0 / IC0 on B -- bit for bit the sequential sweeps on B.
+ * Rows of one colour do not reference each other, so either sweep has exactly `ncolors` dependent levels (smm_hip_precond_info reports
+ * them) -- a handful on a grid, where the natural order has hundreds.  The price is convergence: a solver typically needs somewhat more
+ * iterations than with the exact kind in the natural order (INTEGRATION.md "Multicolour ordering").
+ * Accepted wherever the exact kind is (smm_hip_bicgstab_*, smm_hip_gmres_*, the refinement driver's inner solves: MULTICOLOR_SGS and
+ * MULTICOLOR_ILU0); smm_hip_cg_* takes MULTICOLOR_IC0 and MULTICOLOR_SGS, both symmetric positive definite when A is.  Batched and
+ * row-partitioned solvers and smm_hip_precond_apply_spmv_* refuse the kinds (SMM_HIP_ERR_INVALID).
+ * Errors of create: those of the exact kind (SMM_HIP_ERR_PRECOND for a missing / tiny diagonal, an empty row, a failed pivot;
+ * SMM_HIP_ERR_INVALID for a matrix that is not square).  The handle owns B and the vector the sweeps work on, so ONE HANDLE MUST NOT BE
+ * APPLIED FROM TWO STREAMS AT ONCE.  It is a SNAPSHOT, MULTICOLOR_SGS included: it does not follow a value edit of `a` -- call
+ * smm_hip_precond_multicolor_refresh.  smm_hip_precond_values_* returns the ILU0 / IC0 factor on B's pattern (nnz values). */
+#define SMM_PRECOND_MULTICOLOR_SGS 9
+#define SMM_PRECOND_MULTICOLOR_ILU0 10
+#define SMM_PRECOND_MULTICOLOR_IC0 11
 
 #define SMM_DTYPE_F32 0
 #define SMM_DTYPE_F64 1
@@ -386,6 +404,35 @@ int smm_hip_csr_transpose_create(const smm_hip_csr* a, smm_hip_stream stream, sm
 int smm_hip_csr_transpose_refresh_f32(smm_hip_csr* at, const smm_hip_csr* a, smm_hip_stream stream);
 int smm_hip_csr_transpose_refresh_f64(smm_hip_csr* at, const smm_hip_csr* a, smm_hip_stream stream);
 int smm_hip_csr_is_symmetric(const smm_hip_csr* a, int* pattern_symmetric, int* values_symmetric);
+
+/* ---- a COLOURING of the rows and the SYMMETRIC PERMUTATION B = P A Pᵀ of a matrix, on the device -- additions (csrc/smm_color.hip) ----
+ * smm_hip_csr_color*: colours (0-based) of the rows of a square matrix such that no stored entry (i, j), i != j, joins two rows of one
+ *   colour; explicit zeros count.  Rows i != j are adjacent when (i, j) or (j, i) is stored (the in-neighbours come from the library's
+ *   transpose when the pattern is not symmetric).  THE RULE, fixed so that the result does not depend on scheduling:
+ *     key(i) = splitmix64(i + 1), splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)   (64-bit wrapping arithmetic; a bijection, so no two keys tie);
+ *     the rows are taken in DESCENDING key order and each gets the smallest colour none of its already coloured neighbours holds.
+ *   On the device this runs in rounds (every uncoloured row whose key beats all its uncoloured neighbours' is coloured); the host reads
+ *   one count per round.  The number of colours is bounded by `rows` alone (a dense block needs as many colours as it has rows).
+ *   count must be `rows`; *ncolors = the largest colour + 1 (0 for a matrix without rows).  SMM_HIP_ERR_INVALID: a matrix that is not
+ *   square, a wrong count, a null output, a column outside the matrix.  The host form is a set-up call (it drains the device once);
+ *   the _dev form writes d_colors on `stream` and synchronises it.
+ * smm_hip_csr_permute_create*: b = P A Pᵀ as an ordinary handle that owns its arrays: perm[i] is the row of `a` that becomes row i,
+ *   b(i, j) = a(perm[i], perm[j]); columns ascend inside each row; values are carried bit for bit.  perm (host) / d_perm (device) holds
+ *   `count` == rows entries.  The check that perm is a permutation of 0 .. rows - 1 runs on the device; a value out of range or named
+ *   twice, a wrong count or a matrix that is not square give SMM_HIP_ERR_INVALID with nothing created (*out = NULL).  Synchronises
+ *   `stream`.  Set-up: one radix sort of the entries over the bits 2 x rows need; the entry map (4 bytes per entry) and the permutation
+ *   stay with b.
+ * smm_hip_csr_permute_refresh_*: b's values from the present values of `a` in one gather pass, asynchronous on `stream` -- a value edit
+ *   of b, in the manner of smm_hip_csr_transpose_refresh_*.  `a` may be the source or any matrix with its pattern (checked on the device
+ *   the first time, remembered afterwards).  SMM_HIP_ERR_INVALID, nothing changed: b was not made by smm_hip_csr_permute_create, another
+ *   shape, entry count, pattern or dtype. */
+int smm_hip_csr_color(const smm_hip_csr* a, int* colors, size_t count, int* ncolors);
+int smm_hip_csr_color_dev(const smm_hip_csr* a, int* d_colors, size_t count, smm_hip_stream stream, int* ncolors);
+int smm_hip_csr_permute_create(const smm_hip_csr* a, const int* perm, size_t count, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_permute_create_dev(const smm_hip_csr* a, const int* d_perm, size_t count, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_permute_refresh_f32(smm_hip_csr* b, const smm_hip_csr* a, smm_hip_stream stream);
+int smm_hip_csr_permute_refresh_f64(smm_hip_csr* b, const smm_hip_csr* a, smm_hip_stream stream);
 int smm_hip_csr_get_pattern(const smm_hip_csr* m, int* start, int* positions);
 
 /* ---- the PRODUCT C = A B of two matrices, built on the device (csrc/smm_spgemm.hip); additions with no counterpart in the reference --------
@@ -673,7 +720,8 @@ int smm_hip_cgs_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, in
  *   status: DIVERGED if a column was dropped or rr is not finite; else SUCCESS if rr <= eps*eps; else MAX_ITERATIONS_REACHED
  * A solve that starts with rr <= eps*eps (an exact x included) returns x untouched, 0 iterations, SUCCESS.  rows == 0: SUCCESS, 0
  * iterations, nothing is read or written through b / x.  A matrix whose stored values are all zero: DIVERGED after 1 step, x untouched.
- * M: NULL, or any kind smm_hip_bicgstab_* accepts (JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG created for `a`).
+ * M: NULL, or any kind smm_hip_bicgstab_* accepts (JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG / MULTICOLOR_SGS /
+ *   MULTICOLOR_ILU0 created for `a`).
  * Memory: (restart + 1) * rows elements for the basis (leading dimension rounded up to 64) plus two vectors.
  * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one solve give the same bits.
  * SMM_HIP_ERR_INVALID: restart outside 1 .. SMM_GMRES_MAX_RESTART, a null or dtype-mismatched matrix, a matrix that is not square,
@@ -839,6 +887,23 @@ int smm_hip_precond_amg_level(const smm_hip_precond* M, int level, smm_hip_csr**
 int smm_hip_precond_amg_aggregates(const smm_hip_precond* M, int level, int* agg, size_t count);
 int smm_hip_precond_amg_coarse_inverse_f32(const smm_hip_precond* M, float* out, size_t count);
 int smm_hip_precond_amg_coarse_inverse_f64(const smm_hip_precond* M, double* out, size_t count);
+/* The multicolour kinds (SMM_PRECOND_MULTICOLOR_*, defined above) with a colouring of the caller's.  base_kind: SMM_PRECOND_SGS, _ILU0 or
+ * _IC0.  colors: NULL (count ignored) for smm_hip_csr_color's, or `count` == rows colours on the HOST, each in [0, rows); it is checked
+ * on the device -- a stored entry (i, j), i != j, with colors[i] == colors[j] gives SMM_HIP_ERR_INVALID.  Colours nobody holds are
+ * allowed (they are empty levels); ncolors = the largest colour + 1.  smm_hip_precond_create(a, SMM_PRECOND_MULTICOLOR_*, ...) passes NULL.
+ * multicolor_refresh: keeps the colouring, the permutation and B's pattern; B's values are gathered from the present values of `a`
+ *   and the factor is recomputed: afterwards the handle equals a newly created one bit for bit.  Synchronous.  Errors as create's; on
+ *   an error the handle must not be applied any more (destroy it).
+ * multicolor_info: ncolors, and the first `count` (<= ncolors + 1) of the row bounds of the colours in B (bounds[0] = 0,
+ *   bounds[ncolors] = rows); either pointer may be NULL.
+ * multicolor_perm: the first `count` (<= rows) entries of perm[] (new row i is row perm[i] of `a`).
+ * multicolor_matrix: B as a BORROWED handle owned by M (do not destroy it; it dies with M); it may be read (smm_hip_csr_get_pattern /
+ *   _get_values_*). */
+int smm_hip_precond_create_multicolor(const smm_hip_csr* a, int base_kind, const int* colors, size_t count, smm_hip_precond** out);
+int smm_hip_precond_multicolor_refresh(smm_hip_precond* M);
+int smm_hip_precond_multicolor_info(const smm_hip_precond* M, int* ncolors, int* bounds, size_t count);
+int smm_hip_precond_multicolor_perm(const smm_hip_precond* M, int* perm, size_t count);
+int smm_hip_precond_multicolor_matrix(const smm_hip_precond* M, smm_hip_csr** b);
 int smm_hip_precond_destroy(smm_hip_precond* M);
 int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower, int* levels_upper);
 /* How the two triangular sweeps of SGS / ILU0 / IC0 run (same numbers bit for bit either way):

@@ -81,6 +81,7 @@ struct Abi<float> {
 	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f32(m, nullptr); }
 	static int update(smm_hip_csr* m, int n, const int* r, const int* c, const float* v) { return smm_hip_csr_update_entries_f32(m, n, r, c, v, SMM_UPDATE_SET, nullptr); }
 	static int getValues(const smm_hip_csr* m, float* v) { return smm_hip_csr_get_values_f32(m, v); }
+	static int permuteRefresh(smm_hip_csr* b, const smm_hip_csr* a) { return smm_hip_csr_permute_refresh_f32(b, a, nullptr); }
 	static int assembled(const smm_hip_assembly* p, const float* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f32(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const float* v, int mode) { return smm_hip_assembly_refill_f32(p, m, v, mode); }
 	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f32(c, a, b, nullptr); }
@@ -115,6 +116,7 @@ struct Abi<double> {
 	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f64(m, nullptr); }
 	static int update(smm_hip_csr* m, int n, const int* r, const int* c, const double* v) { return smm_hip_csr_update_entries_f64(m, n, r, c, v, SMM_UPDATE_SET, nullptr); }
 	static int getValues(const smm_hip_csr* m, double* v) { return smm_hip_csr_get_values_f64(m, v); }
+	static int permuteRefresh(smm_hip_csr* b, const smm_hip_csr* a) { return smm_hip_csr_permute_refresh_f64(b, a, nullptr); }
 	static int assembled(const smm_hip_assembly* p, const double* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f64(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const double* v, int mode) { return smm_hip_assembly_refill_f64(p, m, v, mode); }
 	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f64(c, a, b, nullptr); }
@@ -523,6 +525,36 @@ public:
 		}
 	};
 
+	// addition: SGS / ILU0 / IC0 of the matrix renumbered colour by colour (smm_hip.h, SMM_PRECOND_MULTICOLOR_*): either sweep has as many
+	// dependent levels as there are colours.  Base: SGSPreconditioner, ILU0Preconditioner or IC0Preconditioner; usable wherever Base is, and
+	// MulticolorPreconditioner<SGSPreconditioner> in ConjugateGradient as well.  A snapshot of the matrix's values: refresh() follows a value
+	// edit with the colouring kept.  One object serves one stream at a time (it owns the vector its sweeps work on).
+	template <typename Base>
+	class MulticolorPreconditioner : public PreconditionerBase {
+		static_assert(std::is_same<Base, SGSPreconditioner>::value || std::is_same<Base, ILU0Preconditioner>::value || std::is_same<Base, IC0Preconditioner>::value,
+		              "MulticolorPreconditioner<Base>: Base is SGSPreconditioner, ILU0Preconditioner or IC0Preconditioner");
+		static constexpr int kindOf() noexcept {
+			return std::is_same<Base, SGSPreconditioner>::value ? SMM_PRECOND_MULTICOLOR_SGS
+			       : std::is_same<Base, ILU0Preconditioner>::value ? SMM_PRECOND_MULTICOLOR_ILU0 : SMM_PRECOND_MULTICOLOR_IC0;
+		}
+
+	public:
+		MulticolorPreconditioner(const CSRMatrix& m) noexcept : PreconditionerBase(m, kindOf()) {}
+		MulticolorPreconditioner(MulticolorPreconditioner&&) noexcept = default;
+		int validate() noexcept { return this->init(); }
+		// the number of colours and the first `count` of the ncolors + 1 row bounds (either may be null); non-zero when it could not be made
+		int info(int* ncolors, int* bounds, size_t count) const noexcept {
+			if (this->init()) return 1;
+			return detail::note(smm_hip_precond_multicolor_info(this->h, ncolors, bounds, count)) == SMM_HIP_OK ? 0 : 1;
+		}
+		// the permuted values and the factor again from the matrix's present values, colouring kept
+		int refresh() noexcept {
+			if (this->init()) return 1;
+			if (!this->m->device()) return 1;  // (queued entry edits reach the device first)
+			return detail::note(smm_hip_precond_multicolor_refresh(this->h)) == SMM_HIP_OK ? 0 : 1;
+		}
+	};
+
 	CSRMatrix() noexcept = default;
 	CSRMatrix(const TripletMatrix<T>& triplet) noexcept { init(triplet); }
 	CSRMatrix(const CSRMatrix&) = delete;
@@ -643,6 +675,49 @@ public:
 		computeFirstActive();
 		dev = d;
 		return 0;
+	}
+	// addition: this matrix becomes P a Pᵀ, built on the GPU through a's device mirror (smm_hip.h "the SYMMETRIC PERMUTATION": row i is a's row
+	// perm[i], entry (i, j) its (perm[i], perm[j]); columns ascend, values bit for bit); perm holds a's row count of entries.  The host arrays
+	// are filled from the device result and the built handle becomes this matrix's mirror.  Returns 0, or the SMM_HIP_* status (also in
+	// lastHipStatus()) with the matrix left empty: SMM_HIP_ERR_INVALID when perm is no permutation.  SMM::permute(a, perm, out) is this call.
+	int initPermuteOf(const CSRMatrix& a, const int* perm) noexcept {
+		release();
+		values.reset();
+		positions.reset();
+		start.reset();
+		denseRowCount = denseColCount = firstActiveStart = 0;
+		const smm_hip_csr* src = a.device();
+		if (!src) return detail::note(a.start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(smm_hip_csr_permute_create(src, perm, static_cast<size_t>(a.denseRowCount), nullptr, &d)) != SMM_HIP_OK) return lastHipStatus();
+		const int rows = a.denseRowCount, nnz = a.getNonZeroCount();
+		std::unique_ptr<T[]> v(new T[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> p(new int[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> s(new int[rows + 1]());
+		int abi = smm_hip_csr_get_pattern(d, s.get(), p.get());
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(d, v.get());
+		if (detail::note(abi) != SMM_HIP_OK) {
+			smm_hip_csr_destroy(d);
+			return abi;
+		}
+		values = std::move(v);
+		positions = std::move(p);
+		start = std::move(s);
+		denseRowCount = rows;
+		denseColCount = a.denseColCount;
+		computeFirstActive();
+		dev = d;
+		return 0;
+	}
+	// addition: a matrix made by initPermuteOf takes over the present values of `a` (its source, or a matrix with that pattern) in one gather
+	// pass on the GPU; the host values follow.  Returns 0, or the SMM_HIP_* status with this matrix unchanged.  SMM::permuteRefresh is this call.
+	int permuteRefresh(const CSRMatrix& a) noexcept {
+		const smm_hip_csr* src = a.device();
+		if (!src || !device()) return detail::note(lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		int abi = detail::Abi<T>::permuteRefresh(dev, src);
+		if (abi == SMM_HIP_OK) abi = smm_hip_stream_synchronize(nullptr);
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(dev, values.get());
+		return detail::note(abi);
 	}
 	// addition: this matrix becomes `a` in THIS matrix's precision, converted on the GPU through a's device mirror (smm_hip.h "a matrix in the
 	// OTHER PRECISION": double -> float rounds to nearest even, float -> double is exact, underflow is allowed); the host arrays are filled
@@ -1068,6 +1143,28 @@ inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, c
 	return detail::toStatus(rc, st);
 }
 
+// addition: ... and with IC0 / SGS of the multicolour reordering (both symmetric positive definite for such a matrix)
+template <typename T, typename Base>
+using MulticolorPreconditioner = typename CSRMatrix<T>::template MulticolorPreconditioner<Base>;
+template <typename T>
+inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
+                                      const typename CSRMatrix<T>::template MulticolorPreconditioner<typename CSRMatrix<T>::IC0Preconditioner>& M) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = M.handle();
+	const int rc = d && h ? detail::Abi<T>::cg(d, b, x0, x, maxIterations, eps, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+template <typename T>
+inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
+                                      const typename CSRMatrix<T>::template MulticolorPreconditioner<typename CSRMatrix<T>::SGSPreconditioner>& M) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = M.handle();
+	const int rc = d && h ? detail::Abi<T>::cg(d, b, x0, x, maxIterations, eps, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
 // ref:2191-2283.  CSRMatrix<T>'s own preconditioner classes live on the GPU and run inside the device-resident loop.  ANY other type
 // with the reference's `int apply(const T* rhs, T* x) const` (ref:2199, 2218, 2235, 2251) is accepted as well: the loop then runs
 // its SpMVs, reductions and updates on the device and calls the functor on the host around two PCIe copies per apply (the slow
@@ -1185,6 +1282,24 @@ inline bool isSymmetric(const CSRMatrix<T>& a) noexcept {
 	int pattern = 0, vals = 0;
 	if (!d || detail::note(smm_hip_csr_is_symmetric(d, &pattern, &vals)) != SMM_HIP_OK) return false;
 	return pattern != 0 && vals != 0;
+}
+// ---- additions: colouring and symmetric permutation (smm_hip.h "a COLOURING of the rows and the SYMMETRIC PERMUTATION") ----
+// colors[rows] (0-based) such that no stored off-diagonal entry joins two rows of one colour; *ncolors = the largest colour + 1.  0, or the
+// SMM_HIP_* status
+template <typename T>
+inline int color(const CSRMatrix<T>& a, int* colors, int* ncolors) noexcept {
+	const smm_hip_csr* d = a.device();
+	return detail::note(d ? smm_hip_csr_color(d, colors, static_cast<size_t>(a.getDenseRowCount()), ncolors) : SMM_HIP_ERR_NO_DEVICE);
+}
+// out becomes P a Pᵀ (CSRMatrix::initPermuteOf): row i of out is a's row perm[i]; 0, or the SMM_HIP_* status with out left empty
+template <typename T>
+inline int permute(const CSRMatrix<T>& a, const int* perm, CSRMatrix<T>& out) noexcept {
+	return out.initPermuteOf(a, perm);
+}
+// b, made by SMM::permute, takes over the present values of a (CSRMatrix::permuteRefresh); 0, or the SMM_HIP_* status with b unchanged
+template <typename T>
+inline int permuteRefresh(CSRMatrix<T>& b, const CSRMatrix<T>& a) noexcept {
+	return b.permuteRefresh(a);
 }
 // out becomes the product a b, built on the GPU (CSRMatrix::initProductOf); 0, or the SMM_HIP_* status with out left empty
 template <typename T>

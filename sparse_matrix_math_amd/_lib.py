@@ -101,6 +101,7 @@ _TYPED = {
     "smm_hip_assembly_refill": (c_int, [_P, _P, _P, c_int]),
     "smm_hip_assembly_refill_dev": (c_int, [_P, _P, _P, c_int, _P]),
     "smm_hip_csr_transpose_refresh": (c_int, [_P, _P, _P]),
+    "smm_hip_csr_permute_refresh": (c_int, [_P, _P, _P]),
     "smm_hip_csr_multiply_into": (c_int, [_P, _P, _P, _P]),
 }
 
@@ -135,6 +136,10 @@ _PLAIN = {
     "smm_hip_csr_transpose_create": (c_int, [_P, _P, POINTER(_P)]),
     "smm_hip_csr_is_symmetric": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "smm_hip_csr_get_pattern": (c_int, [_P, _P, _P]),
+    "smm_hip_csr_color": (c_int, [_P, _P, c_size_t, POINTER(c_int)]),
+    "smm_hip_csr_color_dev": (c_int, [_P, _P, c_size_t, _P, POINTER(c_int)]),
+    "smm_hip_csr_permute_create": (c_int, [_P, _P, c_size_t, _P, POINTER(_P)]),
+    "smm_hip_csr_permute_create_dev": (c_int, [_P, _P, c_size_t, _P, POINTER(_P)]),
     "smm_hip_csr_multiply_create": (c_int, [_P, _P, _P, POINTER(_P)]),
     "smm_hip_csr_convert_create": (c_int, [_P, c_int, _P, POINTER(_P)]),
     "smm_hip_csr_convert_refresh": (c_int, [_P, _P, _P]),
@@ -163,6 +168,11 @@ _PLAIN = {
     "smm_hip_precond_amg_info": (c_int, [_P, POINTER(c_int), _P, _P, c_size_t, POINTER(c_double)]),
     "smm_hip_precond_amg_level": (c_int, [_P, c_int, POINTER(_P), POINTER(_P), POINTER(_P)]),
     "smm_hip_precond_amg_aggregates": (c_int, [_P, c_int, _P, c_size_t]),
+    "smm_hip_precond_create_multicolor": (c_int, [_P, c_int, _P, c_size_t, POINTER(_P)]),
+    "smm_hip_precond_multicolor_refresh": (c_int, [_P]),
+    "smm_hip_precond_multicolor_info": (c_int, [_P, POINTER(c_int), _P, c_size_t]),
+    "smm_hip_precond_multicolor_perm": (c_int, [_P, _P, c_size_t]),
+    "smm_hip_precond_multicolor_matrix": (c_int, [_P, POINTER(_P)]),
     "smm_hip_precond_destroy": (c_int, [_P]),
     "smm_hip_precond_set_sweep": (c_int, [_P, c_int]),
     "smm_hip_precond_take_error": (c_int, [_P, _P]),

@@ -214,6 +214,10 @@ struct smm_hip_csr {
 	// uid of the handle it was built from (0: not a transpose); smm_hip_csr_transpose_refresh_* gathers through d_tperm
 	int* d_tperm = nullptr;
 	unsigned long long transposeOf = 0;
+	// a symmetric permutation built by smm_hip_csr_permute_create (smm_color.hip): d_tperm is its entry map in the same sense, d_pperm the
+	// row permutation (rows entries, owned: new row i is the source's row d_pperm[i]) and permuteOf the uid of the source (0: not a permutation)
+	int* d_pperm = nullptr;
+	unsigned long long permuteOf = 0;
 	// whether values[] holds finite numbers only: -1 not known, 1 yes, 0 an Inf or a NaN.  Found by one pass over values[] the first time a
 	// Krylov driver starts from x0 = 0 (zeroStart, smm_solver_host.h); back to -1 at every value edit (valuesEdited, smm_csr_update.hip)
 	mutable std::atomic<int> values_finite{-1};
@@ -232,6 +236,7 @@ struct smm_hip_precond {
 	struct smm_precond_plan* plan = nullptr;  // launch groups of the two sweeps (smm_precond.hip)
 	struct smm_precond_block* blk = nullptr;  // BLOCK_ILU0 / BLOCK_SGS: row blocks + packed sweep records (smm_precond_block.hip)
 	struct smm_precond_cheb* cheb = nullptr;  // CHEBYSHEV: degree, bounds, coefficients and the two scratch vectors (smm_precond_cheb.hip)
+	struct smm_precond_mc* mc = nullptr;      // MULTICOLOR_*: the colouring, the permuted matrix B and the colour-by-colour sweeps (smm_precond_mc.hip); d_values: the factor on B's pattern
 	struct smm_precond_amg* amg = nullptr;    // AMG: the levels, their operators, smoothers and vectors, the dense coarse inverse (smm_precond_amg.hip); d_values: level 0's diag[rows]
 };
 
@@ -587,5 +592,26 @@ void chebDestroy(struct smm_precond_cheb* C);
 template <typename T>
 int amgApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
 void amgDestroy(struct smm_precond_amg* G);
+
+// graph colouring and symmetric permutation of a handle (smm_color.hip); include/smm_hip.h states both rules
+// colours of the rows of a square, ready matrix into d_colors[rows] (device), *ncolors on the host; synchronises `s`
+int csrColor(const smm_hip_csr* a, hipStream_t s, int* d_colors, int* ncolors);
+// P A Pᵀ as a handle of its own, d_perm[rows] on the device; SMM_HIP_ERR_INVALID (nothing created) when it is no permutation; synchronises `s`
+int csrPermuteCreate(const smm_hip_csr* a, const int* d_perm, hipStream_t s, smm_hip_csr** out);
+int csrPermuteRefresh(smm_hip_csr* b, const smm_hip_csr* a, int dtype, hipStream_t s);
+
+// multicolour SGS / ILU0 / IC0 (smm_precond_mc.hip)
+// the structural checks of the exact kinds (smm_precond.hip): info[0] != 0 on an empty row, a missing diagonal or (checkMagnitude) |d| < 1e-5
+template <typename T>
+int precondRowCheck(const smm_hip_csr* a, bool checkMagnitude, int* info, hipStream_t s);
+inline bool isMulticolorKind(int kind) { return kind >= SMM_PRECOND_MULTICOLOR_SGS && kind <= SMM_PRECOND_MULTICOLOR_IC0; }
+template <typename T>
+int mcApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
+void mcDestroy(struct smm_precond_mc* C);
+void mcLevels(const struct smm_precond_mc* C, int* lo, int* up);
+// the device factorisations of smm_precond.hip on a matrix whose dependency levels are the `nb` row ranges bounds[0 .. nb] (rows of one
+// range do not reference each other): f[nnz] receives the ILU0 / IC0 factor; *herr as createTyped reads it
+template <typename T>
+int factorByRanges(const smm_hip_csr* b, int kind, const std::vector<int>& bounds, T* f, int* herr, hipStream_t s);
 
 }  // namespace smm

@@ -773,6 +773,7 @@ int precondApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* don
 	if (isBlockKind(M->kind)) return blockApplyDev<T>(M, rhs, x, 0, nullptr, nullptr, doneFlag, s);
 	if (M->kind == SMM_PRECOND_CHEBYSHEV) return chebApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_AMG) return amgApplyDev<T>(M, rhs, x, doneFlag, s);
+	if (isMulticolorKind(M->kind)) return mcApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_JACOBI) {
 		const int grid = static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL));
 		jacobiApplyKernel<T><<<grid, TPB, 0, s>>>(n, static_cast<const T*>(M->d_values), rhs, x, doneFlag);
@@ -905,6 +906,48 @@ static int factorDevice(const smm_hip_csr* a, const SweepPlan& plan, const int* 
 	return SMM_HIP_OK;
 }
 
+// the structural checks of createTyped for another unit: info[0] != 0 on an empty row, a missing diagonal or (checkMagnitude) |d| < 1e-5;
+// info[1] = the longest row
+template <typename T>
+int precondRowCheck(const smm_hip_csr* a, bool checkMagnitude, int* info, hipStream_t s) {
+	info[0] = info[1] = 0;
+	DevBuf<int> dinfo;
+	SMM_TRY(dinfo.alloc(2));
+	SMM_HIP_TRY(hipMemsetAsync(dinfo, 0, 2 * sizeof(int), s));
+	if (a->rows) {
+		const int grid = static_cast<int>(std::min<long long>((a->rows + TPB - 1LL) / TPB, numCUs() * 8LL));
+		rowCheckKernel<T><<<grid, TPB, 0, s>>>(a->rows, a->d_start, a->d_positions, static_cast<const T*>(a->d_values), checkMagnitude ? 1 : 0, dinfo);
+	}
+	SMM_HIP_TRY(hipMemcpyAsync(info, dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+	SMM_HIP_TRY(hipStreamSynchronize(s));
+	return SMM_HIP_OK;
+}
+template int precondRowCheck<float>(const smm_hip_csr*, bool, int*, hipStream_t);
+template int precondRowCheck<double>(const smm_hip_csr*, bool, int*, hipStream_t);
+
+// the factorisation kernels on a matrix whose levels are given as row ranges in the natural order (the multicolour kinds: a colour is a level)
+template <typename T>
+int factorByRanges(const smm_hip_csr* b, int kind, const std::vector<int>& bounds, T* f, int* herr, hipStream_t s) {
+	const int n = b->rows;
+	DevBuf<int> order, lvl;
+	SMM_TRY(order.alloc(std::max(1, n)));
+	SMM_TRY(lvl.alloc(bounds.size()));
+	if (n) iotaKernel<<<static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL)), TPB, 0, s>>>(n, order);
+	SMM_HIP_TRY(hipMemcpyAsync(lvl, bounds.data(), bounds.size() * sizeof(int), hipMemcpyHostToDevice, s));
+	SweepPlan plan;
+	plan.d_lvlPtr = lvl;
+	planGroups(bounds, plan.groups);
+	const size_t nnz = static_cast<size_t>(b->nnz);
+	if (kind == SMM_PRECOND_ILU0) {
+		if (nnz) SMM_HIP_TRY(hipMemcpyAsync(f, b->d_values, nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
+		return factorDevice<T, SMM_PRECOND_ILU0>(b, plan, order, bounds, f, herr, s);
+	}
+	if (nnz) SMM_HIP_TRY(hipMemsetAsync(f, 0, nnz * sizeof(T), s));
+	return factorDevice<T, SMM_PRECOND_IC0>(b, plan, order, bounds, f, herr, s);
+}
+template int factorByRanges<float>(const smm_hip_csr*, int, const std::vector<int>&, float*, int*, hipStream_t);
+template int factorByRanges<double>(const smm_hip_csr*, int, const std::vector<int>&, double*, int*, hipStream_t);
+
 template <typename T>
 static int createTyped(const smm_hip_csr* a, int kind, smm_hip_precond* M) {
 	hipStream_t s = libStream();
@@ -1017,6 +1060,10 @@ static int applySpmvDev(const smm_hip_precond* M, const T* v, T* x, hipStream_t 
 		setError("precond_apply_spmv: null handle / dtype mismatch");
 		return SMM_HIP_ERR_INVALID;
 	}
+	if (isMulticolorKind(M->kind)) {
+		setError("precond_apply_spmv: the multicolour kinds have no fused form (run the SpMV, then smm_hip_precond_apply_*)");
+		return SMM_HIP_ERR_INVALID;
+	}
 	const int n = M->a->rows;
 	if (n > 0 && (!v || !x || v == x)) {
 		setError("precond_apply_spmv: null vector or v aliases x");
@@ -1084,6 +1131,7 @@ static int precondCreate(const smm_hip_csr* a, int kind, int blockRows, int leve
 	*out = nullptr;
 	if (kind == SMM_PRECOND_CHEBYSHEV) return smm_hip_precond_create_chebyshev(a, 3, SMM_CHEB_BOUND_GERSHGORIN, 30.0, 10, 0.0, 0.0, out);  // the defaults
 	if (kind == SMM_PRECOND_AMG) return smm_hip_precond_create_amg(a, 0.08, 10, 256, 2, 30.0, out);  // the defaults
+	if (isMulticolorKind(kind)) return smm_hip_precond_create_multicolor(a, kind == SMM_PRECOND_MULTICOLOR_SGS ? SMM_PRECOND_SGS : kind == SMM_PRECOND_MULTICOLOR_ILU0 ? SMM_PRECOND_ILU0 : SMM_PRECOND_IC0, nullptr, 0, out);  // the library's own colouring
 	if (kind < SMM_PRECOND_NONE || kind > SMM_PRECOND_BLOCK_SGS) {
 		setError("precond_create: unknown kind %d", kind);
 		return SMM_HIP_ERR_INVALID;
@@ -1155,6 +1203,7 @@ int smm_hip_precond_destroy(smm_hip_precond* M) {
 	blockDestroy(M->blk);
 	chebDestroy(M->cheb);
 	amgDestroy(M->amg);
+	mcDestroy(M->mc);
 	smm_precond_plan* plan = M->plan;
 	if (plan) {
 		devFree(plan->lo.d_lvlPtr);
@@ -1180,6 +1229,10 @@ int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower,
 	if (kind) *kind = M->kind;
 	if (M->blk) {  // block kinds: the deepest block
 		blockLevels(M->blk, levels_lower, levels_upper);
+		return SMM_HIP_OK;
+	}
+	if (M->mc) {  // multicolour kinds: a colour is a level of either sweep
+		mcLevels(M->mc, levels_lower, levels_upper);
 		return SMM_HIP_OK;
 	}
 	if (levels_lower) *levels_lower = M->lvl_ptr_lo.empty() ? 0 : static_cast<int>(M->lvl_ptr_lo.size()) - 1;

@@ -754,6 +754,7 @@ int smm_hip_csr_destroy(smm_hip_csr* m) {
 	devFree(m->d_pat_masks8);
 	devFree(m->d_pat_rowblocks);
 	devFree(m->d_tperm);
+	devFree(m->d_pperm);
 	delete m;
 	return SMM_HIP_OK;
 }

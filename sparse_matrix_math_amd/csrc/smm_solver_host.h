@@ -43,17 +43,23 @@ struct SyncOnExit {
 // The host's look at a loop's device `done` word (DonePoller: no stall of the queue).  One poller per host thread, reused by every solve
 // of that thread.  The word is first asked for at iteration `first`, then `every` iterations later each time; every == 0: after
 // max(4, min(64, i / 4)) iterations -- kernels enqueued past the end of the loop are no-ops, so a late answer costs launches, not results.
+// `planned` (every == 0 only): the iterations the loop will enqueue at most.  A look with fewer than MIN_SAVING of them left is not made: it
+// could spare a few no-op launches at best, and whether its answer -- or an earlier look's, which is read at the same place -- has arrived
+// by then depends on how far the GPU has got, so a short loop (a handful of planned iterations) would enqueue a number of launches that
+// varies from run to run.  Without it such a loop enqueues every planned iteration, every time.
 struct LoopWatch {
+	static constexpr int MIN_SAVING = 4;
 	DonePoller* poller = nullptr;
 	const int* flag = nullptr;
-	int next = 0, every = 0;
+	int next = 0, every = 0, planned = 0x7fffffff;
 	int rc = SMM_HIP_OK;  // what a failed look returned: loopFinish hands it on
-	int begin(hipStream_t s, const int* doneFlag, int first, int fixedInterval = 0) {
+	int begin(hipStream_t s, const int* doneFlag, int first, int fixedInterval = 0, int plannedIterations = 0x7fffffff) {
 		static thread_local DonePoller threadPoller;
 		poller = &threadPoller;
 		flag = doneFlag;
 		next = first;
 		every = fixedInterval;
+		planned = plannedIterations;
 		return poller->init(s);
 	}
 	// one device word on the host, through the poller's pinned mailbox; synchronises the stream.  Between begin() and the first leave().
@@ -75,6 +81,7 @@ struct LoopWatch {
 	// true: enqueue no iteration i -- the loop was seen done, or the look failed (rc)
 	bool leave(int i) {
 		if (i != next) return false;
+		if (every == 0 && planned - i < MIN_SAVING) return false;  // (next stays: no later look either)
 		const int seen = poller->post(flag);
 		if (seen < 0) rc = seen;
 		next = i + (every ? every : std::max(4, std::min(64, i / 4)));

@@ -488,9 +488,12 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
           int* iterations, T* resnorm2) {
 	SMM_TRY(solverCheck<T>("cg", a, b, x0, x));
 	const int pcg = M != nullptr;
-	if (pcg && ((M->kind != SMM_PRECOND_IC0 && M->kind != SMM_PRECOND_CHEBYSHEV && M->kind != SMM_PRECOND_AMG) || M->a != a)) {
+	if (pcg && ((M->kind != SMM_PRECOND_IC0 && M->kind != SMM_PRECOND_CHEBYSHEV && M->kind != SMM_PRECOND_AMG && M->kind != SMM_PRECOND_MULTICOLOR_IC0 &&
+	             M->kind != SMM_PRECOND_MULTICOLOR_SGS) ||
+	            M->a != a)) {
 		// the reference only has the IC0 overload (ref:2414-2422); the Chebyshev polynomial and the multigrid V-cycle are symmetric positive definite for such a matrix too
-		setError("cg: preconditioner must be IC0 / CHEBYSHEV / AMG created for this matrix");
+		// (MULTICOLOR_IC0 and MULTICOLOR_SGS are IC0 / SGS of P A Pᵀ carried back by P: symmetric positive definite when A is)
+		setError("cg: preconditioner must be IC0 / CHEBYSHEV / AMG / MULTICOLOR_IC0 / MULTICOLOR_SGS created for this matrix");
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int n = a->rows;
@@ -532,7 +535,7 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
 
 	const int* doneFlag = &sc.p->done;
 	LoopWatch watch;
-	SMM_TRY(watch.begin(s, doneFlag, 0));
+	SMM_TRY(watch.begin(s, doneFlag, 0, 0, maxIterations == -1 ? n : maxIterations));
 	bool fromZero = false;  // x0 = 0 and finite values: r = b without an SpMV (zeroStart, smm_solver_host.h)
 	SMM_TRY(zeroStart<T>(a, x0, watch, s, &fromZero));
 	if (!fromZero) SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x0, r, 0, nullptr, nullptr, nullptr, s));  // r = b - A x0, ref:2337
@@ -679,7 +682,7 @@ static int bicgstabLoop(const smm_hip_csr* a, const T* b, T* x, int maxIteration
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);  // do { } while: the body always runs once (ref:2232, 2277)
 	LoopWatch watch;
-	SMM_TRY(watch.begin(s, doneFlag, 1));
+	SMM_TRY(watch.begin(s, doneFlag, 1, 0, planned));
 	bool fromZero = false;  // x = 0 and finite values: b - A x is b, no SpMV is launched for it (zeroStart, smm_solver_host.h)
 	SMM_TRY(zeroStart<T>(a, x, watch, s, &fromZero));
 	if (precondition) {
@@ -756,8 +759,8 @@ int bicgstabDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T eps
                 int* iterations, T* resnorm) {
 	SMM_TRY(solverCheck<T>("bicgstab", a, b, x));
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;  // ref:2209
-	if (precondition && (M->a != a || M->kind == SMM_PRECOND_IC0)) {
-		setError("bicgstab: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG created for this matrix");
+	if (precondition && (M->a != a || M->kind == SMM_PRECOND_IC0 || M->kind == SMM_PRECOND_MULTICOLOR_IC0)) {
+		setError("bicgstab: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG / MULTICOLOR_SGS / MULTICOLOR_ILU0 created for this matrix");
 		return SMM_HIP_ERR_INVALID;
 	}
 	const DevApplier<T> apply{M};
@@ -821,7 +824,7 @@ int bicgsymmetricDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, 
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);
 	LoopWatch watch;
-	SMM_TRY(watch.begin(s, doneFlag, 1));
+	SMM_TRY(watch.begin(s, doneFlag, 1, 0, planned));
 	for (int i = 0; i < planned && !watch.leave(i); ++i) {
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, p, parts, doneFlag, s));  // ref:2048-2049
 		bsymAlphaScal<T><<<1, TPB, 0, s>>>(parts, sc, eps);

@@ -172,7 +172,7 @@ static int bicgDev(const smm_hip_csr* a, const smm_hip_csr* at, const T* b, T* x
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);
 	LoopWatch watch;
-	SMM_TRY(watch.begin(s, doneFlag, 1));
+	SMM_TRY(watch.begin(s, doneFlag, 1, 0, planned));
 	for (int i = 0; i < planned && !watch.leave(i); ++i) {
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, p, ap, 1, pt, partsD, doneFlag, s));  // ref:2048-2049
 		SMM_TRY(launchSpmv<T>(at, SMM_OP_ASSIGN, nullptr, pt, atp, 0, nullptr, nullptr, doneFlag, s));

@@ -103,7 +103,7 @@ static int cgsDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T e
 	const int* doneFlag = &sc.p->done;
 	const int planned = std::max(1, maxIterations);  // do { } while: the body always runs once (ref:2131, 2172)
 	LoopWatch watch;
-	SMM_TRY(watch.begin(s, doneFlag, 1));
+	SMM_TRY(watch.begin(s, doneFlag, 1, 0, planned));
 	bool fromZero = false;  // x = 0 and finite values: r = b without an SpMV (zeroStart, smm_solver_host.h)
 	SMM_TRY(zeroStart<T>(a, x, watch, s, &fromZero));
 	if (fromZero) {

@@ -28,7 +28,8 @@ class SolverStatus(enum.IntEnum):  # ref:2010-2014
 class SolverPreconditioner(enum.IntEnum):
     """ref:1002-1006 has NONE, SYMMETRIC_GAUS_SEIDEL (sic) and ILU0; JACOBI, IC0 and the BLOCK_ forms (ILU0 / SGS of the
     block-diagonal part of A, one wavefront per block) are additions, and so is CHEBYSHEV (a polynomial in D^-1 A: SpMVs and
-    element-wise passes only) and AMG (smoothed-aggregation multigrid, a symmetric V-cycle).  Values are the SMM_PRECOND_* codes of the C ABI."""
+    element-wise passes only), AMG (smoothed-aggregation multigrid, a symmetric V-cycle) and the MULTICOLOR_ forms (SGS / ILU0 / IC0 of the
+    matrix renumbered colour by colour: a handful of dependent levels per sweep).  Values are the SMM_PRECOND_* codes of the C ABI."""
     NONE = 0
     JACOBI = 1
     ILU0 = 2
@@ -38,6 +39,9 @@ class SolverPreconditioner(enum.IntEnum):
     BLOCK_SGS = 6
     CHEBYSHEV = 7
     AMG = 8
+    MULTICOLOR_SGS = 9
+    MULTICOLOR_ILU0 = 10
+    MULTICOLOR_IC0 = 11
 
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
@@ -45,6 +49,8 @@ MAX_RHS = 8  # SMM_HIP_MAX_RHS: the most right-hand sides one block holds
 SPMV_AUTO, SPMV_VECTOR, SPMV_STREAM, SPMV_PATTERN = 0, 1, 2, 3
 SWEEP_AUTO, SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD = 0, 1, 2, 3
 CHEB_BOUND_GERSHGORIN, CHEB_BOUND_POWER, CHEB_BOUND_USER = 0, 1, 2  # SMM_CHEB_BOUND_*: where a Chebyshev preconditioner's bounds come from
+_MULTICOLOR_BASE = {SolverPreconditioner.MULTICOLOR_SGS: SolverPreconditioner.SYMMETRIC_GAUS_SEIDEL, SolverPreconditioner.MULTICOLOR_ILU0: SolverPreconditioner.ILU0,
+                    SolverPreconditioner.MULTICOLOR_IC0: SolverPreconditioner.IC0}
 _CHEB_BOUNDS = {"GERSHGORIN": CHEB_BOUND_GERSHGORIN, "POWER": CHEB_BOUND_POWER, "USER": CHEB_BOUND_USER}
 
 _SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
@@ -160,7 +166,7 @@ def profile_read_waits(reset=True):
 class Preconditioner:
     """`int apply(const T* rhs, T* x) const` (ref:1173-1235).  Created by CSRMatrix.getPreconditioner."""
 
-    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None):
+    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None, colors=None):
         self.matrix = matrix  # keeps the matrix alive (the reference holds a const CSRMatrix&)
         self.kind = SolverPreconditioner(kind)
         self._h = ctypes.c_void_p()
@@ -171,6 +177,10 @@ class Preconditioner:
         elif amg is not None:  # (theta, max_levels, coarse_rows, smooth_degree, eig_ratio): AMG with chosen parameters
             theta, max_levels, coarse_rows, smooth_degree, ratio = amg
             check(_lib.load().smm_hip_precond_create_amg(matrix._h, float(theta), int(max_levels), int(coarse_rows), int(smooth_degree), float(ratio), ctypes.byref(self._h)))
+        elif colors is not None:  # MULTICOLOR_ kinds with the caller's colouring (one colour per row)
+            colors = np.ascontiguousarray(colors, dtype=np.int32)
+            check(_lib.load().smm_hip_precond_create_multicolor(matrix._h, int(_MULTICOLOR_BASE[self.kind]), _host(colors, np.int32, "colors"), colors.size,
+                                                                ctypes.byref(self._h)))
         elif block_rows is None and level_cap is None and partition is None:
             check(_lib.load().smm_hip_precond_create(matrix._h, int(kind), ctypes.byref(self._h)))
         elif level_cap is None and partition is None:  # BLOCK_ILU0 / BLOCK_SGS with a chosen block size
@@ -280,8 +290,36 @@ class Preconditioner:
         """AMG: keep every aggregate and pattern, redo the values from the matrix's present values (after a value edit).  Synchronous."""
         check(_lib.load().smm_hip_precond_amg_refresh(self._h))
 
+    def multicolor_info(self):
+        """MULTICOLOR_ kinds: (ncolors, the ncolors + 1 row bounds of the colours in the permuted matrix)"""
+        n = ctypes.c_int()
+        check(_lib.load().smm_hip_precond_multicolor_info(self._h, ctypes.byref(n), ctypes.c_void_p(0), 0))
+        bounds = np.zeros(n.value + 1, dtype=np.int32)
+        check(_lib.load().smm_hip_precond_multicolor_info(self._h, ctypes.byref(n), _host(bounds, np.int32, "bounds"), bounds.size))
+        return n.value, bounds
+
+    def multicolor_perm(self):
+        """MULTICOLOR_ kinds: perm[] -- row i of the permuted matrix is row perm[i] of the matrix"""
+        perm = np.zeros(self.matrix.rows, dtype=np.int32)
+        check(_lib.load().smm_hip_precond_multicolor_perm(self._h, _host(perm, np.int32, "perm"), perm.size))
+        return perm
+
+    def multicolor_matrix(self):
+        """MULTICOLOR_ kinds: B = P A Pᵀ as a CSRMatrix around a handle this preconditioner OWNS (closing it does nothing)"""
+        h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_precond_multicolor_matrix(self._h, ctypes.byref(h)))
+        m = CSRMatrix._adopt(h, self.matrix.dtype)
+        m._borrowed = True
+        m._keep = self
+        return m
+
+    def multicolor_refresh(self):
+        """MULTICOLOR_ kinds: keep the colouring, redo the permuted values and the factor from the matrix's present values.  Synchronous."""
+        check(_lib.load().smm_hip_precond_multicolor_refresh(self._h))
+
     def values(self):
-        """factor values: diag (JACOBI, CHEBYSHEV, AMG) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern"""
+        """factor values: diag (JACOBI, CHEBYSHEV, AMG) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern (MULTICOLOR_ILU0 / _IC0: on
+        the permuted matrix's pattern)"""
         count = self.matrix.rows if self.kind in (SolverPreconditioner.JACOBI, SolverPreconditioner.CHEBYSHEV, SolverPreconditioner.AMG) else self.matrix.nnz
         out = np.empty(count, dtype=self.matrix.dtype)
         check(_fn("smm_hip_precond_values", self.matrix._suf)(self._h, _host(out, self.matrix.dtype, "out"), count))
@@ -549,6 +587,41 @@ class CSRMatrix:
         check(_fn("smm_hip_csr_transpose_refresh", self._suf)(self._h, A._h, _dptr(stream)))
         self._edited(stream)
 
+    # ---- colouring and symmetric permutation, on the device (smm_hip.h "a COLOURING of the rows and the SYMMETRIC PERMUTATION") ----
+    def color(self):
+        """(colors[rows], ncolors): greedy colouring of the adjacency graph in descending splitmix64(row + 1) order; no stored
+        off-diagonal entry joins two rows of one colour"""
+        colors = np.zeros(self.rows, dtype=np.int32)
+        n = ctypes.c_int()
+        check(_lib.load().smm_hip_csr_color(self._h, _host(colors, np.int32, "colors"), colors.size, ctypes.byref(n)))
+        return colors, n.value
+
+    def color_dev(self, d_colors, stream=None):
+        """the same into an int32 device array of `rows` entries; returns ncolors"""
+        n = ctypes.c_int()
+        check(_lib.load().smm_hip_csr_color_dev(self._h, _dptr(d_colors), self.rows, _dptr(stream), ctypes.byref(n)))
+        return n.value
+
+    def permute(self, perm, stream=None):
+        """P A Pᵀ as a new CSRMatrix that owns its arrays: row i is this matrix's row perm[i], entry (i, j) its (perm[i], perm[j]); columns
+        ascend, values bit for bit.  SmmHipError (SMM_HIP_ERR_INVALID) when perm is not a permutation of 0 .. rows - 1."""
+        perm = np.ascontiguousarray(perm, dtype=np.int32)
+        h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_csr_permute_create(self._h, _host(perm, np.int32, "perm"), perm.size, _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, self.dtype)
+
+    def permute_dev(self, d_perm, count, stream=None):
+        """permute() with perm[] in an int32 device array of `count` entries"""
+        h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_csr_permute_create_dev(self._h, _dptr(d_perm), int(count), _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, self.dtype)
+
+    def permute_refresh(self, A, stream=None):
+        """called on a matrix made by permute(): take over the present values of A (the source, or a matrix with its pattern) in one
+        gather pass -- a value edit of this matrix.  SmmHipError (SMM_HIP_ERR_INVALID, nothing changed) for any other pair."""
+        check(_fn("smm_hip_csr_permute_refresh", self._suf)(self._h, A._h, _dptr(stream)))
+        self._edited(stream)
+
     def isSymmetric(self):
         """(pattern, values): the pattern equals the transpose's; in addition every value equals its mirror image by IEEE == (a NaN never
         does).  (False, False) for a matrix that is not square."""
@@ -611,13 +684,17 @@ class CSRMatrix:
         check(_fn(name, self._suf)(self._h, int(op), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), int(dot_mode), _dptr(d_w1), _dptr(d_partials), _dptr(stream)))
 
     def getPreconditioner(self, kind, block_rows=None, level_cap=None, partition=None, degree=None, bound=None, eig_ratio=None, power_steps=None,
-                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None):
+                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None, colors=None):
         """ref:1643-1651.  kind: a SolverPreconditioner or its name ("CHEBYSHEV").  block_rows / level_cap / partition: BLOCK_ kinds only;
         degree (3) / bound ("GERSHGORIN", "POWER", "USER" or a CHEB_BOUND_* code) / eig_ratio (30) / power_steps (10) / lambda_min /
         lambda_max (USER): CHEBYSHEV only; theta (0.08) / max_levels (10) / coarse_rows (256) / smooth_degree (2) and eig_ratio (30): AMG only.
-        None = the default."""
+        colors (one per row; None = CSRMatrix.color's): MULTICOLOR_ kinds only.  None = the default."""
         if isinstance(kind, str):
             kind = SolverPreconditioner[kind]
+        if colors is not None:
+            if SolverPreconditioner(kind) not in _MULTICOLOR_BASE:
+                raise ValueError("colors belongs to the MULTICOLOR_ preconditioners")
+            return Preconditioner(self, kind, colors=colors)
         amg = (theta, max_levels, coarse_rows, smooth_degree)
         if any(v is not None for v in amg) or (eig_ratio is not None and SolverPreconditioner(kind) == SolverPreconditioner.AMG):
             if SolverPreconditioner(kind) != SolverPreconditioner.AMG:
@@ -638,7 +715,7 @@ class CSRMatrix:
         return Preconditioner(self, kind, block_rows, level_cap, partition)
 
     def close(self):
-        if self._h and getattr(self, "_borrowed", False):  # a level of a multigrid preconditioner: that handle owns it
+        if self._h and getattr(self, "_borrowed", False):  # a level of a multigrid preconditioner, a multicolour one's matrix: that handle owns it
             self._h = ctypes.c_void_p()
         if self._h:
             _lib.load().smm_hip_csr_destroy(self._h)
