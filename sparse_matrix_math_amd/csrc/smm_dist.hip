@@ -2229,10 +2229,7 @@ static int distBicgstab(smm_hip_dist_csr* D, const T* b, T* x, int maxIterations
 	// block-Jacobi by rank: M is this rank's preconditioner of its diagonal block A_loc, applied without
 	// communication; with one rank it is the single-GPU preconditioner, with more a weaker one (iteration counts differ)
 	const bool pre = M != nullptr && M->kind != SMM_PRECOND_NONE;
-	if (pre && (M->a != D->aLoc || M->kind == SMM_PRECOND_IC0 || M->kind == SMM_PRECOND_CHEBYSHEV || M->kind == SMM_PRECOND_AMG || isMulticolorKind(M->kind))) {
-		setError("dist_bicgstab: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS of the local diagonal block (smm_hip_dist_csr_local_block)");
-		return SMM_HIP_ERR_INVALID;
-	}
+	SMM_TRY(precondAdmissible("dist_bicgstab", M, D->aLoc, SOLVER_DIST_LOCAL));
 	D->reducedInKernel = false;  // (a call that failed between an SpMV and its reduction point must not leave the mark behind)
 	D->totalsFinal = false;
 	maxIterations = std::min(maxIterations, D->nGlobal);  // ref:2200

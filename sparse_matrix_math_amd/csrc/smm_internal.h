@@ -229,11 +229,8 @@ struct smm_hip_precond {
 	const smm_hip_csr* a = nullptr;
 	void* d_values = nullptr;  // JACOBI, CHEBYSHEV: diag[rows]; ILU0 / IC0: factor values on A's pattern [nnz]; SGS: null (uses A)
 	size_t n_values = 0;
-	// level schedules of the lower / upper triangular sweeps: rows sorted by level
-	int* d_order_lo = nullptr;
-	int* d_order_up = nullptr;
-	std::vector<int> lvl_ptr_lo, lvl_ptr_up;  // host: level l covers order[lvl_ptr[l] .. lvl_ptr[l+1])
-	struct smm_precond_plan* plan = nullptr;  // launch groups of the two sweeps (smm_precond.hip)
+	// one pointer per family that keeps state of its own
+	struct smm_precond_plan* plan = nullptr;  // SGS / ILU0 / IC0: the level schedules of the two sweeps, the synchronisation-free sweeps' scratch (smm_precond.hip)
 	struct smm_precond_block* blk = nullptr;  // BLOCK_ILU0 / BLOCK_SGS: row blocks + packed sweep records (smm_precond_block.hip)
 	struct smm_precond_cheb* cheb = nullptr;  // CHEBYSHEV: degree, bounds, coefficients and the two scratch vectors (smm_precond_cheb.hip)
 	struct smm_precond_mc* mc = nullptr;      // MULTICOLOR_*: the colouring, the permuted matrix B and the colour-by-colour sweeps (smm_precond_mc.hip); d_values: the factor on B's pattern
@@ -566,8 +563,66 @@ int precondApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* don
 // sticky error of the synchronisation-free sweeps applied on `s`; synchronises `s`.  M may be null.
 int precondTakeError(const smm_hip_precond* M, hipStream_t s);
 
+void planDestroy(struct smm_precond_plan* plan);  // (smm_precond.hip)
+
+// ---------------------------------------------------------------------------------------------------------
+// The preconditioner kinds describe themselves: one row per SMM_PRECOND_* value, indexed by it.  `name` is how messages print the kind;
+// the flags are what the solvers' entry checks ask (precondAdmissible).
+// ---------------------------------------------------------------------------------------------------------
+struct PrecondKind {
+	const char* name;
+	bool cg;         // symmetric positive definite when A is: ConjugateGradient takes it
+	bool cholesky;   // a Cholesky-type factor (needs a symmetric matrix): the loops for general matrices refuse it
+	bool distLocal;  // usable as a rank's local preconditioner of the row-partitioned BiCGStab
+	bool batched;    // usable by the loops for several right-hand sides
+	bool block, multicolor;
+};
+constexpr PrecondKind PRECOND_KINDS[] = {
+    //  name               cg     cholesky distLocal batched block  multicolor
+    {"NONE",            false, false, true,  true,  false, false},
+    {"JACOBI",          false, false, true,  true,  false, false},
+    {"ILU0",            false, false, true,  false, false, false},
+    {"SGS",             false, false, true,  false, false, false},
+    {"IC0",             true,  true,  false, false, false, false},
+    {"BLOCK_ILU0",      false, false, true,  false, true,  false},
+    {"BLOCK_SGS",       false, false, true,  false, true,  false},
+    {"CHEBYSHEV",       true,  false, false, false, false, false},
+    {"AMG",             true,  false, false, false, false, false},
+    {"MULTICOLOR_SGS",  true,  false, false, false, false, true},
+    {"MULTICOLOR_ILU0", false, false, false, false, false, true},
+    {"MULTICOLOR_IC0",  true,  true,  false, false, false, true},
+};
+constexpr int N_PRECOND_KINDS = static_cast<int>(sizeof(PRECOND_KINDS) / sizeof(PRECOND_KINDS[0]));
+static_assert(SMM_PRECOND_NONE == 0 && SMM_PRECOND_JACOBI == 1 && SMM_PRECOND_ILU0 == 2 && SMM_PRECOND_SGS == 3 && SMM_PRECOND_IC0 == 4 && SMM_PRECOND_BLOCK_ILU0 == 5 &&
+                  SMM_PRECOND_BLOCK_SGS == 6 && SMM_PRECOND_CHEBYSHEV == 7 && SMM_PRECOND_AMG == 8 && SMM_PRECOND_MULTICOLOR_SGS == 9 &&
+                  SMM_PRECOND_MULTICOLOR_ILU0 == 10 && SMM_PRECOND_MULTICOLOR_IC0 == 11 && N_PRECOND_KINDS == 12,
+              "PRECOND_KINDS is indexed by the SMM_PRECOND_* values");
+inline bool isBlockKind(int kind) { return kind >= 0 && kind < N_PRECOND_KINDS && PRECOND_KINDS[kind].block; }
+inline bool isMulticolorKind(int kind) { return kind >= 0 && kind < N_PRECOND_KINDS && PRECOND_KINDS[kind].multicolor; }
+
+// Which kinds a class of solver takes.  CG takes a handle of kind NONE for what it is (and refuses it); to the other classes such a handle
+// means "no preconditioner", like a null M.
+enum SolverClass { SOLVER_CG, SOLVER_GENERAL, SOLVER_DIST_LOCAL, SOLVER_BATCHED };
+inline bool precondKindTaken(int kind, SolverClass c) {
+	if (kind < 0 || kind >= N_PRECOND_KINDS) return false;
+	const PrecondKind& k = PRECOND_KINDS[kind];
+	return c == SOLVER_CG ? k.cg : c == SOLVER_GENERAL ? !k.cholesky : c == SOLVER_DIST_LOCAL ? k.distLocal : k.batched;
+}
+// The entry check of a solver `who` on matrix `a`: M (may be null) is of a kind the class takes and was created for `a`.  The message names
+// the kinds the class does take, from the table.
+inline int precondAdmissible(const char* who, const smm_hip_precond* M, const smm_hip_csr* a, SolverClass c) {
+	if (!M || (c != SOLVER_CG && M->kind == SMM_PRECOND_NONE)) return SMM_HIP_OK;
+	if (precondKindTaken(M->kind, c) && M->a == a) return SMM_HIP_OK;
+	std::string names;
+	for (int kind = SMM_PRECOND_NONE + 1; kind < N_PRECOND_KINDS; ++kind) {
+		if (precondKindTaken(kind, c)) names += std::string(names.empty() ? "" : " / ") + PRECOND_KINDS[kind].name;
+	}
+	setError("%s: preconditioner must be %s %s", who, names.c_str(),
+	         c == SOLVER_DIST_LOCAL ? "of the local diagonal block (smm_hip_dist_csr_local_block)" : "created for this matrix");
+	return SMM_HIP_ERR_INVALID;
+}
+
 // block preconditioners (smm_precond_block.hip)
-inline bool isBlockKind(int kind) { return kind == SMM_PRECOND_BLOCK_ILU0 || kind == SMM_PRECOND_BLOCK_SGS; }
 template <typename T>
 int blockCreateTyped(const smm_hip_csr* a, int kind, int blockRows, int levelCap, int partition, smm_hip_precond* M);
 // x = M^-1 rhs; dotMode / w1 / partials: dot products of x fused into the epilogue, as in launchSpmv (partials: 2 * NPART elements)
@@ -601,17 +656,18 @@ int csrPermuteCreate(const smm_hip_csr* a, const int* d_perm, hipStream_t s, smm
 int csrPermuteRefresh(smm_hip_csr* b, const smm_hip_csr* a, int dtype, hipStream_t s);
 
 // multicolour SGS / ILU0 / IC0 (smm_precond_mc.hip)
-// the structural checks of the exact kinds (smm_precond.hip): info[0] != 0 on an empty row, a missing diagonal or (checkMagnitude) |d| < 1e-5
+// the structural checks of the exact kinds (smm_precond.hip): SMM_HIP_ERR_PRECOND (message set) on an empty row, a missing diagonal or
+// (checkMagnitude) |d| < 1e-5; *longestRow may be null
 template <typename T>
-int precondRowCheck(const smm_hip_csr* a, bool checkMagnitude, int* info, hipStream_t s);
-inline bool isMulticolorKind(int kind) { return kind >= SMM_PRECOND_MULTICOLOR_SGS && kind <= SMM_PRECOND_MULTICOLOR_IC0; }
+int precondRowCheck(const smm_hip_csr* a, bool checkMagnitude, int* longestRow, hipStream_t s);
 template <typename T>
 int mcApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
 void mcDestroy(struct smm_precond_mc* C);
 void mcLevels(const struct smm_precond_mc* C, int* lo, int* up);
-// the device factorisations of smm_precond.hip on a matrix whose dependency levels are the `nb` row ranges bounds[0 .. nb] (rows of one
-// range do not reference each other): f[nnz] receives the ILU0 / IC0 factor; *herr as createTyped reads it
+// the device factorisations of smm_precond.hip on a matrix whose dependency levels are the row ranges of `ranges` (smm_trisweep.h; rows of
+// one range do not reference each other): f[nnz] receives the ILU0 / IC0 factor; a failed factorisation returns SMM_HIP_ERR_PRECOND, message set
+struct LevelSchedule;
 template <typename T>
-int factorByRanges(const smm_hip_csr* b, int kind, const std::vector<int>& bounds, T* f, int* herr, hipStream_t s);
+int factorByRanges(const smm_hip_csr* b, int kind, const LevelSchedule& ranges, T* f, hipStream_t s);
 
 }  // namespace smm

@@ -6,8 +6,9 @@
 // level depend only on rows of earlier levels), rows are sorted by level, and a sweep runs level by level with
 // one lane per row.  Inside a row the entries are visited in exactly the reference's order, and a row only
 // starts when all rows it reads are final, so the result is bit-identical to the sequential sweep.
-// Runs of small levels are executed by a single 1024-lane workgroup with a workgroup barrier between levels
-// (no launch per level); a large level gets a multi-workgroup launch of its own.
+// The arithmetic of a row, the lane-per-row walker, the level / chain kernels and their launch plan are smm_trisweep.h's (shared with the
+// multicolour kinds); this unit keeps what is its own: the synchronisation-free sweeps (one launch per sweep), the level analysis, the
+// factor kernels, Jacobi and the C entry points.
 //
 // Set-up (structural checks, the level sets, the ILU0 / IC0 factorisation) runs on the device as well, at create time: the level sets
 // by a synchronisation-free propagation kernel, the factorisation level by level with one wavefront per row.
@@ -17,115 +18,11 @@
 #include <map>
 #include <memory>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "smm_device.h"
-#include "smm_internal.h"
+#include "smm_trisweep.h"
 
 namespace smm {
 
-constexpr int TPB = 256;
-constexpr int SMALL_LEVEL = 1024;  // levels up to this many rows are chained inside one workgroup
-
-enum SweepMode { SGS_LO = 0, SGS_UP = 1, ILU_LO = 2, ILU_UP = 3, IC_LO = 4, IC_UP = 5 };
-
-template <typename T, int MODE>
-__device__ __forceinline__ void solveRow(int row, const int* __restrict__ start, const int* __restrict__ positions, const T* __restrict__ vals,
-                                         const T* __restrict__ rhs, T* x) {
-	const int b = start[row];
-	const int e = start[row + 1];
-	if (MODE == SGS_LO) {  // ref:1673-1695
-		int k = b;
-		T lhs = rhs[row];
-		int col = positions[k];
-		T value = vals[k];
-		while (col < row) {
-			lhs = smmFma(-value, x[col], lhs);
-			++k;
-			col = positions[k];
-			value = vals[k];
-		}
-		x[row] = lhs / value;
-	} else if (MODE == SGS_UP) {  // ref:1698-1711
-		int k = e - 1;
-		int col = positions[k];
-		T value = vals[k];
-		T lhs = T(0);
-		while (col > row) {
-			lhs = smmFma(value, x[col], lhs);
-			--k;
-			col = positions[k];
-			value = vals[k];
-		}
-		x[row] = x[row] - lhs / value;
-	} else if (MODE == ILU_LO) {  // L y = rhs, unit diagonal
-		T sum = rhs[row];
-		for (int k = b; k < e && positions[k] < row; ++k) {
-			sum = smmFma(-vals[k], x[positions[k]], sum);
-		}
-		x[row] = sum;
-	} else if (MODE == ILU_UP) {  // U x = y
-		T sum = x[row];
-		int k = e - 1;
-		for (; k >= b && positions[k] > row; --k) {
-			sum = smmFma(-vals[k], x[positions[k]], sum);
-		}
-		x[row] = sum / vals[k];
-	} else if (MODE == IC_LO) {  // ref:1806-1819: sum -= l*x (plain multiply and subtract)
-		T sum = rhs[row];
-		int k = b;
-		int col = positions[k];
-		while (col < row && k < e) {
-			const T prod = vals[k] * x[col];
-			sum = sum - prod;
-			++k;
-			col = positions[k];
-		}
-		x[row] = sum / vals[k];
-	} else {  // IC_UP, ref:1822-1835
-		T sum = x[row];
-		int k = e - 1;
-		int col = positions[k];
-		while (col > row && k >= b) {
-			const T prod = vals[k] * x[col];
-			sum = sum - prod;
-			--k;
-			col = positions[k];
-		}
-		x[row] = sum / vals[k];
-	}
-}
-
-// one large level: rows order[begin .. begin+count)
-template <typename T, int MODE>
-__global__ __launch_bounds__(TPB) void sweepLevelKernel(const int* __restrict__ order, int begin, int count, const int* __restrict__ start,
-                                                        const int* __restrict__ positions, const T* __restrict__ vals, const T* __restrict__ rhs,
-                                                        T* x, const int* __restrict__ doneFlag) {
-	if (doneFlag && *doneFlag) return;
-	const int i = blockIdx.x * TPB + threadIdx.x;
-	if (i < count) {
-		solveRow<T, MODE>(order[begin + i], start, positions, vals, rhs, x);
-	}
-}
-
-// a run of small levels [l0, l1) inside one workgroup; lvlPtr is the device copy of the level pointers
-template <typename T, int MODE>
-__global__ __launch_bounds__(SMALL_LEVEL) void sweepChainKernel(const int* __restrict__ order, const int* __restrict__ lvlPtr, int l0, int l1,
-                                                                const int* __restrict__ start, const int* __restrict__ positions,
-                                                                const T* __restrict__ vals, const T* __restrict__ rhs, T* x,
-                                                                const int* __restrict__ doneFlag) {
-	if (doneFlag && *doneFlag) return;
-	for (int l = l0; l < l1; ++l) {
-		const int begin = lvlPtr[l];
-		const int count = lvlPtr[l + 1] - begin;
-		if (static_cast<int>(threadIdx.x) < count) {
-			solveRow<T, MODE>(order[begin + threadIdx.x], start, positions, vals, rhs, x);
-		}
-		// rows of the next level read x[] written above by other wavefronts of this workgroup
-		__threadfence_block();
-		__syncthreads();
-	}
-}
+constexpr int TPB = SWEEP_TPB;
 
 // ---------------------------------------------------------------------------------------------------------
 // Synchronisation-free sweeps: ONE launch per sweep instead of one per level.
@@ -140,7 +37,7 @@ __global__ __launch_bounds__(SMALL_LEVEL) void sweepChainKernel(const int* __res
 // rows can always finish them: no deadlock whatever the residency.  Lanes of one wavefront that depend on each other resolve
 // over successive passes of the loop (nobody waits inside a pass).  A pass counter bounds the loop regardless: on overrun the
 // row publishes NaN and raises the error word the host checks at the end of the solve.
-// Arithmetic per row is exactly solveRow's, so results are bit-identical to the level-scheduled and the sequential sweeps.
+// Arithmetic per row is sweepStart / sweepTerm / sweepFinish (smm_trisweep.h), as in sweepRow, so results are bit-identical to the level-scheduled and the sequential sweeps.
 // ---------------------------------------------------------------------------------------------------------
 template <typename T>
 struct SweepBits;
@@ -222,7 +119,7 @@ __global__ __launch_bounds__(TPB) void sweepFreeKernel(int n, const int* __restr
 		chosen = __builtin_amdgcn_readfirstlane(chosen);
 		if (chosen != mine) return;
 	}
-	constexpr bool LOWER = MODE == SGS_LO || MODE == ILU_LO || MODE == IC_LO;
+	constexpr bool LOWER = isLower(MODE);
 	constexpr int W = SWEEP_WINDOW;
 	constexpr int DIR = LOWER ? 1 : -1;
 	using U = typename SweepBits<T>::U;
@@ -241,15 +138,9 @@ __global__ __launch_bounds__(TPB) void sweepFreeKernel(int n, const int* __restr
 			const int b = start[row];
 			const int e = start[row + 1];
 			own = in[row];
-			if (LOWER) {
-				k = b;
-				stop = e;
-				acc = own;
-			} else {
-				k = e - 1;
-				stop = b - 1;
-				acc = MODE == SGS_UP ? T(0) : own;
-			}
+			acc = sweepStart<T, MODE>(own);
+			k = LOWER ? b : e - 1;
+			stop = LOWER ? e : b - 1;
 		}
 		int wc[W];     // columns of the window; `row` marks the end of the row's triangular part
 		T wv[W];       // values of the window
@@ -288,24 +179,13 @@ __global__ __launch_bounds__(TPB) void sweepFreeKernel(int n, const int* __restr
 						const T value = wv[u];
 						if (LOWER ? col >= row : col <= row) {
 							// the diagonal (or, for ILU's unit-lower part only, the end of the row)
-							T result;
-							if (MODE == SGS_LO) result = acc / value;             // ref:1695
-							else if (MODE == SGS_UP) result = own - acc / value;  // ref:1710
-							else if (MODE == ILU_LO) result = acc;
-							else result = acc / value;                            // ILU_UP, IC_LO (ref:1818), IC_UP (ref:1834)
-							publishX<T, ONE_XCD>(out, row, result);
+							publishX<T, ONE_XCD>(out, row, sweepFinish<T, MODE>(acc, own, value));
 							pending = false;
 							moved = true;
 						} else if (xb[u] != SweepBits<T>::SENT) {
 							T xv;
 							__builtin_memcpy(&xv, &xb[u], sizeof(T));
-							if (MODE == SGS_LO) acc = smmFma(-value, xv, acc);
-							else if (MODE == SGS_UP) acc = smmFma(value, xv, acc);
-							else if (MODE == ILU_LO || MODE == ILU_UP) acc = smmFma(-value, xv, acc);
-							else {
-								const T prod = value * xv;  // ref:1812-1813, 1828-1829: multiply, then subtract
-								acc = acc - prod;
-							}
+							acc = sweepTerm<T, MODE>(acc, value, xv);
 							used = u + 1;
 							moved = true;
 						} else {
@@ -450,18 +330,6 @@ __global__ __launch_bounds__(TPB) void maxLevelKernel(int n, const int* __restri
 	if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(out, top);
 }
 
-__global__ __launch_bounds__(TPB) void iotaKernel(int n, int* out) {
-	for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * TPB) out[i] = static_cast<int>(i);
-}
-
-// sortedLevel[] ascending: lvlPtr[l] = first index of level l (every level 0 .. nLevels-1 holds at least one row), lvlPtr[nLevels] = n
-__global__ __launch_bounds__(TPB) void levelPtrKernel(int n, int nLevels, const int* __restrict__ sortedLevel, int* __restrict__ lvlPtr) {
-	for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * TPB) {
-		if (i == 0 || sortedLevel[i] != sortedLevel[i - 1]) lvlPtr[sortedLevel[i]] = static_cast<int>(i);
-	}
-	if (blockIdx.x == 0 && threadIdx.x == 0) lvlPtr[nLevels] = n;
-}
-
 // position of column c among positions[b .. e) (ascending), or -1
 __device__ __forceinline__ int findColumn(const int* __restrict__ positions, int b, int e, int c) {
 	int lo = b, hi = e;
@@ -593,38 +461,11 @@ __global__ __launch_bounds__(SMALL_LEVEL) void factorChainKernel(const int* __re
 	}
 }
 
-struct SweepPlan {
-	// launch groups: chains of small levels, or single large levels
-	struct Group {
-		int l0, l1;
-		bool chain;
-	};
-	std::vector<Group> groups;
-	int* d_lvlPtr = nullptr;
-};
-
-static void planGroups(const std::vector<int>& lvlPtr, std::vector<SweepPlan::Group>& groups) {
-	const int nl = static_cast<int>(lvlPtr.size()) - 1;
-	int l = 0;
-	while (l < nl) {
-		const int sz = lvlPtr[l + 1] - lvlPtr[l];
-		if (sz > SMALL_LEVEL) {
-			groups.push_back({l, l + 1, false});
-			++l;
-		} else {
-			int e = l + 1;
-			while (e < nl && lvlPtr[e + 1] - lvlPtr[e] <= SMALL_LEVEL) ++e;
-			groups.push_back({l, e, true});
-			l = e;
-		}
-	}
-}
-
 }  // namespace smm
 
-// the level pointers and launch groups ride along behind the public handle
+// the exact kinds' state behind the public handle: the level schedules of both sweeps and what the synchronisation-free sweeps need
 struct smm_precond_plan {
-	smm::SweepPlan lo, up;
+	smm::LevelSchedule lo, up;  // the level sets of the two sweeps: rows sorted by level, the level pointers, the launch groups
 	int sweep = SMM_SWEEP_AUTO;
 	// Escape bound of the synchronisation-free sweeps, in polling passes of a waiting wavefront.  A waiter polls about as fast as a
 	// worker consumes one window of SWEEP_WINDOW entries, so a row that must wait for a row of L entries needs ~L / SWEEP_WINDOW
@@ -645,23 +486,15 @@ struct smm_precond_plan {
 
 namespace smm {
 
-static smm_precond_plan* planOf(const smm_hip_precond* M) { return M->plan; }
-
-template <typename T, int MODE>
-static int runSweep(const smm_hip_precond* M, const SweepPlan& plan, const int* d_order, const std::vector<int>& lvlPtr, const T* vals, const T* rhs,
-                    T* x, const int* doneFlag, hipStream_t s) {
-	const smm_hip_csr* a = M->a;
-	for (const auto& g : plan.groups) {
-		if (g.chain) {
-			sweepChainKernel<T, MODE><<<1, SMALL_LEVEL, 0, s>>>(d_order, plan.d_lvlPtr, g.l0, g.l1, a->d_start, a->d_positions, vals, rhs, x, doneFlag);
-		} else {
-			const int begin = lvlPtr[g.l0];
-			const int count = lvlPtr[g.l1] - begin;
-			sweepLevelKernel<T, MODE><<<(count + TPB - 1) / TPB, TPB, 0, s>>>(d_order, begin, count, a->d_start, a->d_positions, vals, rhs, x, doneFlag);
-		}
+void planDestroy(smm_precond_plan* plan) {
+	if (!plan) return;
+	plan->lo.release();
+	plan->up.release();
+	for (auto& kv : plan->scratch) {
+		devFree(kv.second.y);
+		devFree(kv.second.words);
 	}
-	SMM_HIP_TRY(hipGetLastError());
-	return SMM_HIP_OK;
+	delete plan;
 }
 
 static int scratchFor(const smm_hip_precond* M, size_t elemBytes, hipStream_t s, smm_precond_plan::Scratch* out) {
@@ -712,13 +545,14 @@ static int runSweepsFree(const smm_hip_precond* M, const T* vals, const T* rhs, 
 	const int fill = static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL));
 	// ONE_XCD: workgroups are dealt round-robin over the 8 XCDs, so 8 x as many are launched and the elected eighth stays
 	const int spread = ONE_XCD ? 8 : 1;
-	const int wLo = spread * sweepWaves(n, M->lvl_ptr_lo.size() - 1, ONE_XCD);
-	const int wUp = spread * sweepWaves(n, M->lvl_ptr_up.size() - 1, ONE_XCD);
-	const unsigned limit = M->plan->passLimit;
+	const smm_precond_plan* plan = M->plan;
+	const int wLo = spread * sweepWaves(n, plan->lo.levels(), ONE_XCD);
+	const int wUp = spread * sweepWaves(n, plan->up.levels(), ONE_XCD);
+	const unsigned limit = plan->passLimit;
 	std::lock_guard<std::mutex> whole(M->plan->enqueueMutex);
 	sweepPrefillKernel<T><<<fill, TPB, 0, s>>>(n, y, x, sc.words, doneFlag);
-	sweepFreeKernel<T, LO, ONE_XCD><<<wLo, WAVE, 0, s>>>(n, M->d_order_lo, a->d_start, a->d_positions, vals, rhs, y, sc.words, sc.words + 2, doneFlag, limit, sc.words + 3);
-	sweepFreeKernel<T, UP, ONE_XCD><<<wUp, WAVE, 0, s>>>(n, M->d_order_up, a->d_start, a->d_positions, vals, y, x, sc.words + 1, sc.words + 2, doneFlag, limit, sc.words + 4);
+	sweepFreeKernel<T, LO, ONE_XCD><<<wLo, WAVE, 0, s>>>(n, plan->lo.d_order, a->d_start, a->d_positions, vals, rhs, y, sc.words, sc.words + 2, doneFlag, limit, sc.words + 3);
+	sweepFreeKernel<T, UP, ONE_XCD><<<wUp, WAVE, 0, s>>>(n, plan->up.d_order, a->d_start, a->d_positions, vals, y, x, sc.words + 1, sc.words + 2, doneFlag, limit, sc.words + 4);
 	SMM_HIP_TRY(hipGetLastError());
 	return SMM_HIP_OK;
 }
@@ -752,7 +586,7 @@ static int sweepModeOf(const smm_hip_precond* M) {
 	const smm_precond_plan* plan = M->plan;
 	int mode = plan->sweep;
 	if (mode == SMM_SWEEP_AUTO) {
-		const size_t levels = std::max<size_t>(1, std::min(M->lvl_ptr_lo.size(), M->lvl_ptr_up.size()) - 1);
+		const size_t levels = std::max<size_t>(1, std::min(plan->lo.bounds.size(), plan->up.bounds.size()) - 1);
 		mode = env::intOr(env::SWEEP, static_cast<size_t>(M->a->rows) / levels <= 2048 ? SMM_SWEEP_SYNCFREE_XCD : SMM_SWEEP_SYNCFREE);
 	}
 	return mode;
@@ -775,115 +609,70 @@ int precondApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* don
 	if (M->kind == SMM_PRECOND_AMG) return amgApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (isMulticolorKind(M->kind)) return mcApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_JACOBI) {
-		const int grid = static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL));
-		jacobiApplyKernel<T><<<grid, TPB, 0, s>>>(n, static_cast<const T*>(M->d_values), rhs, x, doneFlag);
+		jacobiApplyKernel<T><<<sweepGrid(n), TPB, 0, s>>>(n, static_cast<const T*>(M->d_values), rhs, x, doneFlag);
 		SMM_HIP_TRY(hipGetLastError());
 		return SMM_HIP_OK;
 	}
-	const smm_precond_plan* plan = planOf(M);
+	const smm_precond_plan* plan = M->plan;
 	if (!plan) {
 		setError("precond_apply: preconditioner has no sweep plan");
 		return SMM_HIP_ERR_INVALID;
 	}
-	const T* aVals = static_cast<const T*>(M->a->d_values);
-	const T* fVals = static_cast<const T*>(M->d_values);
+	const T* vals = static_cast<const T*>(M->kind == SMM_PRECOND_SGS ? M->a->d_values : M->d_values);  // SGS sweeps A itself, ILU0 / IC0 their factor
 	const int mode = sweepModeOf(M);
-	if (mode == SMM_SWEEP_SYNCFREE_XCD) {
-		switch (M->kind) {
-		case SMM_PRECOND_SGS: return runSweepsFree<T, SGS_LO, SGS_UP, true>(M, aVals, rhs, x, doneFlag, s);
-		case SMM_PRECOND_ILU0: return runSweepsFree<T, ILU_LO, ILU_UP, true>(M, fVals, rhs, x, doneFlag, s);
-		case SMM_PRECOND_IC0: return runSweepsFree<T, IC_LO, IC_UP, true>(M, fVals, rhs, x, doneFlag, s);
-		default: break;
-		}
-	} else if (mode != SMM_SWEEP_LEVELS) {
-		switch (M->kind) {
-		case SMM_PRECOND_SGS: return runSweepsFree<T, SGS_LO, SGS_UP, false>(M, aVals, rhs, x, doneFlag, s);
-		case SMM_PRECOND_ILU0: return runSweepsFree<T, ILU_LO, ILU_UP, false>(M, fVals, rhs, x, doneFlag, s);
-		case SMM_PRECOND_IC0: return runSweepsFree<T, IC_LO, IC_UP, false>(M, fVals, rhs, x, doneFlag, s);
-		default: break;
-		}
-	}
-	switch (M->kind) {
-	case SMM_PRECOND_SGS:
-		SMM_TRY((runSweep<T, SGS_LO>(M, plan->lo, M->d_order_lo, M->lvl_ptr_lo, aVals, rhs, x, doneFlag, s)));
-		SMM_TRY((runSweep<T, SGS_UP>(M, plan->up, M->d_order_up, M->lvl_ptr_up, aVals, rhs, x, doneFlag, s)));
-		return SMM_HIP_OK;
-	case SMM_PRECOND_ILU0:
-		SMM_TRY((runSweep<T, ILU_LO>(M, plan->lo, M->d_order_lo, M->lvl_ptr_lo, fVals, rhs, x, doneFlag, s)));
-		SMM_TRY((runSweep<T, ILU_UP>(M, plan->up, M->d_order_up, M->lvl_ptr_up, fVals, rhs, x, doneFlag, s)));
-		return SMM_HIP_OK;
-	case SMM_PRECOND_IC0:
-		SMM_TRY((runSweep<T, IC_LO>(M, plan->lo, M->d_order_lo, M->lvl_ptr_lo, fVals, rhs, x, doneFlag, s)));
-		SMM_TRY((runSweep<T, IC_UP>(M, plan->up, M->d_order_up, M->lvl_ptr_up, fVals, rhs, x, doneFlag, s)));
-		return SMM_HIP_OK;
-	default:
-		setError("precond_apply: kind %d has no apply", M->kind);
-		return SMM_HIP_ERR_INVALID;
-	}
+	return withSweepModes(M->kind, [&](auto lo, auto up) -> int {
+		constexpr int LO = decltype(lo)::value, UP = decltype(up)::value;
+		if (mode == SMM_SWEEP_SYNCFREE_XCD) return runSweepsFree<T, LO, UP, true>(M, vals, rhs, x, doneFlag, s);
+		if (mode != SMM_SWEEP_LEVELS) return runSweepsFree<T, LO, UP, false>(M, vals, rhs, x, doneFlag, s);
+		const NaturalIO<T> io{rhs, x};
+		SMM_TRY((runLevelSweep<T, LO, NaturalIO<T>, true>(plan->lo, false, M->a, vals, io, doneFlag, s)));
+		return runLevelSweep<T, UP, NaturalIO<T>, true>(plan->up, false, M->a, vals, io, doneFlag, s);
+	});
 }
 
 template int precondApplyDev<float>(const smm_hip_precond*, const float*, float*, const int*, hipStream_t);
 template int precondApplyDev<double>(const smm_hip_precond*, const double*, double*, const int*, hipStream_t);
 
-// level sets of one sweep, on the device: d_order (rows sorted by level, ascending row inside a level), the level pointers on the host
-// (the launch plan is made from them) and on the device (the chained kernels read them)
+// level sets of one sweep, on the device: the schedule's d_order (rows sorted by level, ascending row inside a level), the level pointers on
+// the host (the launch groups are made from them) and on the device (the chained kernels read them)
 template <bool LOWER>
-static int buildLevelsDevice(const smm_hip_csr* a, unsigned passLimit, int maxRowLen, hipStream_t s, int** d_order, std::vector<int>& lvlPtr, int** d_lvlPtr) {
+static int buildLevelsDevice(const smm_hip_csr* a, int maxRowLen, hipStream_t s, LevelSchedule& sch) {
 	const int n = a->rows;
-	*d_order = nullptr;
-	*d_lvlPtr = nullptr;
-	lvlPtr.assign(1, 0);
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(d_order), static_cast<size_t>(std::max(1, n)) * sizeof(int)));
-	if (n == 0) {
-		SMM_TRY(devAlloc(reinterpret_cast<void**>(d_lvlPtr), sizeof(int)));
-		SMM_HIP_TRY(hipMemsetAsync(*d_lvlPtr, 0, sizeof(int), s));
-		return SMM_HIP_OK;
-	}
-	DevBuf<int> level, sorted, rowsIn, words;
+	SMM_TRY(devAlloc(reinterpret_cast<void**>(&sch.d_order), static_cast<size_t>(std::max(1, n)) * sizeof(int)));
+	DevBuf<int> level, words;
 	SMM_TRY(level.alloc(n));
-	SMM_TRY(sorted.alloc(n));
-	SMM_TRY(rowsIn.alloc(n));
-	SMM_TRY(words.alloc(4));
-	SMM_HIP_TRY(hipMemsetAsync(level, 0xFF, static_cast<size_t>(n) * sizeof(int), s));  // -1: not known yet
-	SMM_HIP_TRY(hipMemsetAsync(words, 0, 4 * sizeof(int), s));
-	// Resident wavefronts only (8 per CU), and the escape bound follows from their number: the wavefront that drew the last of the
-	// first `waves` tickets may have to wait for every chunk in front of it, each of which needs at most 64 rows x (longest row + 2)
-	// passes once ITS predecessors are done (a pure chain -- a tridiagonal matrix, a dense band -- is the worst case; the r02 bound,
-	// 2^21 + 64 x longest row for up to 8192 wavefronts, left a factor 2 for a tridiagonal matrix and none for a 50-entry band).
-	const int waves = std::min((n + WAVE - 1) / WAVE, numCUs() * 8);
-	const unsigned long long perChunk = 64ull * (static_cast<unsigned long long>(maxRowLen) + 2ull);
-	const unsigned levelLimit = static_cast<unsigned>(std::min<unsigned long long>(0x7fffffffull, (1ull << 21) + 8ull * static_cast<unsigned long long>(waves) * perChunk));
-	(void)passLimit;
-	levelFreeKernel<LOWER><<<(waves + TPB / WAVE - 1) / (TPB / WAVE), TPB, 0, s>>>(n, a->d_start, a->d_positions, level, words, levelLimit);
-	const int grid = static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL));
-	maxLevelKernel<<<grid, TPB, 0, s>>>(n, level, words.p + 1);
-	iotaKernel<<<grid, TPB, 0, s>>>(n, rowsIn);
-	int h[4] = {0, 0, 0, 0};
-	SMM_HIP_TRY(hipMemcpyAsync(h, words, sizeof(h), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
-	if (h[2]) {
-		setError("preconditioner: the level analysis ran into its pass limit");
-		return SMM_HIP_ERR_HIP;
+	int nLevels = 0;
+	if (n > 0) {
+		SMM_TRY(words.alloc(4));
+		SMM_HIP_TRY(hipMemsetAsync(level, 0xFF, static_cast<size_t>(n) * sizeof(int), s));  // -1: not known yet
+		SMM_HIP_TRY(hipMemsetAsync(words, 0, 4 * sizeof(int), s));
+		// Resident wavefronts only (8 per CU), and the escape bound follows from their number: the wavefront that drew the last of the
+		// first `waves` tickets may have to wait for every chunk in front of it, each of which needs at most 64 rows x (longest row + 2)
+		// passes once ITS predecessors are done (a pure chain -- a tridiagonal matrix, a dense band -- is the worst case; the r02 bound,
+		// 2^21 + 64 x longest row for up to 8192 wavefronts, left a factor 2 for a tridiagonal matrix and none for a 50-entry band).
+		const int waves = std::min((n + WAVE - 1) / WAVE, numCUs() * 8);
+		const unsigned long long perChunk = 64ull * (static_cast<unsigned long long>(maxRowLen) + 2ull);
+		const unsigned levelLimit = static_cast<unsigned>(std::min<unsigned long long>(0x7fffffffull, (1ull << 21) + 8ull * static_cast<unsigned long long>(waves) * perChunk));
+		levelFreeKernel<LOWER><<<(waves + TPB / WAVE - 1) / (TPB / WAVE), TPB, 0, s>>>(n, a->d_start, a->d_positions, level, words, levelLimit);
+		maxLevelKernel<<<sweepGrid(n), TPB, 0, s>>>(n, level, words.p + 1);
+		int h[4] = {0, 0, 0, 0};
+		SMM_HIP_TRY(hipMemcpyAsync(h, words, sizeof(h), hipMemcpyDeviceToHost, s));
+		SMM_HIP_TRY(hipStreamSynchronize(s));
+		if (h[2]) {
+			setError("preconditioner: the level analysis ran into its pass limit");
+			return SMM_HIP_ERR_HIP;
+		}
+		nLevels = h[1] + 1;
 	}
-	const int nLevels = h[1] + 1;
-	int bits = 1;
-	while ((1ll << bits) <= h[1]) ++bits;
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, level.p, sorted.p, rowsIn.p, *d_order, static_cast<size_t>(n), 0, bits, s));
-	DevBuf<char> temp;
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, level.p, sorted.p, rowsIn.p, *d_order, static_cast<size_t>(n), 0, bits, s));
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(d_lvlPtr), (static_cast<size_t>(nLevels) + 1) * sizeof(int)));
-	levelPtrKernel<<<grid, TPB, 0, s>>>(n, nLevels, sorted, *d_lvlPtr);
-	lvlPtr.resize(static_cast<size_t>(nLevels) + 1);
-	SMM_HIP_TRY(hipMemcpyAsync(lvlPtr.data(), *d_lvlPtr, lvlPtr.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));  // the scratch buffers go back to the allocator when this scope ends
+	SMM_TRY(devAlloc(reinterpret_cast<void**>(&sch.d_bounds), (static_cast<size_t>(nLevels) + 1) * sizeof(int)));
+	SMM_TRY(sortRowsByKey(level, n, nLevels, s, sch.d_order, sch.d_bounds, sch.bounds));
+	planGroups(sch.bounds, sch.groups);
 	return SMM_HIP_OK;
 }
 
 // ILU(0) / IC(0) on the device, level by level in the order of the lower sweep (a row is eliminated with rows of earlier levels only)
 template <typename T, int KIND>
-static int factorDevice(const smm_hip_csr* a, const SweepPlan& plan, const int* d_order, const std::vector<int>& lvlPtr, T* f, int* herr, hipStream_t s) {
+static int factorDevice(const smm_hip_csr* a, const LevelSchedule& sch, T* f, int* herr, hipStream_t s) {
 	const int n = a->rows;
 	DevBuf<T> piv;
 	DevBuf<int> err;
@@ -891,13 +680,13 @@ static int factorDevice(const smm_hip_csr* a, const SweepPlan& plan, const int* 
 	SMM_TRY(err.alloc(1));
 	SMM_HIP_TRY(hipMemsetAsync(err, 0, sizeof(int), s));
 	const T* aVals = static_cast<const T*>(a->d_values);
-	for (const auto& g : plan.groups) {
+	for (const auto& g : sch.groups) {
 		if (g.chain) {
-			factorChainKernel<T, KIND><<<1, SMALL_LEVEL, 0, s>>>(d_order, plan.d_lvlPtr, g.l0, g.l1, a->d_start, a->d_positions, aVals, f, piv.p, err.p);
+			factorChainKernel<T, KIND><<<1, SMALL_LEVEL, 0, s>>>(sch.d_order, sch.d_bounds, g.l0, g.l1, a->d_start, a->d_positions, aVals, f, piv.p, err.p);
 		} else {
-			const int begin = lvlPtr[g.l0];
-			const int count = lvlPtr[g.l0 + 1] - begin;
-			factorLevelKernel<T, KIND><<<(count + TPB / WAVE - 1) / (TPB / WAVE), TPB, 0, s>>>(d_order, begin, count, a->d_start, a->d_positions, aVals, f, piv.p, err.p);
+			const int begin = sch.bounds[g.l0];
+			const int count = sch.bounds[g.l0 + 1] - begin;
+			factorLevelKernel<T, KIND><<<(count + TPB / WAVE - 1) / (TPB / WAVE), TPB, 0, s>>>(sch.d_order, begin, count, a->d_start, a->d_positions, aVals, f, piv.p, err.p);
 		}
 	}
 	SMM_HIP_TRY(hipGetLastError());
@@ -906,47 +695,55 @@ static int factorDevice(const smm_hip_csr* a, const SweepPlan& plan, const int* 
 	return SMM_HIP_OK;
 }
 
-// the structural checks of createTyped for another unit: info[0] != 0 on an empty row, a missing diagonal or (checkMagnitude) |d| < 1e-5;
-// info[1] = the longest row
+// f[nnz] = the ILU0 / IC0 factor of `a` on its pattern, over the levels of `sch` (rows by d_order); a failed factorisation sets its message
 template <typename T>
-int precondRowCheck(const smm_hip_csr* a, bool checkMagnitude, int* info, hipStream_t s) {
-	info[0] = info[1] = 0;
+static int factorOn(const smm_hip_csr* a, int kind, const LevelSchedule& sch, T* f, hipStream_t s) {
+	const size_t nnz = static_cast<size_t>(a->nnz);
+	int herr = 0;
+	if (kind == SMM_PRECOND_ILU0) {
+		if (nnz) SMM_HIP_TRY(hipMemcpyAsync(f, a->d_values, nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
+		SMM_TRY((factorDevice<T, SMM_PRECOND_ILU0>(a, sch, f, &herr, s)));
+	} else {
+		if (nnz) SMM_HIP_TRY(hipMemsetAsync(f, 0, nnz * sizeof(T), s));
+		SMM_TRY((factorDevice<T, SMM_PRECOND_IC0>(a, sch, f, &herr, s)));
+	}
+	return factorErrorFor(kind, herr);
+}
+
+// the structural checks of the exact kinds, for the multicolour unit too: SMM_HIP_ERR_PRECOND (message set) on an empty row, a missing
+// diagonal or (checkMagnitude) |d| < 1e-5; *longestRow (may be null) = the longest row
+template <typename T>
+int precondRowCheck(const smm_hip_csr* a, bool checkMagnitude, int* longestRow, hipStream_t s) {
+	int info[2] = {0, 0};
 	DevBuf<int> dinfo;
 	SMM_TRY(dinfo.alloc(2));
 	SMM_HIP_TRY(hipMemsetAsync(dinfo, 0, 2 * sizeof(int), s));
-	if (a->rows) {
-		const int grid = static_cast<int>(std::min<long long>((a->rows + TPB - 1LL) / TPB, numCUs() * 8LL));
-		rowCheckKernel<T><<<grid, TPB, 0, s>>>(a->rows, a->d_start, a->d_positions, static_cast<const T*>(a->d_values), checkMagnitude ? 1 : 0, dinfo);
-	}
+	if (a->rows) rowCheckKernel<T><<<sweepGrid(a->rows), TPB, 0, s>>>(a->rows, a->d_start, a->d_positions, static_cast<const T*>(a->d_values), checkMagnitude ? 1 : 0, dinfo);
 	SMM_HIP_TRY(hipMemcpyAsync(info, dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));
+	if (longestRow) *longestRow = info[1];
+	if (info[0]) {
+		setError("preconditioner: empty row, missing diagonal or |d|<1e-5");
+		return SMM_HIP_ERR_PRECOND;
+	}
 	return SMM_HIP_OK;
 }
 template int precondRowCheck<float>(const smm_hip_csr*, bool, int*, hipStream_t);
 template int precondRowCheck<double>(const smm_hip_csr*, bool, int*, hipStream_t);
 
-// the factorisation kernels on a matrix whose levels are given as row ranges in the natural order (the multicolour kinds: a colour is a level)
+// the factorisation on a matrix whose levels are row ranges in the natural order (the multicolour kinds: a colour is a level)
 template <typename T>
-int factorByRanges(const smm_hip_csr* b, int kind, const std::vector<int>& bounds, T* f, int* herr, hipStream_t s) {
+int factorByRanges(const smm_hip_csr* b, int kind, const LevelSchedule& ranges, T* f, hipStream_t s) {
 	const int n = b->rows;
-	DevBuf<int> order, lvl;
+	DevBuf<int> order;  // (the factor kernels take their rows through an order)
 	SMM_TRY(order.alloc(std::max(1, n)));
-	SMM_TRY(lvl.alloc(bounds.size()));
-	if (n) iotaKernel<<<static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL)), TPB, 0, s>>>(n, order);
-	SMM_HIP_TRY(hipMemcpyAsync(lvl, bounds.data(), bounds.size() * sizeof(int), hipMemcpyHostToDevice, s));
-	SweepPlan plan;
-	plan.d_lvlPtr = lvl;
-	planGroups(bounds, plan.groups);
-	const size_t nnz = static_cast<size_t>(b->nnz);
-	if (kind == SMM_PRECOND_ILU0) {
-		if (nnz) SMM_HIP_TRY(hipMemcpyAsync(f, b->d_values, nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
-		return factorDevice<T, SMM_PRECOND_ILU0>(b, plan, order, bounds, f, herr, s);
-	}
-	if (nnz) SMM_HIP_TRY(hipMemsetAsync(f, 0, nnz * sizeof(T), s));
-	return factorDevice<T, SMM_PRECOND_IC0>(b, plan, order, bounds, f, herr, s);
+	if (n) iotaKernel<<<sweepGrid(n), TPB, 0, s>>>(n, order);
+	LevelSchedule sch = ranges;
+	sch.d_order = order;
+	return factorOn<T>(b, kind, sch, f, s);
 }
-template int factorByRanges<float>(const smm_hip_csr*, int, const std::vector<int>&, float*, int*, hipStream_t);
-template int factorByRanges<double>(const smm_hip_csr*, int, const std::vector<int>&, double*, int*, hipStream_t);
+template int factorByRanges<float>(const smm_hip_csr*, int, const LevelSchedule&, float*, hipStream_t);
+template int factorByRanges<double>(const smm_hip_csr*, int, const LevelSchedule&, double*, hipStream_t);
 
 template <typename T>
 static int createTyped(const smm_hip_csr* a, int kind, smm_hip_precond* M) {
@@ -959,10 +756,7 @@ static int createTyped(const smm_hip_csr* a, int kind, smm_hip_precond* M) {
 		DevBuf<int> err;
 		SMM_TRY(err.alloc(1));
 		SMM_HIP_TRY(hipMemsetAsync(err, 0, sizeof(int), s));
-		if (n) {
-			const int grid = static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL));
-			extractDiagKernel<T><<<grid, TPB, 0, s>>>(n, a->d_start, a->d_positions, static_cast<const T*>(a->d_values), static_cast<T*>(M->d_values), err);
-		}
+		if (n) extractDiagKernel<T><<<sweepGrid(n), TPB, 0, s>>>(n, a->d_start, a->d_positions, static_cast<const T*>(a->d_values), static_cast<T*>(M->d_values), err);
 		int herr = 0;
 		SMM_HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
 		SMM_HIP_TRY(hipStreamSynchronize(s));
@@ -981,50 +775,18 @@ static int createTyped(const smm_hip_csr* a, int kind, smm_hip_precond* M) {
 		setError("preconditioner: matrix has leading empty rows (firstActiveStart != 0)");
 		return SMM_HIP_ERR_PRECOND;
 	}
-	int info[2] = {0, 0};  // structural error, longest row
-	{
-		DevBuf<int> dinfo;
-		SMM_TRY(dinfo.alloc(2));
-		SMM_HIP_TRY(hipMemsetAsync(dinfo, 0, 2 * sizeof(int), s));
-		if (n) {
-			const int grid = static_cast<int>(std::min<long long>((n + TPB - 1LL) / TPB, numCUs() * 8LL));
-			rowCheckKernel<T><<<grid, TPB, 0, s>>>(n, a->d_start, a->d_positions, static_cast<const T*>(a->d_values), kind == SMM_PRECOND_SGS ? 1 : 0, dinfo);
-		}
-		SMM_HIP_TRY(hipMemcpyAsync(info, dinfo, sizeof(info), hipMemcpyDeviceToHost, s));
-		SMM_HIP_TRY(hipStreamSynchronize(s));
-	}
-	if (info[0]) {
-		setError("preconditioner: empty row, missing diagonal or |d|<1e-5");
-		return SMM_HIP_ERR_PRECOND;
-	}
+	int longestRow = 0;
+	SMM_TRY(precondRowCheck<T>(a, kind == SMM_PRECOND_SGS, &longestRow, s));
 	auto* plan = new smm_precond_plan();
 	M->plan = plan;  // (smm_hip_precond_destroy releases it together with whatever the steps below have allocated so far)
-	plan->passLimit = static_cast<unsigned>(std::min<long long>(0x7fffffffLL, (1LL << 21) + 64LL * info[1]));
-	SMM_TRY(buildLevelsDevice<true>(a, plan->passLimit, info[1], s, &M->d_order_lo, M->lvl_ptr_lo, &plan->lo.d_lvlPtr));
-	SMM_TRY(buildLevelsDevice<false>(a, plan->passLimit, info[1], s, &M->d_order_up, M->lvl_ptr_up, &plan->up.d_lvlPtr));
-	planGroups(M->lvl_ptr_lo, plan->lo.groups);
-	planGroups(M->lvl_ptr_up, plan->up.groups);
+	plan->passLimit = static_cast<unsigned>(std::min<long long>(0x7fffffffLL, (1LL << 21) + 64LL * longestRow));
+	SMM_TRY(buildLevelsDevice<true>(a, longestRow, s, plan->lo));
+	SMM_TRY(buildLevelsDevice<false>(a, longestRow, s, plan->up));
 	if (kind == SMM_PRECOND_ILU0 || kind == SMM_PRECOND_IC0) {
 		const size_t nnz = static_cast<size_t>(a->nnz);
 		SMM_TRY(devAlloc(&M->d_values, std::max<size_t>(1, nnz) * sizeof(T)));
 		M->n_values = nnz;
-		int herr = 0;
-		if (kind == SMM_PRECOND_ILU0) {
-			if (nnz) SMM_HIP_TRY(hipMemcpyAsync(M->d_values, a->d_values, nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
-			SMM_TRY((factorDevice<T, SMM_PRECOND_ILU0>(a, plan->lo, M->d_order_lo, M->lvl_ptr_lo, static_cast<T*>(M->d_values), &herr, s)));
-			if (herr) {
-				setError("ilu0: zero / missing pivot (reordering would be needed, ref:1741-1746)");
-				return SMM_HIP_ERR_PRECOND;
-			}
-		} else {
-			if (nnz) SMM_HIP_TRY(hipMemsetAsync(M->d_values, 0, nnz * sizeof(T), s));
-			SMM_TRY((factorDevice<T, SMM_PRECOND_IC0>(a, plan->lo, M->d_order_lo, M->lvl_ptr_lo, static_cast<T*>(M->d_values), &herr, s)));
-			if (herr) {
-				setError(herr & 1 ? "ic0: matrix is not symmetric positive definite on its pattern (ref:1871-1878)"
-				                  : "ic0: the pattern of the matrix is not symmetric");
-				return SMM_HIP_ERR_PRECOND;
-			}
-		}
+		SMM_TRY(factorOn<T>(a, kind, plan->lo, static_cast<T*>(M->d_values), s));
 	}
 	SMM_HIP_TRY(hipStreamSynchronize(s));
 	return SMM_HIP_OK;
@@ -1204,19 +966,8 @@ int smm_hip_precond_destroy(smm_hip_precond* M) {
 	chebDestroy(M->cheb);
 	amgDestroy(M->amg);
 	mcDestroy(M->mc);
-	smm_precond_plan* plan = M->plan;
-	if (plan) {
-		devFree(plan->lo.d_lvlPtr);
-		devFree(plan->up.d_lvlPtr);
-		for (auto& kv : plan->scratch) {
-			devFree(kv.second.y);
-			devFree(kv.second.words);
-		}
-		delete plan;
-	}
+	planDestroy(M->plan);
 	devFree(M->d_values);
-	devFree(M->d_order_lo);
-	devFree(M->d_order_up);
 	delete M;
 	return SMM_HIP_OK;
 }
@@ -1235,8 +986,8 @@ int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower,
 		mcLevels(M->mc, levels_lower, levels_upper);
 		return SMM_HIP_OK;
 	}
-	if (levels_lower) *levels_lower = M->lvl_ptr_lo.empty() ? 0 : static_cast<int>(M->lvl_ptr_lo.size()) - 1;
-	if (levels_upper) *levels_upper = M->lvl_ptr_up.empty() ? 0 : static_cast<int>(M->lvl_ptr_up.size()) - 1;
+	if (levels_lower) *levels_lower = M->plan ? M->plan->lo.levels() : 0;  // (Jacobi, NONE, Chebyshev, AMG: no sweeps)
+	if (levels_upper) *levels_upper = M->plan ? M->plan->up.levels() : 0;
 	return SMM_HIP_OK;
 }
 

@@ -488,14 +488,9 @@ int cgDev(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIterations
           int* iterations, T* resnorm2) {
 	SMM_TRY(solverCheck<T>("cg", a, b, x0, x));
 	const int pcg = M != nullptr;
-	if (pcg && ((M->kind != SMM_PRECOND_IC0 && M->kind != SMM_PRECOND_CHEBYSHEV && M->kind != SMM_PRECOND_AMG && M->kind != SMM_PRECOND_MULTICOLOR_IC0 &&
-	             M->kind != SMM_PRECOND_MULTICOLOR_SGS) ||
-	            M->a != a)) {
-		// the reference only has the IC0 overload (ref:2414-2422); the Chebyshev polynomial and the multigrid V-cycle are symmetric positive definite for such a matrix too
-		// (MULTICOLOR_IC0 and MULTICOLOR_SGS are IC0 / SGS of P A Pᵀ carried back by P: symmetric positive definite when A is)
-		setError("cg: preconditioner must be IC0 / CHEBYSHEV / AMG / MULTICOLOR_IC0 / MULTICOLOR_SGS created for this matrix");
-		return SMM_HIP_ERR_INVALID;
-	}
+	// the reference only has the IC0 overload (ref:2414-2422); the Chebyshev polynomial and the multigrid V-cycle are symmetric positive definite for such a matrix too
+	// (MULTICOLOR_IC0 and MULTICOLOR_SGS are IC0 / SGS of P A Pᵀ carried back by P: symmetric positive definite when A is)
+	SMM_TRY(precondAdmissible("cg", M, a, SOLVER_CG));
 	const int n = a->rows;
 	if (!pcg) {
 		// a matrix that fits the chip's register file is solved in one launch (smm_resident.hip)
@@ -759,10 +754,7 @@ int bicgstabDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T eps
                 int* iterations, T* resnorm) {
 	SMM_TRY(solverCheck<T>("bicgstab", a, b, x));
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;  // ref:2209
-	if (precondition && (M->a != a || M->kind == SMM_PRECOND_IC0 || M->kind == SMM_PRECOND_MULTICOLOR_IC0)) {
-		setError("bicgstab: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG / MULTICOLOR_SGS / MULTICOLOR_ILU0 created for this matrix");
-		return SMM_HIP_ERR_INVALID;
-	}
+	SMM_TRY(precondAdmissible("bicgstab", M, a, SOLVER_GENERAL));
 	const DevApplier<T> apply{M};
 	SMM_TRY(ensureCsrReady(a, s, true));
 	SMM_TRY(adoptPatternForSolver(a, maxIterations, s));

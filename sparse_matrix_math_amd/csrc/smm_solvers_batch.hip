@@ -347,12 +347,9 @@ int bicgstabBatchDev(const smm_hip_csr* a, int k, const T* b, T* x, int maxItera
 	SMM_TRY(batchCheck<T>("bicgstab_batch", a, k, b, x));
 	const int n = a->rows;
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;  // ref:2209
-	if (precondition && M->kind != SMM_PRECOND_JACOBI) {
-		setError("bicgstab_batch: only no preconditioner or JACOBI is supported for several right-hand sides (SGS / ILU0 / IC0 / BLOCK_ kinds are not)");
-		return SMM_HIP_ERR_INVALID;
-	}
-	if (precondition && (M->a != a || M->dtype != dtypeOf<T>())) {
-		setError("bicgstab_batch: the JACOBI preconditioner must have been created for this matrix");
+	SMM_TRY(precondAdmissible("bicgstab_batch", M, a, SOLVER_BATCHED));  // (the sweeps of the other kinds exist for one right-hand side only)
+	if (precondition && M->dtype != dtypeOf<T>()) {
+		setError("bicgstab_batch: the preconditioner holds values of the other dtype");
 		return SMM_HIP_ERR_INVALID;
 	}
 	SMM_TRY(ensureCsrReady(a, s, true));

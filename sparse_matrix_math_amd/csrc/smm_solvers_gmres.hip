@@ -327,8 +327,9 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
                     int* iterations, T* resnorm2) {
 	SMM_TRY(gmresCheck<T>(a, b, x, restart));
 	const bool precondition = M != nullptr && M->kind != SMM_PRECOND_NONE;
-	if (precondition && (M->a != a || M->kind == SMM_PRECOND_IC0 || M->kind == SMM_PRECOND_MULTICOLOR_IC0 || M->dtype != dtypeOf<T>())) {
-		setError("gmres: preconditioner must be JACOBI / ILU0 / SGS / BLOCK_ILU0 / BLOCK_SGS / CHEBYSHEV / AMG / MULTICOLOR_SGS / MULTICOLOR_ILU0 created for this matrix");
+	SMM_TRY(precondAdmissible("gmres", M, a, SOLVER_GENERAL));
+	if (precondition && M->dtype != dtypeOf<T>()) {
+		setError("gmres: the preconditioner holds values of the other dtype");
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int n = a->rows;

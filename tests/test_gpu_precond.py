@@ -286,3 +286,76 @@ def test_deep_chains_do_not_trip_the_escape_bound(smm, oracle, case):
             np.testing.assert_array_equal(x, oracle.ilu0_apply(csr, lu, rhs)[1])
         else:
             np.testing.assert_array_equal(x, oracle.sgs_apply(csr, rhs)[1])
+
+
+def _smallest_shapes(dtype):
+    """symmetric positive definite, so that every kind can be created: 1 x 1; 2 x 2 diagonal (no row has an off-diagonal entry); a 65-row
+    tridiagonal matrix (every row its own level, one level more than a wavefront has lanes, first and last row with one neighbour)"""
+    one = (np.array([0, 1], dtype=np.int32), np.array([0], dtype=np.int32), np.array([3.0], dtype=dtype))
+    diag2 = (np.array([0, 1, 2], dtype=np.int32), np.array([0, 1], dtype=np.int32), np.array([3.0, 7.0], dtype=dtype))
+    n = 65
+    cols = np.arange(n)[:, None] + np.array([-1, 0, 1])[None, :]
+    ok = (cols >= 0) & (cols < n)
+    start = np.zeros(n + 1, dtype=np.int32)
+    np.cumsum(ok.sum(axis=1), out=start[1:])
+    lower = -(1.0 + 0.003 * np.arange(n))  # a(i, i - 1) = a(i - 1, i)
+    vals = np.stack([lower, 4.0 + 0.01 * np.arange(n), np.roll(lower, -1)], axis=1)
+    return {"1x1": one, "2x2_diagonal": diag2, "tridiagonal_65": (start, cols[ok].astype(np.int32), vals[ok].astype(dtype))}
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_smallest_triangular_shapes(smm, oracle, dtype):
+    """SGS / ILU0 / IC0 in every sweep mode and their multicolour forms on the smallest shapes a sweep can take: bit for bit the oracle's
+    sequential sweeps (the multicolour kinds: on the restated permuted matrix, tests/multicolor_restatement.py); no rows: OK, nothing written"""
+    import torch
+    from device_views import address, assert_guards_intact, carve
+    from multicolor_restatement import IC0, ILU0, SGS, make_apply
+
+    from sparse_matrix_math_amd.host import SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD
+
+    P = smm.SolverPreconditioner
+    exact = {SGS: P.SYMMETRIC_GAUS_SEIDEL, ILU0: P.ILU0, IC0: P.IC0}
+    multi = {SGS: P.MULTICOLOR_SGS, ILU0: P.MULTICOLOR_ILU0, IC0: P.MULTICOLOR_IC0}
+
+    def bits(a):
+        return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+    def sequential(csr, base, rhs):
+        if base == SGS:
+            err, x = oracle.sgs_apply(csr, rhs)
+        else:
+            e, f = oracle.ilu0_factorize(csr) if base == ILU0 else oracle.ic0_factorize(csr)
+            assert e == 0
+            err, x = oracle.ilu0_apply(csr, f, rhs) if base == ILU0 else oracle.ic0_apply(csr, f, rhs)
+        assert err == 0
+        return x
+
+    for name, csr in _smallest_shapes(dtype).items():
+        n = len(csr[0]) - 1
+        A = make(smm, csr)
+        rhs = np.random.default_rng(21).uniform(-1, 1, n).astype(dtype)
+        for base in (SGS, ILU0, IC0):
+            want = sequential(csr, base, rhs)
+            M = A.getPreconditioner(exact[base])
+            assert M.levels() == ((n, n) if name == "tridiagonal_65" else (1, 1))
+            for mode in (SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD):
+                M.set_sweep(mode)
+                x = np.full(n, np.nan, dtype=dtype)
+                M.apply(rhs, x)
+                np.testing.assert_array_equal(bits(x), bits(want), err_msg=f"{name} {base} sweep mode {mode}")
+            want = make_apply(oracle, csr, base)(rhs)
+            x = np.full(n, np.nan, dtype=dtype)
+            A.getPreconditioner(multi[base]).apply(rhs, x)
+            np.testing.assert_array_equal(bits(x), bits(want), err_msg=f"{name} MULTICOLOR_{base}")
+    E = smm.CSRMatrix(0, 0, np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=dtype))
+    for kind in list(exact.values()) + list(multi.values()):
+        M = E.getPreconditioner(kind)
+        for mode in (SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD):
+            M.set_sweep(mode)
+            M.apply(np.zeros(0, dtype=dtype), np.zeros(0, dtype=dtype))
+            d_r, d_x = carve(0, dtype, 0, device="cuda:0"), carve(0, dtype, 1, device="cuda:0")
+            M.apply_dev(address(d_r), address(d_x))  # (a view of no elements has no address of its own)
+            M.take_error()
+            torch.cuda.synchronize()
+            assert_guards_intact(d_r, "rhs")
+            assert_guards_intact(d_x, "x")
