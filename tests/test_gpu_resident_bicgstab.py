@@ -97,8 +97,12 @@ def test_every_rows_per_lane_shape(smm, oracle, modes, grid, dtype):
     # it, by the same amount -- tests/test_gpu_resident.py has the same note for CG)
     assert float(np.max(np.abs(res[2] - x_o))) <= (2e-2 if dtype == np.float32 else ORACLE_TOL[dtype])
     # ... then a constant-diagonal operator with Jacobi to convergence: the convection-diffusion one in fp64; in fp32 BiCGStab's residual on
-    # that non-normal matrix climbs to 1e4-1e6 before it turns NaN in BOTH paths (tools/lab/resident_fp32_diag.py: a property of the method
-    # in that precision, not of a kernel), so fp32 takes the symmetric Laplacian of the same grid
+    # that non-normal matrix climbs to 1e4-1e6 before it turns NaN in BOTH paths at these sizes (profiles/r05/resident_fp32_diag.txt), so fp32
+    # takes the symmetric Laplacian of the same grid.  What is known of that NaN (tests/test_gpu_bicgstab_long.py, KNOWN_NAN): at 64^3 + Jacobi
+    # the loop's sum ap . r0 is exactly 0 at iteration 49 and alpha = rr0 / 0; on the CPU every summation order tried stays finite and converges
+    # at 32^3-64^3, but r . r0 is at the rounding level there too from iteration ~16 on
+    # (tests/test_bicgstab_restatement_cpu.py::test_rho_is_at_the_rounding_level): fp32 BiCGStab runs in near-breakdown on this operator.  A CPU
+    # sum with the kernels' exact partition that lands on the zero has not been shown, and 128^3 / 144^3 are too large for the suite to audit
     csr = gen.convdiff3d(grid, 0.3, dtype=dtype) if dtype == np.float64 else gen.poisson3d(grid, dtype=dtype)
     A = smm.CSRMatrix(n, n, *csr)
     b = gen.row_sums(csr[0], csr[2]).astype(dtype)
