@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 import torch
+from amg_cases import NAMES as GRAPH_CASES
+from amg_cases import case as graph_case
 from amg_restatement import coarse_inverse, dense_of, hierarchy, make_apply, operator_complexity, products
 from chebyshev_restatement import bicgstab, diagonal, gershgorin, pcg, sensitivity
 from device_views import assert_guards_intact, assert_unchanged, carve_like, fit, snapshot
@@ -25,6 +27,7 @@ pytestmark = pytest.mark.gpu
 DTYPES = [np.float32, np.float64]
 INVALID, PRECOND = -1, -4  # SMM_HIP_ERR_INVALID, SMM_HIP_ERR_PRECOND
 CASES = ("poisson2d_32", "stencil3d_12", "convdiff3d_12", "convdiff3d_20", "spd5", "poisson2d_32_c48")
+FIXED_STEPS = 5  # the passes of the fixed-step comparisons with the restated loops
 ids = lambda v: v.__name__ if isinstance(v, type) else str(v)  # noqa: E731
 
 _REF = {}
@@ -41,9 +44,10 @@ def bits(a):
 
 
 def reference(name, dtype):
-    """(csr, keyword arguments, the restated hierarchy, b = A 1, a fixed right-hand side), made once"""
+    """(csr, keyword arguments, the restated hierarchy, b = A 1, a fixed right-hand side), made once; the names of tests/amg_cases.py
+    (tests/test_gpu_amg_graphs.py) are served as well"""
     def compute():
-        csr, kw = case(name, dtype)
+        csr, kw = (graph_case if name in GRAPH_CASES else case)(name, dtype)
         n = len(csr[0]) - 1
         return csr, kw, hierarchy(csr, **kw), gen.row_sums(csr[0], csr[2]), np.random.default_rng(5).uniform(-1, 1, n).astype(dtype)
     return cached(("ref", name, np.dtype(dtype).name), compute)
@@ -254,7 +258,7 @@ def run(smm, solver, A, b, it, eps, M, dtype):
 @pytest.mark.parametrize("dtype", DTYPES, ids=ids)
 @pytest.mark.parametrize("solver,name", [("cg", "poisson2d_32"), ("cg", "stencil3d_12"), ("bicgstab", "convdiff3d_12"), ("gmres", "convdiff3d_12")])
 def test_fixed_steps_match_the_restated_loops(smm, oracle, solver, name, dtype):
-    it = 5
+    it = FIXED_STEPS
     csr, kw, _, b, _ = reference(name, dtype)
     st_ref, x_ref, it_ref, sens = restated(oracle, solver, name, dtype, it, 0.0)
     tol = allowed(x_ref, sens, dtype)
