@@ -469,6 +469,50 @@ int smm_hip_csr_multiply_create(const smm_hip_csr* a, const smm_hip_csr* b, smm_
 int smm_hip_csr_multiply_into_f32(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b, smm_hip_stream stream);
 int smm_hip_csr_multiply_into_f64(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b, smm_hip_stream stream);
 
+/* ---- the SUM C = alpha A + beta B of two matrices with ANY two patterns, built on the device (csrc/smm_add.hip); additions with no
+ * counterpart in the reference (inplaceAdd / inplaceSubtract, ref:1533-1549, and smm_hip_csr_axpy_* need equal patterns) -----------------
+ * Operands: `a` and `b` have the same rows, cols and dtype; the suffix names that dtype.  Anything else is SMM_HIP_ERR_INVALID.
+ *   The columns of every row of either operand must ASCEND STRICTLY.  Every matrix the library builds does (assembly, transpose, permute,
+ *   product, convert, the generators), and so does the reference's fillArrays (ref:1634-1635).  A flag on the device finds, before any
+ *   column is used as an address: a row whose columns do not ascend strictly (caller-made arrays), a column outside [0, cols), a start[]
+ *   that does not ascend from 0.  Each returns SMM_HIP_ERR_INVALID, never a fault, and creates nothing; smm_hip_last_error() names the
+ *   operand (a / b / c) and the first offending row.  A handle that has passed is not checked again.
+ *   Legal: rectangular matrices, empty rows in either operand, nnz == 0, rows == 0 or cols == 0, a == b.
+ * Pattern of C: (i, j) is stored iff it is stored in `a` or in `b`.  Rows ascend, columns ascend strictly inside a row.  Nothing is
+ *   dropped by value: an entry whose terms cancel, an explicitly stored zero, alpha == 0 or beta == 0 all keep their entries.  start[],
+ *   positions[] and what smm_hip_csr_info reports are those of smm_hip_csr_create_* for the same arrays built on the host.  The entry
+ *   count is kept in 64 bits while it is formed; more than 2^31 - 1 stored entries returns SMM_HIP_ERR_INVALID.
+ * Values: u = alpha * a_ij (one rounding) where `a` stores (i, j), v = beta * b_ij (one rounding) where `b` stores it;
+ *   c_ij = u + v (one more rounding) where both store it, u where only `a` does, v where only `b` does -- never u + 0: a lone -0.0 times
+ *   1 stays -0.0.  No _smm_fma, no contraction, no special-casing of alpha or beta: both library flavours give the same bits.  No
+ *   floating-point atomics: every stored entry of C is written exactly once by one lane, nothing depends on the launch geometry.
+ *   Consequences: with equal patterns, alpha = 1 gives the bits of smm_hip_csr_axpy_*(a, beta, b); for any patterns the result has the
+ *   bits of smm_hip_assembly_csr_create_* on the list that holds a's triplets with values alpha * a_ij followed by b's with beta * b_ij.
+ * add_create_*: *out owns its three arrays and does not depend on `a` or `b` -- an smm_hip_csr like any other (AUTO kernel choice, PATTERN
+ *   analysis on first use, edits, preconditioners, smm_hip_csr_same_pattern, transpose, product).  Synchronises `stream` (nnz is needed on
+ *   the host).
+ * add_into_*: the numeric phase alone, into the existing pattern of `c`: every stored entry of `c` gets the value defined above, an entry
+ *   neither operand stores gets +0.0.  No bookkeeping ties `c` to `a` or `b`.  Unlike multiply_into, `c` MAY BE `a`, `b`, OR BOTH: the
+ *   values are formed in scratch memory first, so A <- A + sigma D with D's pattern inside A's is one call.  An operand that stores an
+ *   entry `c` does not returns SMM_HIP_ERR_INVALID: `c` keeps all its old bits (values, pattern, kernel choice) and smm_hip_last_error()
+ *   names the first such row.  Order of work as in multiply_into_*: the values go into scratch (nnz(c) sizeof(T) bytes), the device flag is
+ *   read -- the call synchronises `stream` --, and only then the scratch becomes c's values (arrays the handle owns) or is copied into them
+ *   (caller-owned arrays).  On success it is a value edit of `c` with exactly the rules of smm_hip_csr_set_values_dev_*: what was derived
+ *   from the pattern stays (the next SpMV runs no analysis), what was derived from the values follows (constant diagonals re-verified, the
+ *   slots / sweep / single-launch copies; preconditioners by their own rules).  SMM_HIP_ERR_INVALID, nothing changed: a null handle, a
+ *   shape or dtype mismatch, bad input as above.
+ * How (a merge by ranking; nothing is sorted): a stored entry of `b` is new iff a binary search of a's row does not find its column; one
+ *   scan of those flags gives every entry of either operand its place in C.  Entries are dealt flat over lanes, so a 7-entry row and a
+ *   5 000-entry row load alike; the searched row segments sit in LDS when a workgroup's are at most 1024 columns.
+ * Cost (s = sizeof(T)): the operand check reads (nnz + rows) 4 bytes once per handle; create reads (nnz_a + nnz_b) 4 in the symbolic pass
+ *   (plus nnz_b 8 written and scanned) and (nnz_a + nnz_b)(s + 4) plus the search probes in the fill, and writes nnz_c (s + 4); into reads
+ *   (nnz_a + nnz_b)(s + 4) + nnz_c 4 plus the probes (the operands' columns once more to prove that c covers them) and writes nnz_c s.
+ * Distributed handles are not covered. */
+int smm_hip_csr_add_create_f32(const smm_hip_csr* a, float alpha, const smm_hip_csr* b, float beta, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_add_create_f64(const smm_hip_csr* a, double alpha, const smm_hip_csr* b, double beta, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_add_into_f32(smm_hip_csr* c, const smm_hip_csr* a, float alpha, const smm_hip_csr* b, float beta, smm_hip_stream stream);
+int smm_hip_csr_add_into_f64(smm_hip_csr* c, const smm_hip_csr* a, double alpha, const smm_hip_csr* b, double beta, smm_hip_stream stream);
+
 /* ---- a matrix in the OTHER PRECISION, converted on the device (csrc/smm_convert.hip); additions with no counterpart in the reference -------
  * convert_create: *out is `a`'s matrix with values of `dtype` (SMM_DTYPE_F32 or SMM_DTYPE_F64).  It owns its three device arrays -- start[]
  *   and positions[] are copies -- and does not depend on `a`'s lifetime: an smm_hip_csr like any other (AUTO kernel choice, PATTERN analysis

@@ -7,7 +7,7 @@
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
 //     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
-//     SMM::convert, SMM::IterativeRefinement)
+//     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
 //
 // compiles against this header unchanged and runs those calls on an MI355X: same names, same argument order and meaning,
 // same return values (SolverStatus; int != 0 on failure for init / apply).  Matrix assembly (TripletMatrix, CSR arrays)
@@ -85,6 +85,8 @@ struct Abi<float> {
 	static int assembled(const smm_hip_assembly* p, const float* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f32(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const float* v, int mode) { return smm_hip_assembly_refill_f32(p, m, v, mode); }
 	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f32(c, a, b, nullptr); }
+	static int addCreate(const smm_hip_csr* a, float alpha, const smm_hip_csr* b, float beta, smm_hip_csr** o) { return smm_hip_csr_add_create_f32(a, alpha, b, beta, nullptr, o); }
+	static int addInto(smm_hip_csr* c, const smm_hip_csr* a, float alpha, const smm_hip_csr* b, float beta) { return smm_hip_csr_add_into_f32(c, a, alpha, b, beta, nullptr); }
 	static int spmm(const smm_hip_csr* m, int op, int k, const float* l, const float* x, float* o) { return smm_hip_spmm_f32(m, op, k, l, x, o); }
 	static int bicgstabBatch(const smm_hip_csr* a, int k, float* b, float* x, int it, float eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_bicgstab_batch_f32(a, k, b, x, it, eps, M, st, nullptr, nullptr);
@@ -120,6 +122,8 @@ struct Abi<double> {
 	static int assembled(const smm_hip_assembly* p, const double* v, smm_hip_csr** o) { return smm_hip_assembly_csr_create_f64(p, v, o); }
 	static int refill(const smm_hip_assembly* p, smm_hip_csr* m, const double* v, int mode) { return smm_hip_assembly_refill_f64(p, m, v, mode); }
 	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f64(c, a, b, nullptr); }
+	static int addCreate(const smm_hip_csr* a, double alpha, const smm_hip_csr* b, double beta, smm_hip_csr** o) { return smm_hip_csr_add_create_f64(a, alpha, b, beta, nullptr, o); }
+	static int addInto(smm_hip_csr* c, const smm_hip_csr* a, double alpha, const smm_hip_csr* b, double beta) { return smm_hip_csr_add_into_f64(c, a, alpha, b, beta, nullptr); }
 	static int spmm(const smm_hip_csr* m, int op, int k, const double* l, const double* x, double* o) { return smm_hip_spmm_f64(m, op, k, l, x, o); }
 	static int bicgstabBatch(const smm_hip_csr* a, int k, double* b, double* x, int it, double eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_bicgstab_batch_f64(a, k, b, x, it, eps, M, st, nullptr, nullptr);
@@ -804,6 +808,58 @@ public:
 		deviceEdited(abi);
 		return abi;
 	}
+	// addition: this matrix becomes the sum alpha a + beta b of two matrices with ANY two patterns, built on the GPU through the two device
+	// mirrors (smm_hip.h "the SUM C = alpha A + beta B": the union of the patterns, columns ascending, u = alpha a, v = beta b, the entry
+	// u + v, u or v); the host arrays are filled from the device result and the built handle becomes this matrix's mirror.  Returns 0, or
+	// the SMM_HIP_* status (also in lastHipStatus()) with the matrix left empty.  a and b may be one matrix; neither may be this one (use
+	// addInto for that).  SMM::add(a, alpha, b, beta, out) is this call.
+	int initSumOf(const CSRMatrix& a, T alpha, const CSRMatrix& b, T beta) noexcept {
+		if (&a == this || &b == this) return detail::note(SMM_HIP_ERR_INVALID);
+		release();
+		values.reset();
+		positions.reset();
+		start.reset();
+		denseRowCount = denseColCount = firstActiveStart = 0;
+		const smm_hip_csr* da = a.device();
+		if (!da) return detail::note(a.start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const smm_hip_csr* db = b.device();
+		if (!db) return detail::note(b.start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(detail::Abi<T>::addCreate(da, alpha, db, beta, &d)) != SMM_HIP_OK) return lastHipStatus();
+		int rows = 0, cols = 0, nnz = 0;
+		int abi = smm_hip_csr_info(d, &rows, &cols, &nnz, nullptr, nullptr);
+		std::unique_ptr<T[]> v(new T[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> p(new int[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> s(new int[rows + 1]());
+		if (abi == SMM_HIP_OK) abi = smm_hip_csr_get_pattern(d, s.get(), p.get());
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(d, v.get());
+		if (detail::note(abi) != SMM_HIP_OK) {
+			smm_hip_csr_destroy(d);
+			return abi;
+		}
+		values = std::move(v);
+		positions = std::move(p);
+		start = std::move(s);
+		denseRowCount = rows;
+		denseColCount = cols;
+		computeFirstActive();
+		dev = d;
+		return 0;
+	}
+	// addition: the numeric phase alone -- this matrix's values become those of alpha a + beta b on ITS pattern (+0.0 where neither stores an
+	// entry), a bulk edit on the device like operator*=.  Unlike multiplyInto, a or b (or both) MAY BE THIS MATRIX: A.addInto(A, 1, D, sigma)
+	// is the shift A <- A + sigma D in place.  Non-zero (the SMM_HIP_* status, nothing changed): a or b stores an entry this matrix does
+	// not, the shapes do not fit, no GPU.  SMM::addInto(c, a, alpha, b, beta) is this call.
+	int addInto(const CSRMatrix& a, T alpha, const CSRMatrix& b, T beta) {
+		(void)device();
+		if (!flushedMirror()) return detail::note(start ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const smm_hip_csr* da = a.device();
+		const smm_hip_csr* db = b.device();
+		if (!da || !db) return detail::note((a.start && b.start) ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const int abi = detail::Abi<T>::addInto(dev, da, alpha, db, beta);
+		deviceEdited(abi);
+		return abi;
+	}
 	// addition: new values for a matrix made by init(plan, ...) from the same plan -- those of init(plan, valuesIn), or added to the present
 	// ones (add) -- in one device pass; the pattern and what the library derived from it stay.  Non-zero (the SMM_HIP_* status): not this
 	// plan's matrix, no GPU; nothing changed then.
@@ -1310,6 +1366,20 @@ inline int multiply(const CSRMatrix<T>& a, const CSRMatrix<T>& b, CSRMatrix<T>& 
 template <typename T>
 inline int multiplyInto(CSRMatrix<T>& c, const CSRMatrix<T>& a, const CSRMatrix<T>& b) {
 	return c.multiplyInto(a, b);
+}
+// out becomes alpha a + beta b over the union of the two patterns, built on the GPU (CSRMatrix::initSumOf); 0, or the SMM_HIP_* status with
+// out left empty
+template <typename T>
+inline int add(const CSRMatrix<T>& a, typename std::enable_if<true, T>::type alpha, const CSRMatrix<T>& b, typename std::enable_if<true, T>::type beta,
+               CSRMatrix<T>& out) noexcept {  // (the scalars are not deduced: add(a, 1, b, -1, out) works for float and double)
+	return out.initSumOf(a, alpha, b, beta);
+}
+// the values of c become those of alpha a + beta b on c's own pattern (CSRMatrix::addInto); c may be a, b or both; 0, or the SMM_HIP_*
+// status with c unchanged
+template <typename T>
+inline int addInto(CSRMatrix<T>& c, const CSRMatrix<T>& a, typename std::enable_if<true, T>::type alpha, const CSRMatrix<T>& b,
+                   typename std::enable_if<true, T>::type beta) {
+	return c.addInto(a, alpha, b, beta);
 }
 // BiCGSymmetric's text (ref:2021-2102) with the shadow sequence on `at`, the transpose of `a` (SMM::transpose): for matrices that are not
 // symmetric.  That `at` is the transpose is the caller's contract; `a` itself as `at` asserts symmetry and gives BiCGSymmetric's bits.

@@ -103,6 +103,8 @@ _TYPED = {
     "smm_hip_csr_transpose_refresh": (c_int, [_P, _P, _P]),
     "smm_hip_csr_permute_refresh": (c_int, [_P, _P, _P]),
     "smm_hip_csr_multiply_into": (c_int, [_P, _P, _P, _P]),
+    "smm_hip_csr_add_create": (c_int, [_P, "T", _P, "T", _P, POINTER(_P)]),
+    "smm_hip_csr_add_into": (c_int, [_P, _P, "T", _P, "T", _P]),
 }
 
 

@@ -221,6 +221,9 @@ struct smm_hip_csr {
 	// whether values[] holds finite numbers only: -1 not known, 1 yes, 0 an Inf or a NaN.  Found by one pass over values[] the first time a
 	// Krylov driver starts from x0 = 0 (zeroStart, smm_solver_host.h); back to -1 at every value edit (valuesEdited, smm_csr_update.hip)
 	mutable std::atomic<int> values_finite{-1};
+	// the operand check of smm_hip_csr_add_* (smm_add.hip) has passed: start[] ascends from 0 to nnz, every column lies in [0, cols), columns
+	// ascend strictly inside a row.  1 yes, 0 not checked yet; a failed check is not kept.  The pattern of a handle never changes.
+	mutable std::atomic<int> sorted_ok{0};
 };
 
 struct smm_hip_precond {

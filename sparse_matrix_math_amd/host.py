@@ -658,6 +658,34 @@ class CSRMatrix:
         check(_fn("smm_hip_csr_multiply_into", self._suf)(self._h, A._h, B._h, _dptr(stream)))
         self._edited(stream)
 
+    # ---- the sum of two matrices with any two patterns, built on the device (smm_hip.h "the SUM C = alpha A + beta B") ----
+    def add(self, B, alpha=1, beta=1, stream=None):
+        """alpha self + beta B as a new CSRMatrix that owns its arrays: the union of the two patterns (nothing dropped by value), columns
+        ascending; u = alpha a, v = beta b, the entry u + v, u or v -- the bits of the assembly of self's scaled triplets followed by B's.
+        Both matrices must hold strictly ascending columns in every row (SmmHipError otherwise).  Synchronises `stream`."""
+        if not isinstance(B, CSRMatrix):
+            raise TypeError("add needs a CSRMatrix")
+        h = ctypes.c_void_p()
+        check(_fn("smm_hip_csr_add_create", self._suf)(self._h, float(alpha), B._h, float(beta), _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, self.dtype)
+
+    def __add__(self, B):
+        if not isinstance(B, CSRMatrix):
+            return NotImplemented
+        return self.add(B)
+
+    def __sub__(self, B):
+        if not isinstance(B, CSRMatrix):
+            return NotImplemented
+        return self.add(B, 1, -1)
+
+    def add_into(self, A, B, alpha=1, beta=1, stream=None):
+        """the numeric phase alone: this matrix's values become those of alpha A + beta B on ITS pattern (+0.0 where neither stores an
+        entry) -- a value edit of this matrix, which may itself be A, B or both (A <- A + sigma D in place).  SmmHipError
+        (SMM_HIP_ERR_INVALID, nothing changed) when A or B stores an entry this matrix does not.  Synchronises `stream`."""
+        check(_fn("smm_hip_csr_add_into", self._suf)(self._h, A._h, float(alpha), B._h, float(beta), _dptr(stream)))
+        self._edited(stream)
+
     # ---- the other precision, converted on the device (smm_hip.h "a matrix in the OTHER PRECISION") ----
     def astype(self, dtype, stream=None):
         """this matrix with values of `dtype` (float32 / float64) as a new CSRMatrix that owns its arrays: float64 -> float32 rounds to
