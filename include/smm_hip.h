@@ -141,6 +141,44 @@ extern "C" {
 #define SMM_PRECOND_MULTICOLOR_SGS 9
 #define SMM_PRECOND_MULTICOLOR_ILU0 10
 #define SMM_PRECOND_MULTICOLOR_IC0 11
+/* FSAI and SPAI -- additions: preconditioners that ARE sparse matrices, so an apply is the library's SpMV (csrc/smm_precond_ainv.hip; the
+ * definition, line by line, is tests/ainv_restatement.py).  FSAI is for symmetric positive definite matrices: M^-1 = G^T G with G lower
+ * triangular and diag(G A G^T) = 1.  SPAI is for general matrices: M ~ A^-1, row i minimising ||e_i^T - m_i A||_2 over a fixed pattern.
+ *   pattern   Pat = a for power 1; for power p > 1 the structural product of p copies of a (smm_hip_csr_multiply_create; only the pattern
+ *             is used).  J_i = the distinct columns of row i of Pat, ascending; FSAI keeps the columns <= i only.  n = |J_i|.  i not in J_i
+ *             (a missing diagonal) and n > SMM_AINV_MAX_ROW are SMM_HIP_ERR_PRECOND; the message names the row (for n > 64 also n and the
+ *             power; a row of Pat whose columns do not ascend and that holds more than 64 distinct ones is reported by its stored entries).
+ *   source    look(X, r, c) = the value of the FIRST stored entry of row r of X with column c, +0.0 when there is none.
+ *             FSAI: Src = a, b = e_{n-1} (the 1 stands at i, the last of J_i).
+ *             SPAI: At = smm_hip_csr_transpose_create(a), Src = N = a At (smm_hip_csr_multiply_create), b[p] = look(At, i, J[p]).
+ *             S[p][q] = look(Src, J[p], J[q]) for q <= p; the upper triangle is never read.
+ *   solve     in the matrix dtype T, every operation rounding once, s - l m written _smm_fma(-l, m, s):
+ *               j = 0 .. n-1:  d = S[j][j]; not (d > 0) or not finite: the row FAILS; S[j][j] = sqrt(d)
+ *                              i > j:              S[i][j] = S[i][j] / S[j][j]
+ *                              i > j, j < k <= i:  S[i][k] = S[i][k] - S[i][j] S[k][j]
+ *               j = 0 .. n-1:  y[j] = b[j] / S[j][j];  i > j:  b[i] = b[i] - S[i][j] y[j]
+ *               j = n-1 .. 0:  y[j] = y[j] / S[j][j];  i < j:  y[i] = y[i] - S[j][i] y[j]
+ *             FSAI: row i of G on the columns J_i = y / sqrt(y[n-1]).  SPAI: row i of M on the columns J_i = y.
+ *             Every entry is updated in ascending j and nothing is summed across lanes: the bits are those of the sequential loops.
+ *             A failed row makes create and refresh return SMM_HIP_ERR_PRECOND naming the smallest such row: the matrix is not symmetric
+ *             positive definite (FSAI), or has dependent rows or is too ill-conditioned for T (SPAI solves NORMAL EQUATIONS: the condition
+ *             number of the row systems is that of a squared; fine for diagonally dominant matrices, fragile in fp32 otherwise).
+ *   result    G (or M) is an ordinary smm_hip_csr on the pattern J; Gt = smm_hip_csr_transpose_create(G).  The handle owns both.
+ *   apply     FSAI: w = G r, z = Gt w.  SPAI: z = M r.  The library's SpMV with SMM_OP_ASSIGN in whatever kernel family those matrices run.
+ *             Launches only, every launch honours the solver's done flag, and the kind itself allocates nothing in an apply; w belongs to
+ *             the handle, so ONE HANDLE MUST NOT BE APPLIED FROM TWO STREAMS AT ONCE.  What an SpMV of any matrix builds lazily on its
+ *             first launch in a kernel family (the tile table, the PATTERN analysis and its copies) is built by the first apply after
+ *             create, after smm_hip_csr_set_kernel on a borrowed handle, and re-verified after ainv_refresh, as for any other matrix.
+ * smm_hip_cg_* accepts FSAI (G^T G is symmetric positive definite whenever the create succeeded) and refuses SPAI (SMM_HIP_ERR_INVALID);
+ * smm_hip_bicgstab_*, smm_hip_gmres_* and the refinement driver's inner solves (the handle made on the fp32 matrix) accept both;
+ * smm_hip_precond_apply_spmv_* runs the SpMV and then the apply.  The batched, row-partitioned and single-launch paths refuse both kinds or
+ * are not taken, as for AMG.  smm_hip_precond_info reports 0 levels; smm_hip_precond_values_* returns the nnz values of G (FSAI) or M (SPAI).
+ * Memory: G and Gt (FSAI), or M, a^T and a a^T (SPAI; both kept for the refresh: about 7 + 25 entries per row for a 7-point stencil beside
+ * M's own 7 / 25 / 63 at power 1 / 2 / 3), each entry sizeof(T) + 4 bytes, Gt and a^T 4 more for the transpose's permutation.
+ * It is a SNAPSHOT: it does not follow a value edit of `a` -- call smm_hip_precond_ainv_refresh.
+ * smm_hip_precond_create(a, 12 | 13, &M) means power 1. */
+#define SMM_PRECOND_FSAI 12
+#define SMM_PRECOND_SPAI 13
 
 #define SMM_DTYPE_F32 0
 #define SMM_DTYPE_F64 1
@@ -948,6 +986,24 @@ int smm_hip_precond_multicolor_refresh(smm_hip_precond* M);
 int smm_hip_precond_multicolor_info(const smm_hip_precond* M, int* ncolors, int* bounds, size_t count);
 int smm_hip_precond_multicolor_perm(const smm_hip_precond* M, int* perm, size_t count);
 int smm_hip_precond_multicolor_matrix(const smm_hip_precond* M, smm_hip_csr** b);
+/* The approximate-inverse kinds (SMM_PRECOND_FSAI / SMM_PRECOND_SPAI, defined above) on the pattern of the power-th structural power of a.
+ * SMM_HIP_ERR_INVALID: a matrix that is not square, a kind other than 12 or 13, power outside 1 .. SMM_AINV_MAX_POWER, a column outside
+ * the matrix.  SMM_HIP_ERR_PRECOND: a missing diagonal, a row of the pattern longer than SMM_AINV_MAX_ROW, a failed row (above).  A matrix
+ * with no rows gives a handle whose apply does nothing.  Set-up: power - 1 symbolic products, (SPAI) one transpose and one product, one
+ * launch that gathers and solves all row systems out of LDS, (FSAI) one transpose.
+ * ainv_refresh: keeps every pattern and redoes the values from the present values of `a`: a^T by smm_hip_csr_transpose_refresh_*, a a^T by
+ *   smm_hip_csr_multiply_into_*, the solve, Gt by transpose_refresh; afterwards the handle equals a newly created one bit for bit.
+ *   Synchronous.  Errors as create's; on an error the handle must not be applied any more (destroy it).
+ * ainv_info: the power, the longest row of the pattern and the entries of G / M; any pointer may be NULL.
+ * ainv_matrix: G (FSAI) or M (SPAI) and Gt (NULL for SPAI) as BORROWED handles owned by M (do not destroy them; they die with M); they may
+ *   be read (smm_hip_csr_get_pattern / _get_values_*) and their kernel choice set (smm_hip_csr_set_kernel).  Either pointer may be NULL.
+ * The three queries return SMM_HIP_ERR_INVALID for a handle of another kind. */
+#define SMM_AINV_MAX_ROW 64
+#define SMM_AINV_MAX_POWER 4
+int smm_hip_precond_create_ainv(const smm_hip_csr* a, int kind, int power, smm_hip_precond** out);
+int smm_hip_precond_ainv_refresh(smm_hip_precond* M);
+int smm_hip_precond_ainv_info(const smm_hip_precond* M, int* power, int* max_row, size_t* nnz);
+int smm_hip_precond_ainv_matrix(const smm_hip_precond* M, smm_hip_csr** g, smm_hip_csr** gt);
 int smm_hip_precond_destroy(smm_hip_precond* M);
 int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower, int* levels_upper);
 /* How the two triangular sweeps of SGS / ILU0 / IC0 run (same numbers bit for bit either way):
@@ -977,7 +1033,8 @@ int smm_hip_precond_apply_spmv_dev_f64(const smm_hip_precond* M, const double* d
  * since the last call tripped the bound, and clears the flag.  The solver entry points call it themselves before they return. */
 int smm_hip_precond_take_error(const smm_hip_precond* M, smm_hip_stream stream);
 /* copies the factor values (ILU0 / IC0 / BLOCK_ILU0: nnz values on A's pattern -- for BLOCK_ILU0 the entries that couple two blocks
- * keep A's value; JACOBI, CHEBYSHEV, AMG: rows diagonal entries of (level 0 of) the matrix) to the host */
+ * keep A's value; JACOBI, CHEBYSHEV, AMG: rows diagonal entries of (level 0 of) the matrix; FSAI / SPAI: the values of G / M on their own
+ * pattern, smm_hip_precond_ainv_info tells how many) to the host */
 int smm_hip_precond_values_f32(const smm_hip_precond* M, float* out, size_t count);
 int smm_hip_precond_values_f64(const smm_hip_precond* M, double* out, size_t count);
 

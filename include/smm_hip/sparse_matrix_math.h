@@ -395,7 +395,7 @@ public:
 	public:
 		PreconditionerBase(const PreconditionerBase&) = delete;
 		PreconditionerBase& operator=(const PreconditionerBase&) = delete;
-		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h), cheb(o.cheb), amg(o.amg) { o.h = nullptr; }
+		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h), cheb(o.cheb), amg(o.amg), ainvPower(o.ainvPower) { o.h = nullptr; }
 		~PreconditionerBase() { smm_hip_precond_destroy(h); }
 		// non-zero on structural failure (missing / tiny diagonal, empty row, non-SPD pivot), like ref:1668-1693
 		// (every init / apply / handle goes through m->device(): entries queued by updateEntry / addEntry / setValue reach the matrix's
@@ -409,6 +409,9 @@ public:
 			}
 			if (kind == SMM_PRECOND_AMG) {
 				return detail::note(smm_hip_precond_create_amg(dev, amg.theta, amg.maxLevels, amg.coarseRows, amg.smoothDegree, amg.eigRatio, &h)) == SMM_HIP_OK ? 0 : 1;
+			}
+			if (kind == SMM_PRECOND_FSAI || kind == SMM_PRECOND_SPAI) {
+				return detail::note(smm_hip_precond_create_ainv(dev, kind, ainvPower, &h)) == SMM_HIP_OK ? 0 : 1;
 			}
 			return detail::note(smm_hip_precond_create(dev, kind, &h)) == SMM_HIP_OK ? 0 : 1;
 		}
@@ -434,6 +437,7 @@ public:
 			int maxLevels = 10, coarseRows = 256, smoothDegree = 2;
 			double eigRatio = 30.0;
 		} amg;
+		int ainvPower = 1;  // what smm_hip_precond_create_ainv takes (kinds FSAI / SPAI only)
 	};
 	class IDPreconditioner {  // ref:1166-1170
 	public:
@@ -526,6 +530,30 @@ public:
 			if (this->init()) return 1;
 			if (!this->m->device()) return 1;  // (queued entry edits reach the device first)
 			return detail::note(smm_hip_precond_amg_refresh(this->h)) == SMM_HIP_OK ? 0 : 1;
+		}
+	};
+
+	// addition: FSAI / SPAI (smm_hip.h, SMM_PRECOND_FSAI / SMM_PRECOND_SPAI): the preconditioner is a sparse matrix, an apply one or two SpMVs.
+	// kind SMM_PRECOND_FSAI (symmetric positive definite matrices; taken by ConjugateGradient, BiCGStab and GMRES) or SMM_PRECOND_SPAI (general
+	// matrices; BiCGStab and GMRES -- ConjugateGradient refuses it); power 1 .. SMM_AINV_MAX_POWER: the pattern is that of the power-th
+	// structural power of the matrix.  A snapshot of the matrix's values: refresh() follows a value edit with every pattern kept.
+	// One object serves one stream at a time (it owns the vector between its two SpMVs).
+	class ApproximateInversePreconditioner : public PreconditionerBase {
+	public:
+		ApproximateInversePreconditioner(const CSRMatrix& m, int kind = SMM_PRECOND_FSAI, int power = 1) noexcept : PreconditionerBase(m, kind) { this->ainvPower = power; }
+		ApproximateInversePreconditioner(ApproximateInversePreconditioner&&) noexcept = default;
+		int validate() noexcept { return this->init(); }
+		int power() const noexcept { return this->ainvPower; }
+		// the power, the longest row of the pattern and the entries of G / M (any may be null); non-zero when the preconditioner could not be made
+		int info(int* power, int* maxRow, size_t* nnz) const noexcept {
+			if (this->init()) return 1;
+			return detail::note(smm_hip_precond_ainv_info(this->h, power, maxRow, nnz)) == SMM_HIP_OK ? 0 : 1;
+		}
+		// the values again from the matrix's present values, every pattern kept
+		int refresh() noexcept {
+			if (this->init()) return 1;
+			if (!this->m->device()) return 1;  // (queued entry edits reach the device first)
+			return detail::note(smm_hip_precond_ainv_refresh(this->h)) == SMM_HIP_OK ? 0 : 1;
 		}
 	};
 
@@ -1192,6 +1220,19 @@ using AMGPreconditioner = typename CSRMatrix<T>::AMGPreconditioner;
 template <typename T>
 inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
                                       const typename CSRMatrix<T>::AMGPreconditioner& M) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = M.handle();
+	const int rc = d && h ? detail::Abi<T>::cg(d, b, x0, x, maxIterations, eps, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// addition: ... and with the factored approximate inverse (kind SMM_PRECOND_FSAI; SMM_PRECOND_SPAI is refused: DIVERGED, lastHipStatus() != 0)
+template <typename T>
+using ApproximateInversePreconditioner = typename CSRMatrix<T>::ApproximateInversePreconditioner;
+template <typename T>
+inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
+                                      const typename CSRMatrix<T>::ApproximateInversePreconditioner& M) {
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const smm_hip_precond* h = M.handle();

@@ -165,6 +165,10 @@ _PLAIN = {
     "smm_hip_precond_block_bounds": (c_int, [_P, _P, c_size_t]),
     "smm_hip_precond_create_chebyshev": (c_int, [_P, c_int, c_int, c_double, c_int, c_double, c_double, POINTER(_P)]),
     "smm_hip_precond_chebyshev_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_double)]),
+    "smm_hip_precond_create_ainv": (c_int, [_P, c_int, c_int, POINTER(_P)]),
+    "smm_hip_precond_ainv_refresh": (c_int, [_P]),
+    "smm_hip_precond_ainv_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]),
+    "smm_hip_precond_ainv_matrix": (c_int, [_P, POINTER(_P), POINTER(_P)]),
     "smm_hip_precond_create_amg": (c_int, [_P, c_double, c_int, c_int, c_int, c_double, POINTER(_P)]),
     "smm_hip_precond_amg_refresh": (c_int, [_P]),
     "smm_hip_precond_amg_info": (c_int, [_P, POINTER(c_int), _P, _P, c_size_t, POINTER(c_double)]),

@@ -238,6 +238,7 @@ struct smm_hip_precond {
 	struct smm_precond_cheb* cheb = nullptr;  // CHEBYSHEV: degree, bounds, coefficients and the two scratch vectors (smm_precond_cheb.hip)
 	struct smm_precond_mc* mc = nullptr;      // MULTICOLOR_*: the colouring, the permuted matrix B and the colour-by-colour sweeps (smm_precond_mc.hip); d_values: the factor on B's pattern
 	struct smm_precond_amg* amg = nullptr;    // AMG: the levels, their operators, smoothers and vectors, the dense coarse inverse (smm_precond_amg.hip); d_values: level 0's diag[rows]
+	struct smm_precond_ainv* ainv = nullptr;  // FSAI / SPAI: the pattern, G (and Gt) or M as matrices, the kept a^T and a a^T (smm_precond_ainv.hip); d_values: G's / M's values [nnz of it]
 };
 
 namespace smm {
@@ -594,11 +595,13 @@ constexpr PrecondKind PRECOND_KINDS[] = {
     {"MULTICOLOR_SGS",  true,  false, false, false, false, true},
     {"MULTICOLOR_ILU0", false, false, false, false, false, true},
     {"MULTICOLOR_IC0",  true,  true,  false, false, false, true},
+    {"FSAI",            true,  false, false, false, false, false},
+    {"SPAI",            false, false, false, false, false, false},
 };
 constexpr int N_PRECOND_KINDS = static_cast<int>(sizeof(PRECOND_KINDS) / sizeof(PRECOND_KINDS[0]));
 static_assert(SMM_PRECOND_NONE == 0 && SMM_PRECOND_JACOBI == 1 && SMM_PRECOND_ILU0 == 2 && SMM_PRECOND_SGS == 3 && SMM_PRECOND_IC0 == 4 && SMM_PRECOND_BLOCK_ILU0 == 5 &&
                   SMM_PRECOND_BLOCK_SGS == 6 && SMM_PRECOND_CHEBYSHEV == 7 && SMM_PRECOND_AMG == 8 && SMM_PRECOND_MULTICOLOR_SGS == 9 &&
-                  SMM_PRECOND_MULTICOLOR_ILU0 == 10 && SMM_PRECOND_MULTICOLOR_IC0 == 11 && N_PRECOND_KINDS == 12,
+                  SMM_PRECOND_MULTICOLOR_ILU0 == 10 && SMM_PRECOND_MULTICOLOR_IC0 == 11 && SMM_PRECOND_FSAI == 12 && SMM_PRECOND_SPAI == 13 && N_PRECOND_KINDS == 14,
               "PRECOND_KINDS is indexed by the SMM_PRECOND_* values");
 inline bool isBlockKind(int kind) { return kind >= 0 && kind < N_PRECOND_KINDS && PRECOND_KINDS[kind].block; }
 inline bool isMulticolorKind(int kind) { return kind >= 0 && kind < N_PRECOND_KINDS && PRECOND_KINDS[kind].multicolor; }
@@ -616,10 +619,12 @@ inline bool precondKindTaken(int kind, SolverClass c) {
 inline int precondAdmissible(const char* who, const smm_hip_precond* M, const smm_hip_csr* a, SolverClass c) {
 	if (!M || (c != SOLVER_CG && M->kind == SMM_PRECOND_NONE)) return SMM_HIP_OK;
 	if (precondKindTaken(M->kind, c) && M->a == a) return SMM_HIP_OK;
-	std::string names;
+	std::string names, inverses;  // (the approximate inverses come in a clause of their own: they take a parameter, the power)
 	for (int kind = SMM_PRECOND_NONE + 1; kind < N_PRECOND_KINDS; ++kind) {
-		if (precondKindTaken(kind, c)) names += std::string(names.empty() ? "" : " / ") + PRECOND_KINDS[kind].name;
+		std::string& list = kind == SMM_PRECOND_FSAI || kind == SMM_PRECOND_SPAI ? inverses : names;
+		if (precondKindTaken(kind, c)) list += std::string(list.empty() ? "" : " / ") + PRECOND_KINDS[kind].name;
 	}
+	if (!inverses.empty()) names += ", or " + inverses + " of any power,";
 	setError("%s: preconditioner must be %s %s", who, names.c_str(),
 	         c == SOLVER_DIST_LOCAL ? "of the local diagonal block (smm_hip_dist_csr_local_block)" : "created for this matrix");
 	return SMM_HIP_ERR_INVALID;
@@ -650,6 +655,11 @@ void chebDestroy(struct smm_precond_cheb* C);
 template <typename T>
 int amgApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
 void amgDestroy(struct smm_precond_amg* G);
+
+// FSAI / SPAI (smm_precond_ainv.hip): an apply is one or two of the library's SpMVs, launches only
+template <typename T>
+int ainvApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
+void ainvDestroy(struct smm_precond_ainv* A);
 
 // graph colouring and symmetric permutation of a handle (smm_color.hip); include/smm_hip.h states both rules
 // colours of the rows of a square, ready matrix into d_colors[rows] (device), *ncolors on the host; synchronises `s`

@@ -608,6 +608,7 @@ int precondApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* don
 	if (M->kind == SMM_PRECOND_CHEBYSHEV) return chebApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_AMG) return amgApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (isMulticolorKind(M->kind)) return mcApplyDev<T>(M, rhs, x, doneFlag, s);
+	if (M->kind == SMM_PRECOND_FSAI || M->kind == SMM_PRECOND_SPAI) return ainvApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_JACOBI) {
 		jacobiApplyKernel<T><<<sweepGrid(n), TPB, 0, s>>>(n, static_cast<const T*>(M->d_values), rhs, x, doneFlag);
 		SMM_HIP_TRY(hipGetLastError());
@@ -894,6 +895,7 @@ static int precondCreate(const smm_hip_csr* a, int kind, int blockRows, int leve
 	if (kind == SMM_PRECOND_CHEBYSHEV) return smm_hip_precond_create_chebyshev(a, 3, SMM_CHEB_BOUND_GERSHGORIN, 30.0, 10, 0.0, 0.0, out);  // the defaults
 	if (kind == SMM_PRECOND_AMG) return smm_hip_precond_create_amg(a, 0.08, 10, 256, 2, 30.0, out);  // the defaults
 	if (isMulticolorKind(kind)) return smm_hip_precond_create_multicolor(a, kind == SMM_PRECOND_MULTICOLOR_SGS ? SMM_PRECOND_SGS : kind == SMM_PRECOND_MULTICOLOR_ILU0 ? SMM_PRECOND_ILU0 : SMM_PRECOND_IC0, nullptr, 0, out);  // the library's own colouring
+	if (kind == SMM_PRECOND_FSAI || kind == SMM_PRECOND_SPAI) return smm_hip_precond_create_ainv(a, kind, 1, out);  // the pattern of a itself
 	if (kind < SMM_PRECOND_NONE || kind > SMM_PRECOND_BLOCK_SGS) {
 		setError("precond_create: unknown kind %d", kind);
 		return SMM_HIP_ERR_INVALID;
@@ -966,6 +968,7 @@ int smm_hip_precond_destroy(smm_hip_precond* M) {
 	chebDestroy(M->cheb);
 	amgDestroy(M->amg);
 	mcDestroy(M->mc);
+	ainvDestroy(M->ainv);  // (before d_values, which its matrix wraps)
 	planDestroy(M->plan);
 	devFree(M->d_values);
 	delete M;
@@ -986,7 +989,7 @@ int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower,
 		mcLevels(M->mc, levels_lower, levels_upper);
 		return SMM_HIP_OK;
 	}
-	if (levels_lower) *levels_lower = M->plan ? M->plan->lo.levels() : 0;  // (Jacobi, NONE, Chebyshev, AMG: no sweeps)
+	if (levels_lower) *levels_lower = M->plan ? M->plan->lo.levels() : 0;  // (Jacobi, NONE, Chebyshev, AMG, FSAI, SPAI: no sweeps)
 	if (levels_upper) *levels_upper = M->plan ? M->plan->up.levels() : 0;
 	return SMM_HIP_OK;
 }

@@ -29,7 +29,8 @@ class SolverPreconditioner(enum.IntEnum):
     """ref:1002-1006 has NONE, SYMMETRIC_GAUS_SEIDEL (sic) and ILU0; JACOBI, IC0 and the BLOCK_ forms (ILU0 / SGS of the
     block-diagonal part of A, one wavefront per block) are additions, and so is CHEBYSHEV (a polynomial in D^-1 A: SpMVs and
     element-wise passes only), AMG (smoothed-aggregation multigrid, a symmetric V-cycle) and the MULTICOLOR_ forms (SGS / ILU0 / IC0 of the
-    matrix renumbered colour by colour: a handful of dependent levels per sweep).  Values are the SMM_PRECOND_* codes of the C ABI."""
+    matrix renumbered colour by colour: a handful of dependent levels per sweep) and FSAI / SPAI (approximate inverses that are sparse
+    matrices themselves: an apply is one or two SpMVs).  Values are the SMM_PRECOND_* codes of the C ABI."""
     NONE = 0
     JACOBI = 1
     ILU0 = 2
@@ -42,6 +43,8 @@ class SolverPreconditioner(enum.IntEnum):
     MULTICOLOR_SGS = 9
     MULTICOLOR_ILU0 = 10
     MULTICOLOR_IC0 = 11
+    FSAI = 12
+    SPAI = 13
 
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
@@ -51,6 +54,7 @@ SWEEP_AUTO, SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD = 0, 1, 2, 3
 CHEB_BOUND_GERSHGORIN, CHEB_BOUND_POWER, CHEB_BOUND_USER = 0, 1, 2  # SMM_CHEB_BOUND_*: where a Chebyshev preconditioner's bounds come from
 _MULTICOLOR_BASE = {SolverPreconditioner.MULTICOLOR_SGS: SolverPreconditioner.SYMMETRIC_GAUS_SEIDEL, SolverPreconditioner.MULTICOLOR_ILU0: SolverPreconditioner.ILU0,
                     SolverPreconditioner.MULTICOLOR_IC0: SolverPreconditioner.IC0}
+_AINV_KINDS = (SolverPreconditioner.FSAI, SolverPreconditioner.SPAI)
 _CHEB_BOUNDS = {"GERSHGORIN": CHEB_BOUND_GERSHGORIN, "POWER": CHEB_BOUND_POWER, "USER": CHEB_BOUND_USER}
 
 _SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
@@ -166,7 +170,7 @@ def profile_read_waits(reset=True):
 class Preconditioner:
     """`int apply(const T* rhs, T* x) const` (ref:1173-1235).  Created by CSRMatrix.getPreconditioner."""
 
-    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None, colors=None):
+    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None, colors=None, power=None):
         self.matrix = matrix  # keeps the matrix alive (the reference holds a const CSRMatrix&)
         self.kind = SolverPreconditioner(kind)
         self._h = ctypes.c_void_p()
@@ -177,6 +181,8 @@ class Preconditioner:
         elif amg is not None:  # (theta, max_levels, coarse_rows, smooth_degree, eig_ratio): AMG with chosen parameters
             theta, max_levels, coarse_rows, smooth_degree, ratio = amg
             check(_lib.load().smm_hip_precond_create_amg(matrix._h, float(theta), int(max_levels), int(coarse_rows), int(smooth_degree), float(ratio), ctypes.byref(self._h)))
+        elif power is not None:  # FSAI / SPAI on the pattern of the power-th structural power of the matrix
+            check(_lib.load().smm_hip_precond_create_ainv(matrix._h, int(kind), int(power), ctypes.byref(self._h)))
         elif colors is not None:  # MULTICOLOR_ kinds with the caller's colouring (one colour per row)
             colors = np.ascontiguousarray(colors, dtype=np.int32)
             check(_lib.load().smm_hip_precond_create_multicolor(matrix._h, int(_MULTICOLOR_BASE[self.kind]), _host(colors, np.int32, "colors"), colors.size,
@@ -317,10 +323,37 @@ class Preconditioner:
         """MULTICOLOR_ kinds: keep the colouring, redo the permuted values and the factor from the matrix's present values.  Synchronous."""
         check(_lib.load().smm_hip_precond_multicolor_refresh(self._h))
 
+    def ainv_info(self):
+        """FSAI / SPAI: {power, max_row (the longest row of the pattern), nnz (the entries of G / M)}"""
+        power, max_row, nnz = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+        check(_lib.load().smm_hip_precond_ainv_info(self._h, ctypes.byref(power), ctypes.byref(max_row), ctypes.byref(nnz)))
+        return {"power": power.value, "max_row": max_row.value, "nnz": int(nnz.value)}
+
+    def ainv_matrix(self):
+        """FSAI: (G, Gt); SPAI: (M, None) -- CSRMatrix objects around handles this preconditioner OWNS (closing them does nothing)"""
+        hs = [ctypes.c_void_p(), ctypes.c_void_p()]
+        check(_lib.load().smm_hip_precond_ainv_matrix(self._h, ctypes.byref(hs[0]), ctypes.byref(hs[1])))
+        out = []
+        for h in hs:
+            if not h:
+                out.append(None)
+                continue
+            m = CSRMatrix._adopt(h, self.matrix.dtype)
+            m._borrowed = True
+            m._keep = self
+            out.append(m)
+        return tuple(out)
+
+    def ainv_refresh(self):
+        """FSAI / SPAI: keep every pattern, redo the values from the matrix's present values (after a value edit).  Synchronous."""
+        check(_lib.load().smm_hip_precond_ainv_refresh(self._h))
+
     def values(self):
         """factor values: diag (JACOBI, CHEBYSHEV, AMG) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern (MULTICOLOR_ILU0 / _IC0: on
-        the permuted matrix's pattern)"""
+        the permuted matrix's pattern); FSAI / SPAI: the values of G / M on their own pattern (ainv_matrix)"""
         count = self.matrix.rows if self.kind in (SolverPreconditioner.JACOBI, SolverPreconditioner.CHEBYSHEV, SolverPreconditioner.AMG) else self.matrix.nnz
+        if self.kind in _AINV_KINDS:
+            count = self.ainv_info()["nnz"]
         out = np.empty(count, dtype=self.matrix.dtype)
         check(_fn("smm_hip_precond_values", self.matrix._suf)(self._h, _host(out, self.matrix.dtype, "out"), count))
         return out
@@ -712,13 +745,20 @@ class CSRMatrix:
         check(_fn(name, self._suf)(self._h, int(op), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), int(dot_mode), _dptr(d_w1), _dptr(d_partials), _dptr(stream)))
 
     def getPreconditioner(self, kind, block_rows=None, level_cap=None, partition=None, degree=None, bound=None, eig_ratio=None, power_steps=None,
-                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None, colors=None):
+                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None, colors=None, power=None):
         """ref:1643-1651.  kind: a SolverPreconditioner or its name ("CHEBYSHEV").  block_rows / level_cap / partition: BLOCK_ kinds only;
         degree (3) / bound ("GERSHGORIN", "POWER", "USER" or a CHEB_BOUND_* code) / eig_ratio (30) / power_steps (10) / lambda_min /
         lambda_max (USER): CHEBYSHEV only; theta (0.08) / max_levels (10) / coarse_rows (256) / smooth_degree (2) and eig_ratio (30): AMG only.
-        colors (one per row; None = CSRMatrix.color's): MULTICOLOR_ kinds only.  None = the default."""
+        colors (one per row; None = CSRMatrix.color's): MULTICOLOR_ kinds only; power (1 .. 4; 1): FSAI / SPAI only.  None = the default."""
         if isinstance(kind, str):
             kind = SolverPreconditioner[kind]
+        if power is not None:
+            if SolverPreconditioner(kind) not in _AINV_KINDS:
+                raise ValueError("power belongs to the FSAI / SPAI preconditioners")
+            if any(v is not None for v in (block_rows, level_cap, partition, degree, bound, eig_ratio, power_steps, lambda_min, lambda_max, theta, max_levels,
+                                           coarse_rows, smooth_degree, colors)):
+                raise ValueError("the FSAI / SPAI preconditioners take power only")
+            return Preconditioner(self, kind, power=power)
         if colors is not None:
             if SolverPreconditioner(kind) not in _MULTICOLOR_BASE:
                 raise ValueError("colors belongs to the MULTICOLOR_ preconditioners")
