@@ -1023,7 +1023,13 @@ int smm_hip_precond_apply_dev_f64(const smm_hip_precond* M, const double* d_rhs,
 /* x = M^-1 (A v), A being the matrix M was created for: the operator a preconditioned loop applies twice per pass (ref:2234-2235,
  * 2250-2251).  BLOCK_ILU0 / BLOCK_SGS form A v inside the apply's launch, each row summed in the order of its stored entries (the
  * reference's rMult, ref:1484-1489) -- no SpMV launch, A v never travels through memory; every other kind runs the SpMV and then the
- * apply.  v must not alias x. */
+ * apply.  For the BLOCK_ kinds the result is bit for bit that of smm_hip_spmv_* followed by smm_hip_precond_apply_* ONLY WHILE THE
+ * MATRIX RUNS ONE LANE PER ROW (smm_hip_csr_get_kernel): with L > 1 lanes the SpMV kernels sum a row in L pieces, this call still sums
+ * it as one chain, and the two agree to rounding only.  smm_hip_bicgstab_* with a BLOCK_ kind uses this call or the two launches,
+ * decided per solve from the block count against the device's compute units, from whether the PATTERN analysis has run on the matrix
+ * and from SMM_HIP_BLOCK_FUSE_SPMV; so with L > 1 the iterates of the same solve may differ in the last bits, and a converged run in its
+ * pass count, between devices, between the first and a later solve on one handle, and with that switch
+ * (tests/test_gpu_precond_block_lanes.py bounds both).  v must not alias x. */
 int smm_hip_precond_apply_spmv_f32(const smm_hip_precond* M, const float* v, float* x);
 int smm_hip_precond_apply_spmv_f64(const smm_hip_precond* M, const double* v, double* x);
 int smm_hip_precond_apply_spmv_dev_f32(const smm_hip_precond* M, const float* d_v, float* d_x, smm_hip_stream stream);
