@@ -483,6 +483,7 @@ public:
 	// addition: a Chebyshev polynomial in D^-1 A (smm_hip.h, SMM_PRECOND_CHEBYSHEV): SpMVs and element-wise passes only, symmetric positive
 	// definite for such a matrix -- taken by ConjugateGradient, BiCGStab and GMRES.  boundMode: SMM_CHEB_BOUND_GERSHGORIN / _POWER (a heuristic,
 	// not a bound) / _USER (lambdaMin, lambdaMax are the caller's).  One object serves one stream at a time (it owns its scratch vectors).
+	// Any number of host threads may share it on that stream: an apply is enqueued whole.
 	class ChebyshevPreconditioner : public PreconditionerBase {
 	public:
 		ChebyshevPreconditioner(const CSRMatrix& m, int degree = 3, int boundMode = SMM_CHEB_BOUND_GERSHGORIN, double eigRatio = 30.0, int powerSteps = 10,
@@ -508,6 +509,7 @@ public:
 	// not grow with the grid; symmetric positive definite for such a matrix -- taken by ConjugateGradient, BiCGStab and GMRES (matrices that
 	// are not symmetric: the last two only).  A snapshot of the matrix's values: refresh() follows a value edit with the aggregates kept.
 	// One object serves one stream at a time (it owns its level vectors).
+	// Any number of host threads may share it on that stream: an apply is enqueued whole.
 	class AMGPreconditioner : public PreconditionerBase {
 	public:
 		AMGPreconditioner(const CSRMatrix& m, double theta = 0.08, int maxLevels = 10, int coarseRows = 256, int smoothDegree = 2, double eigRatio = 30.0) noexcept
@@ -538,6 +540,7 @@ public:
 	// matrices; BiCGStab and GMRES -- ConjugateGradient refuses it); power 1 .. SMM_AINV_MAX_POWER: the pattern is that of the power-th
 	// structural power of the matrix.  A snapshot of the matrix's values: refresh() follows a value edit with every pattern kept.
 	// One object serves one stream at a time (it owns the vector between its two SpMVs).
+	// Any number of host threads may share it on that stream: an apply is enqueued whole.
 	class ApproximateInversePreconditioner : public PreconditionerBase {
 	public:
 		ApproximateInversePreconditioner(const CSRMatrix& m, int kind = SMM_PRECOND_FSAI, int power = 1) noexcept : PreconditionerBase(m, kind) { this->ainvPower = power; }
@@ -561,6 +564,7 @@ public:
 	// dependent levels as there are colours.  Base: SGSPreconditioner, ILU0Preconditioner or IC0Preconditioner; usable wherever Base is, and
 	// MulticolorPreconditioner<SGSPreconditioner> in ConjugateGradient as well.  A snapshot of the matrix's values: refresh() follows a value
 	// edit with the colouring kept.  One object serves one stream at a time (it owns the vector its sweeps work on).
+	// Any number of host threads may share it on that stream: an apply is enqueued whole.
 	template <typename Base>
 	class MulticolorPreconditioner : public PreconditionerBase {
 		static_assert(std::is_same<Base, SGSPreconditioner>::value || std::is_same<Base, ILU0Preconditioner>::value || std::is_same<Base, IC0Preconditioner>::value,

@@ -239,6 +239,12 @@ struct smm_hip_precond {
 	struct smm_precond_mc* mc = nullptr;      // MULTICOLOR_*: the colouring, the permuted matrix B and the colour-by-colour sweeps (smm_precond_mc.hip); d_values: the factor on B's pattern
 	struct smm_precond_amg* amg = nullptr;    // AMG: the levels, their operators, smoothers and vectors, the dense coarse inverse (smm_precond_amg.hip); d_values: level 0's diag[rows]
 	struct smm_precond_ainv* ainv = nullptr;  // FSAI / SPAI: the pattern, G (and Gt) or M as matrices, the kept a^T and a a^T (smm_precond_ainv.hip); d_values: G's / M's values [nnz of it]
+	// CHEBYSHEV / AMG / MULTICOLOR_* / FSAI keep ONE set of work vectors in the handle and an apply is several launches: they are enqueued
+	// under this lock, so applies issued by several host threads on one stream stay whole (the stream then runs them one after the
+	// other), as the exact kinds' are under their plan's enqueueMutex.  Order: an AMG handle's lock, then a level's Chebyshev handle's
+	// (amgCycle); a level's handle never reaches the AMG handle, so the order cannot invert.  After the first use of the matrices involved (a first SpMV builds
+	// its tile table: it allocates and synchronises) it is held around launches only.
+	mutable std::mutex enqueueMutex;
 };
 
 namespace smm {

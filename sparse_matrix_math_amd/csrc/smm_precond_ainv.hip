@@ -436,6 +436,7 @@ int ainvApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFl
 	}
 	if (M->kind == SMM_PRECOND_SPAI) return launchSpmv<T>(A->G, SMM_OP_ASSIGN, nullptr, rhs, x, 0, nullptr, nullptr, doneFlag, s);  // z = M r
 	T* w = static_cast<T*>(A->d_w);
+	std::lock_guard<std::mutex> whole(M->enqueueMutex);  // d_w is the handle's: the two SpMVs stay together
 	SMM_TRY(launchSpmv<T>(A->G, SMM_OP_ASSIGN, nullptr, rhs, w, 0, nullptr, nullptr, doneFlag, s));  // w = G r
 	return launchSpmv<T>(A->Gt, SMM_OP_ASSIGN, nullptr, w, x, 0, nullptr, nullptr, doneFlag, s);     // z = Gt w
 }

@@ -515,6 +515,7 @@ int amgApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFla
 		setError("precond_apply: the multigrid preconditioner has no hierarchy");
 		return SMM_HIP_ERR_INVALID;
 	}
+	std::lock_guard<std::mutex> whole(M->enqueueMutex);  // every level's x, b, r, d are the handle's: one cycle's launches stay together
 	return amgCycle<T>(G, 0, rhs, x, doneFlag, s);
 }
 

@@ -148,6 +148,7 @@ int chebApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFl
 	T* q = static_cast<T*>(C->q);
 	T* d = static_cast<T*>(C->d);
 	const int degree = C->degree;
+	std::lock_guard<std::mutex> whole(M->enqueueMutex);  // q and d are the handle's: one apply's launches stay together
 	SMM_LAUNCH_UPDATE(chebFirstKernel, updateNT(n, sizeof(T), degree > 0 ? 4 : 3), g, s, n, static_cast<T>(C->invTheta), degree > 0 ? 1 : 0, rhs, diag, d, x, doneFlag);
 	for (int k = 1; k <= degree; ++k) {
 		SMM_TRY(launchSpmv<T>(M->a, SMM_OP_SUB, rhs, x, q, 0, nullptr, nullptr, doneFlag, s));  // q = r - A z

@@ -132,6 +132,7 @@ int mcApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag
 	}
 	const T* vals = static_cast<const T*>(C->base == SMM_PRECOND_SGS ? C->B->d_values : M->d_values);  // SGS sweeps B itself, ILU0 / IC0 their factor
 	const PermutedIO<T> io{C->d_perm, rhs, static_cast<T*>(C->d_y), x};
+	std::lock_guard<std::mutex> whole(M->enqueueMutex);  // d_y is the handle's: the launches of the two sweeps stay together
 	return withSweepModes(C->base, [&](auto lo, auto up) -> int {
 		SMM_TRY((runLevelSweep<T, decltype(lo)::value, PermutedIO<T>, false>(C->colours, false, C->B, vals, io, doneFlag, s)));
 		return runLevelSweep<T, decltype(up)::value, PermutedIO<T>, false>(C->colours, true, C->B, vals, io, doneFlag, s);

@@ -195,19 +195,28 @@ def test_fused_dot_entry_point(smm, oracle):
 
 
 def test_concurrent_host_api_solves(smm, oracle):
-    """the reference's solvers are re-entrant on a const matrix: two threads solve on the same matrix"""
+    """the reference's solvers are re-entrant on a const matrix: four threads solve on the same matrix, each with
+    a right-hand side of its own (a vector shared by mistake then holds foreign data), and get the bits of the same solve made alone
+    (tests/test_gpu_concurrent.py has the other solvers, the preconditioners and the overlap condition)"""
     csr = gen.poisson2d(40, dtype=np.float64)
     n = len(csr[0]) - 1
     A = smm.CSRMatrix(n, n, *csr)
-    b = gen.row_sums(csr[0], csr[2])
-    _, x_ref, _, _ = oracle.cg(csr, b, np.zeros(n), -1, 1e-10)
+    bs = [gen.row_sums(csr[0], csr[2]) + np.random.default_rng(i).uniform(-1, 1, n) for i in range(4)]
+    x_refs = [oracle.cg(csr, b, np.zeros(n), -1, 1e-10)[1] for b in bs]
+
+    def solve(i):
+        x = np.zeros(n)
+        st = smm.ConjugateGradient(A, bs[i], x, x, -1, 1e-10) if i % 2 == 0 else smm.BiCGStab(A, bs[i].copy(), x, -1, 1e-10)
+        return int(st), x
+
+    alone = [solve(i) for i in range(4)]
     results, errors = [None] * 4, []
+    gate = threading.Barrier(4)
 
     def work(i):
         try:
-            x = np.zeros(n)
-            st = smm.ConjugateGradient(A, b, x, x, -1, 1e-10) if i % 2 == 0 else smm.BiCGStab(A, b.copy(), x, -1, 1e-10)
-            results[i] = (int(st), x)
+            gate.wait()
+            results[i] = solve(i)
         except Exception as e:  # noqa: BLE001
             errors.append(e)
 
@@ -217,9 +226,10 @@ def test_concurrent_host_api_solves(smm, oracle):
     for t in threads:
         t.join()
     assert not errors, errors
-    for st, x in results:
-        assert st == 0
+    for (st, x), x_ref, (st_alone, x_alone) in zip(results, x_refs, alone):
+        assert st == 0 == st_alone
         np.testing.assert_allclose(x, x_ref, rtol=1e-7, atol=1e-9)
+        np.testing.assert_array_equal(x.view(np.uint64), x_alone.view(np.uint64))
 
 
 @pytest.mark.parametrize("kind", ["convdiff64_auto_adopts", "iid_auto_refuses"])
