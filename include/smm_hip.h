@@ -819,6 +819,64 @@ int smm_hip_gmres_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, in
 int smm_hip_gmres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, int restart, const smm_hip_precond* M,
                           smm_hip_stream stream, int* solver_status, int* iterations, double* resnorm2);
 
+/* smm_hip_idrs_*: IDR(s) in the biorthogonal form (Sonneveld and van Gijzen 2008; van Gijzen and Sonneveld 2011) with right
+ * preconditioning -- an addition, the reference has no IDR(s) (csrc/smm_solvers_idrs.hip; the definition, line by line, is
+ * tests/idrs_restatement.py).  For general matrices: transpose-free, one SpMV per step, recurrences of the fixed length s with no
+ * restart, and s shadow vectors where BiCGStab has one (s = 1 is mathematically BiCGStab).
+ * Semantics (x in/out; `iterations` counts SpMVs: every inner step and every dimension-reduction step is one):
+ *   maxIterations < 0 means rows; there is no other clamp
+ *   r = b - A x;  rr = r.r;  G = U = 0 (rows x s);  M = I (s x s);  om = 1
+ *   while (rr > eps*eps && iterations < maxIterations) {                               -- a cycle
+ *     f = P^T r                                                      (s dot products)
+ *     for k = 0 .. s-1:
+ *       c[k:] = solve(lower(M[k:, k:]), f[k:])                       forward substitution
+ *       v = r;  v = _smm_fma(-c_i, G_i, v), i = k .. s-1 ascending
+ *       z = M^-1 v                                                   (right preconditioning: the residual tested is the recurrence
+ *                                                                     residual of the original system)
+ *       u = om * z;  u = _smm_fma(c_i, U_i, u), i = k .. s-1 ascending
+ *       g = A u;  h = P^T g                                          (s dot products, all from the same g)
+ *       a_i = (h_i - sum_{j<i} M[i][j] a_j) / M[i][i], i < k         (one pass of classical Gram-Schmidt against the biorthogonal set)
+ *       g = _smm_fma(-a_i, G_i, g);  u = _smm_fma(-a_i, U_i, u), i < k ascending;  G_k = g;  U_k = u
+ *       M[i][k] = h_i - sum_{j<k} M[i][j] a_j for i >= k, 0 for i < k (algebraic: no second product pass)
+ *       M[k][k] == 0 or not finite: DIVERGED, x and r as they are, the solve ends
+ *       beta = f_k / M[k][k];  r = _smm_fma(-beta, g, r);  x = _smm_fma(beta, u, x);  rr = r.r;  iterations++
+ *       !(rr > eps*eps && iterations < maxIterations): the solve ends
+ *       f_i = f_i - beta M[i][k], i > k
+ *     z = M^-1 r;  t = A z;  tt = t.t;  tr = t.r
+ *     tt == 0 or not finite: DIVERGED, the solve ends
+ *     rho = |tr| / sqrt(tt * rr);  om = tr / tt;  if (rho < 0.7) om = om * (0.7 / rho)       ("maintaining the convergence")
+ *     x = _smm_fma(om, z, x);  r = _smm_fma(-om, t, r);  rr = r.r;  iterations++
+ *   }
+ *   status: SUCCESS iff the last rr <= eps*eps; else DIVERGED on the two tests above; else MAX_ITERATIONS_REACHED (a NaN rr leaves
+ *   the loop and reports MAX_ITERATIONS_REACHED unless one of the two tests fired)
+ * maxIterations == 0, rows == 0 and an x that already passes the test take no step: x untouched; SUCCESS in the last two cases.
+ * The shadow space P: 1 <= s <= SMM_IDRS_MAX_S columns of `rows` elements.  smm_hip_idrs_dev_*: d_P != NULL is a device array, column i
+ *   at d_P + i * ldP (ldP >= rows; element alignment suffices), read only and used as given; d_P == NULL: the library generates P from
+ *   `seed` for the duration of the call, as smm_hip_idrs_* (host vectors) always does.
+ * smm_hip_idrs_shadow_dev_*: fills d_P (column i at d_P + i * ld) the way the library generates it, so that a caller who solves many
+ *   systems keeps one P: element (row, col) = ((h >> 40) + 0.5) 2^-23 - 1 with h = sm(sm(sm(seed) ^ col) ^ row), sm(z) the splitmix64
+ *   step (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31) -- exact
+ *   in fp32 and fp64 -- then the columns are made orthonormal by classical Gram-Schmidt applied twice, column by column, and a division
+ *   by the norm.  Synchronises `stream`.  A solve with this P passed in (16-byte aligned, ld a multiple of 64) gives the bits of the
+ *   solve that generates it from the same seed.  s > rows gives dependent columns: no error, the solve reports what the loop makes of it.
+ * M: NULL, or any kind smm_hip_gmres_* accepts, created for `a`.
+ * Memory: 3 s vectors (G, U and P, leading dimension rounded up to 64; 2 s with a caller's P) plus two (four with a preconditioner).
+ * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one solve give the same bits.
+ * SMM_HIP_ERR_INVALID: s outside 1 .. SMM_IDRS_MAX_S, ldP < rows with a d_P, a null or dtype-mismatched matrix, a matrix that is not
+ * square, null vectors with rows > 0, a preconditioner of another matrix or kind; x is not touched.
+ * Additive outputs (may be NULL, like solver_status): iterations, resnorm2 = the last rr. */
+#define SMM_IDRS_MAX_S 8
+int smm_hip_idrs_f32(const smm_hip_csr* a, float* b, float* x, int maxIterations, float eps, int s, const smm_hip_precond* M, unsigned long long seed,
+                     int* solver_status, int* iterations, float* resnorm2);
+int smm_hip_idrs_f64(const smm_hip_csr* a, double* b, double* x, int maxIterations, double eps, int s, const smm_hip_precond* M, unsigned long long seed,
+                     int* solver_status, int* iterations, double* resnorm2);
+int smm_hip_idrs_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, int maxIterations, float eps, int s, const smm_hip_precond* M, const float* d_P,
+                         long long ldP, unsigned long long seed, smm_hip_stream stream, int* solver_status, int* iterations, float* resnorm2);
+int smm_hip_idrs_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, int s, const smm_hip_precond* M, const double* d_P,
+                         long long ldP, unsigned long long seed, smm_hip_stream stream, int* solver_status, int* iterations, double* resnorm2);
+int smm_hip_idrs_shadow_dev_f32(int n, int s, unsigned long long seed, float* d_P, long long ld, smm_hip_stream stream);
+int smm_hip_idrs_shadow_dev_f64(int n, int s, unsigned long long seed, double* d_P, long long ld, smm_hip_stream stream);
+
 /* smm_hip_refine_*: MIXED-PRECISION ITERATIVE REFINEMENT -- an fp64 answer from fp32 solves; an addition, the reference has none
  * (csrc/smm_solvers_refine.hip; the definition, line by line, is tests/refine_restatement.py).
  * `a` is the fp64 matrix, `a32` an fp32 matrix of the same rows, cols and nnz: a's values rounded (smm_hip_csr_convert_create(a,

@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
 //
@@ -74,6 +74,9 @@ struct Abi<float> {
 	static int gmres(const smm_hip_csr* a, float* b, float* x, int it, float eps, int restart, const smm_hip_precond* M, int* st) {
 		return smm_hip_gmres_f32(a, b, x, it, eps, restart, M, st, nullptr, nullptr);
 	}
+	static int idrs(const smm_hip_csr* a, float* b, float* x, int it, float eps, int s, const smm_hip_precond* M, int* st) {
+		return smm_hip_idrs_f32(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
+	}
 	static int bicg(const smm_hip_csr* a, const smm_hip_csr* at, float* b, float* x, int it, float eps, int* st) { return smm_hip_bicg_f32(a, at, b, x, it, eps, st, nullptr, nullptr); }
 	static int apply(const smm_hip_precond* M, const float* r, float* x) { return smm_hip_precond_apply_f32(M, r, x); }
 	static int scale(smm_hip_csr* m, float a) { return smm_hip_csr_scale_f32(m, a, nullptr); }
@@ -110,6 +113,9 @@ struct Abi<double> {
 	static int cgs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int* st) { return smm_hip_cgs_f64(a, b, x, it, eps, st, nullptr, nullptr); }
 	static int gmres(const smm_hip_csr* a, double* b, double* x, int it, double eps, int restart, const smm_hip_precond* M, int* st) {
 		return smm_hip_gmres_f64(a, b, x, it, eps, restart, M, st, nullptr, nullptr);
+	}
+	static int idrs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int s, const smm_hip_precond* M, int* st) {
+		return smm_hip_idrs_f64(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
 	}
 	static int bicg(const smm_hip_csr* a, const smm_hip_csr* at, double* b, double* x, int it, double eps, int* st) { return smm_hip_bicg_f64(a, at, b, x, it, eps, st, nullptr, nullptr); }
 	static int apply(const smm_hip_precond* M, const double* r, double* x) { return smm_hip_precond_apply_f64(M, r, x); }
@@ -1367,6 +1373,28 @@ inline SolverStatus GMRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, 
 template <typename T>
 inline SolverStatus GMRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps, int restart = 30) {
 	return GMRES(a, b, x, maxIterations, eps, restart, typename CSRMatrix<T>::IDPreconditioner());
+}
+
+// ---- an addition with no counterpart in the reference: IDR(s), biorthogonal form, with right preconditioning (smm_hip.h states the loop) ----
+// For general matrices; x is the initial guess and receives the result; maxIterations < 0 means rows, with no other clamp; 1 <= s <=
+// SMM_IDRS_MAX_S shadow vectors, generated by the library from seed 0.  Takes the IDPreconditioner or any of CSRMatrix<T>'s own
+// preconditioner classes that GMRES takes; they run inside the device-resident loop.
+template <typename Preconditioner, typename T>
+inline SolverStatus IDRs(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps, int s, const Preconditioner& preconditioner) {
+	static_assert(std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value ||
+	                  std::is_base_of<typename CSRMatrix<T>::PreconditionerBase, Preconditioner>::value,
+	              "IDRs runs the library's own preconditioners only");
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = preconditioner.handle();
+	constexpr bool precondition = !std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value;
+	if (d && precondition && !h) return SolverStatus::DIVERGED;  // (the preconditioner could not be built: lastHipStatus() says why)
+	const int rc = d ? detail::Abi<T>::idrs(d, b, x, maxIterations, eps, s, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+template <typename T>
+inline SolverStatus IDRs(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps, int s = 4) {
+	return IDRs(a, b, x, maxIterations, eps, s, typename CSRMatrix<T>::IDPreconditioner());
 }
 
 // ---- additions with no counterpart in the reference: the transpose, the symmetry check and BiCG for general matrices (smm_hip.h) ----

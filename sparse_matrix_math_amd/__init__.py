@@ -24,6 +24,8 @@ from .host import (  # noqa: F401
     BiCG,
     ConjugateGradientSquared,
     GMRES,
+    IDRs,
+    IDRS_MAX_S,
     IterativeRefinement,
     CSRMatrix,
     Preconditioner,
@@ -36,6 +38,8 @@ from .host import (  # noqa: F401
     bicg_dev,
     cgs_dev,
     gmres_dev,
+    idrs_dev,
+    idrs_shadow_dev,
     refine_dev,
     multi_axpy_dev,
     multi_dot_dev,

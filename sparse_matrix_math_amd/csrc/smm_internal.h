@@ -79,6 +79,7 @@ void preloadBlas1Unit();
 void preloadSolversUnit();
 void preloadCgsUnit();
 void preloadGmresUnit();
+void preloadIdrsUnit();
 void preloadResidentUnits();  // the two single-launch solvers (smm_resident.hip, smm_resident_bicg.hip)
 
 // caching device allocator (solver temporaries are allocated per call like the reference's SMM::Vector,

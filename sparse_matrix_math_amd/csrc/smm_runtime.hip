@@ -70,6 +70,7 @@ static int initLocked(int device) {
 		preloadSolversUnit();
 		preloadCgsUnit();
 		preloadGmresUnit();
+		preloadIdrsUnit();
 		{
 			// (r05: the first single-launch solve of a process paid 5-7 ms for its code object -- config 5's stand-in 20.4 ms instead of 13.6)
 			SetupTrace traceRes("init:   of which the single-launch solvers");

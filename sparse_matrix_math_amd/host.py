@@ -1028,6 +1028,60 @@ def gmres_dev(a, d_b, d_x, maxIterations, eps, restart=30, M=None, stream=None):
     return SolverStatus(st.value), it.value, res.value
 
 
+IDRS_MAX_S = 8  # SMM_IDRS_MAX_S
+
+
+def IDRs(a, b, x, maxIterations, eps, s=4, M=None, seed=0, P=None, info=None):
+    """IDR(s), biorthogonal form, with right preconditioning -- an addition (include/smm_hip.h states the loop).  For general matrices; x
+    is the initial guess and receives the result; maxIterations < 0 means rows, with no other clamp; 1 <= s <= IDRS_MAX_S.  M: None or any
+    preconditioner GMRES accepts.  P: None (the library generates the shadow space from `seed`) or an (s, rows) array, row i the i-th
+    shadow vector, used as given -- b, x and P are then staged through torch tensors on the current device and the device-pointer form
+    runs.  `info`, when a dict, receives iterations (SpMVs) and resnorm2 (the last r.r)."""
+    suf = a._suf
+    if P is None:
+        st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+        check(_fn("smm_hip_idrs", suf)(a._h, _host(b, a.dtype, "b", a.rows), _host(x, a.dtype, "x", a.rows, True), int(maxIterations),
+                                       a.dtype.type(eps), int(s), _mh(M), int(seed), ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+        status, iterations, resnorm2 = SolverStatus(st.value), it.value, res.value
+    else:
+        import torch
+
+        _host(b, a.dtype, "b", a.rows)
+        _host(x, a.dtype, "x", a.rows, True)
+        P = np.asarray(P)
+        if P.dtype != a.dtype or P.ndim != 2 or P.shape[1] != a.rows:
+            raise TypeError(f"P must be an (s, rows) array of {a.dtype}")
+        if P.shape[0] != int(s):
+            raise ValueError(f"P has {P.shape[0]} shadow vectors, s is {int(s)}")
+        ld = max(64, (a.rows + 63) // 64 * 64)  # the library's own layout: every column 16-byte aligned
+        d_P = torch.zeros((P.shape[0], ld), dtype=torch.from_numpy(P[:0]).dtype, device="cuda")
+        d_P[:, : a.rows] = torch.from_numpy(np.ascontiguousarray(P))
+        d_b = torch.from_numpy(b[: a.rows]).cuda()
+        d_x = torch.from_numpy(x[: a.rows]).cuda()
+        torch.cuda.synchronize()
+        status, iterations, resnorm2 = idrs_dev(a, d_b, d_x, maxIterations, eps, s, M, d_P, ld, seed)
+        x[: a.rows] = d_x.cpu().numpy()
+    if info is not None:
+        info.update(iterations=iterations, resnorm2=resnorm2)
+    return status
+
+
+def idrs_dev(a, d_b, d_x, maxIterations, eps, s=4, M=None, d_P=None, ldP=0, seed=0, stream=None):
+    """device-pointer IDR(s); d_P: None (generated from `seed`) or s columns of `rows` elements, column i at d_P + i * ldP, read only.
+    Returns (SolverStatus, iterations, resnorm2).  Synchronises `stream`."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_idrs_dev", suf)(a._h, _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), int(s), _mh(M), _dptr(d_P), int(ldP), int(seed),
+                                       _dptr(stream), ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+    return SolverStatus(st.value), it.value, res.value
+
+
+def idrs_shadow_dev(n, s, seed, d_P, ld, dtype, stream=None):
+    """fills d_P (s columns of n elements of `dtype`, column i at d_P + i * ld) with the shadow space the library generates from `seed`:
+    the hash of include/smm_hip.h made orthonormal.  Synchronises `stream`."""
+    check(_fn("smm_hip_idrs_shadow_dev", _suffix(dtype))(int(n), int(s), int(seed), _dptr(d_P), int(ld), _dptr(stream)))
+
+
 REFINE_INNER_CG, REFINE_INNER_BICGSTAB, REFINE_INNER_GMRES = 0, 1, 2
 _REFINE_INNER = {"CG": REFINE_INNER_CG, "BICGSTAB": REFINE_INNER_BICGSTAB, "GMRES": REFINE_INNER_GMRES}
 
