@@ -210,6 +210,19 @@ extern "C" {
 #define SMM_PATTERN_CONST 3 /* MASKS, and every diagonal holds one value (verified bit for bit against every entry): with one lane per
                              * row an SpMV reads the row's mask, x and <= 32 numbers -- no positions[], no values[] (the Laplacians) */
 
+/* For matrices that are a sparse matrix of dense b x b blocks, b = 2, 3 or 4 (vector-valued problems on unstructured meshes: elasticity,
+ * Stokes, shells, multi-species transport).  A matrix fits block size b when rows and cols are multiples of b, the b rows of every block
+ * row R (rows R b .. R b + b - 1) hold the same number of entries, a multiple of b (0 is allowed), the k-th group of b entries of each of
+ * those rows has the columns c, c + 1, .. c + b - 1 with c a multiple of b, the same c in all b rows, and a row holds at most
+ * max_row_entries entries (smm_hip_csr_blocks_info; 2048 / 1365 / 1024 for b = 2 / 3 / 4: the b rows of a block row fit one tile of 4096
+ * entries).  Explicitly stored zeros count as entries.  Every entry is checked on the device (smm_hip_csr_find_blocks).  positions[] is
+ * then replaced by ONE column index per block -- 4 / b^2 bytes per entry instead of 4 -- and the b entries of x a block needs are read once
+ * for its b rows.  values[] is read in place: every value edit is seen at once.  One lane per block row; same result bit for bit as
+ * STREAM at one lane per row (the reference's order).  Opt-in only: AUTO and smm_hip_csr_autotune never choose it;
+ * smm_hip_csr_set_kernel(m, SMM_SPMV_BLOCKS, 0 or 1) runs the analysis if none is kept and returns SMM_HIP_ERR_INVALID -- the handle
+ * keeps its kernel -- when no size fits. */
+#define SMM_SPMV_BLOCKS 4
+
 typedef struct smm_hip_csr smm_hip_csr;         /* device-resident CSRMatrix<T> (ref:1243-1259) */
 typedef struct smm_hip_precond smm_hip_precond; /* device-resident preconditioner */
 typedef void* smm_hip_stream;                   /* hipStream_t with HIP's own meaning: NULL = the null (default) stream */
@@ -270,6 +283,15 @@ int smm_hip_csr_pattern_info(const smm_hip_csr* m, int* encoding, int* offsets);
  * positions[] (8 bytes per row of mask; 2 bytes per entry of code; no values[] for CONST) + start[] where the kernel reads it + x +
  * out.  Benchmarks price a kernel's launch time with THIS number, never with another layout's.  Diagnostics, like tile_info. */
 int smm_hip_csr_kernel_desc(const smm_hip_csr* m, char* name, int name_cap, long long* bytes_per_launch);
+/* The BLOCKS family's analysis (SMM_SPMV_BLOCKS above).  A synchronous set-up call, like smm_hip_csr_set_kernel(m, SMM_SPMV_PATTERN, ..).
+ * block_size 2, 3 or 4 tests that size; 0 tries 4, then 3, then 2 and keeps the first that fits (a 6 x 6-blocked matrix is served as 3);
+ * other sizes are SMM_HIP_ERR_INVALID.  *found (may be NULL) receives the size kept by this call, or 0: a matrix that does not fit is
+ * SMM_HIP_OK with *found = 0, not an error.  A later call with another size that fits replaces the kept analysis; one that does not
+ * fit leaves it in place.  The kernel choice of the handle is not changed. */
+int smm_hip_csr_find_blocks(smm_hip_csr* m, int block_size, int* found);
+/* The kept analysis: block size, number of blocks (nnz / b^2) and the most entries a row may hold at that size; 0 / 0 / 0 before an
+ * analysis or when the matrix did not fit.  kernel_desc prices a BLOCKS launch as nnz s + (nnz / b^2) 4 + (rows / b + 1) 4 + cols s + rows s. */
+int smm_hip_csr_blocks_info(const smm_hip_csr* m, int* block_size, long long* blocks, int* max_row_entries);
 /* From how many rows grid-shaped matrices are served by the 2.5-D kernels (csrc/smm_spmv_march.hip): constant diagonals (default
  * 2^21) and values read (default 6 x 2^20 fp64 / 2^24 fp32) -- below, the gather / wave kernels are as fast or faster
  * (profiles/r04/march_threshold.txt).

@@ -1055,6 +1055,20 @@ public:
 		(void)device();
 		return dev ? smm_hip_csr_set_kernel(dev, family, lanesPerRow) : SMM_HIP_ERR_NO_DEVICE;
 	}
+	// The BLOCKS family (SMM_SPMV_BLOCKS: one column index per dense b x b block, b = 2, 3, 4).  findBlocks analyses the matrix on the
+	// device -- blockSize 0 tries 4, 3, 2 -- and returns the size kept, 0 when the matrix does not fit, a negative number on an error
+	// (lastHipStatus() holds the status); setSpmvKernel(SMM_SPMV_BLOCKS) then selects the family.  blocksInfo reports the kept analysis
+	// (0 / 0 / 0 without one); any argument may be null.
+	int findBlocks(const int blockSize = 0) const noexcept {
+		(void)device();
+		int found = 0;
+		const int st = dev ? smm_hip_csr_find_blocks(dev, blockSize, &found) : static_cast<int>(SMM_HIP_ERR_NO_DEVICE);
+		return detail::note(st) == SMM_HIP_OK ? found : -1;
+	}
+	int blocksInfo(int* blockSize, long long* blocks, int* maxRowEntries) const noexcept {
+		(void)device();
+		return dev ? smm_hip_csr_blocks_info(dev, blockSize, blocks, maxRowEntries) : SMM_HIP_ERR_NO_DEVICE;
+	}
 	// call after editing values/positions in place through the raw accessors below
 	void invalidateDevice() noexcept {
 		refreshHost();  // (a device-side edit not yet copied back would be lost with the mirror)

@@ -200,6 +200,15 @@ struct smm_hip_csr {
 	int pat_nnz_cap = 0;
 	int pat_max_rows = 0;
 	int pat_chunk_tiles = 0;
+	// BLOCKS family (opt-in, smm_spmv_blocks.hip): the matrix is a sparse matrix of dense b x b blocks.  0 not analysed, b = 2 / 3 / 4 usable at
+	// that block size, -1 no size fits.  Every blk_* field below is written under tileMutex BEFORE the state turns positive (release) and read
+	// only after it was seen positive (acquire).  values[] is read in place: value edits need no refresh
+	std::atomic<int> blk_state{0};
+	int* d_blk_col = nullptr;    // block column c / b of every block, in stored order (nnz / b^2 entries)
+	int* d_blk_start = nullptr;  // first block of every block row: start[R b] / b^2 (rows / b + 1 entries)
+	int* d_blk_tiles = nullptr;  // tile table cut on block-row boundaries: {first block row, its first block}, blk_n_tiles + 1 entries
+	int blk_n_tiles = 0;
+	int blk_blocks = 0;
 	// one-launch form of the row-partitioned SpMV (smm_spmv_split.hip): the most entries any run of 256 / 128 / 64 consecutive rows (cut at
 	// multiples of that) holds -- its fixed row tiles are staged whole, so their LDS is sized from this; -1: not counted yet (under tileMutex)
 	int split_tile_max[3] = {-1, -1, -1};
@@ -431,6 +440,13 @@ void launchPatSweep(const smm_hip_csr* m, int lanes, int rowsOpen, int op, const
 template <typename T>
 int launchSpmvPattern(const smm_hip_csr* m, int lanes, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                       const int* doneFlag, hipStream_t s);
+// BLOCKS family (smm_spmv_blocks.hip): the analysis if none is kept (SMM_HIP_ERR_INVALID when no block size fits), the launch behind
+// launchSpmv (`op` carries the flags), and the kernel's name and bytes for smm_hip_csr_kernel_desc
+int ensureBlocks(smm_hip_csr* m);
+template <typename T>
+int launchSpmvBlocks(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials, const int* doneFlag,
+                     hipStream_t s);
+const char* blocksKernelDesc(const smm_hip_csr* m, long long* bytes);
 void chooseSpmvConfig(smm_hip_csr* m);
 // The row-partitioned SpMV in ONE launch (smm_spmv_split.hip): out = op(lhs, A_loc own) (+|-) A_rem ext [/ divisor], the local half while the
 // halo is in flight, the remote half once `landed` (a device word, raised on the exchange's stream by launchSplitSignal) has reached `seq`

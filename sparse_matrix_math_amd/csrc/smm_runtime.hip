@@ -754,6 +754,9 @@ int smm_hip_csr_destroy(smm_hip_csr* m) {
 	devFree(m->d_pat_masks32);
 	devFree(m->d_pat_masks8);
 	devFree(m->d_pat_rowblocks);
+	devFree(m->d_blk_col);
+	devFree(m->d_blk_start);
+	devFree(m->d_blk_tiles);
 	devFree(m->d_tperm);
 	devFree(m->d_pperm);
 	delete m;

@@ -1060,6 +1060,12 @@ int launchSpmv(const smm_hip_csr* m, int op, const T* lhs, const T* x, T* out, i
 		profEnd(profSlot, s);
 		return st;
 	}
+	if (family == SMM_SPMV_BLOCKS) {  // one column index per dense b x b block (smm_spmv_blocks.hip); its own tile table
+		const int profSlot = profBegin(s);
+		const int st = launchSpmvBlocks<T>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s);
+		profEnd(profSlot, s);
+		return st;
+	}
 	if (family == SMM_SPMV_STREAM) {
 		const int capNnz = streamCap<T>(m, L) - 3;
 		const int maxRows = useTileKernel(L) ? tileRows(L) : TPB / std::min(L, WAVE);
@@ -1165,7 +1171,7 @@ int smm_hip_csr_set_kernel(smm_hip_csr* m, int family, int lanes_per_row) {
 		setError("csr_set_kernel: null matrix");
 		return SMM_HIP_ERR_INVALID;
 	}
-	if (family != SMM_SPMV_AUTO && family != SMM_SPMV_VECTOR && family != SMM_SPMV_STREAM && family != SMM_SPMV_PATTERN) {
+	if (family != SMM_SPMV_AUTO && family != SMM_SPMV_VECTOR && family != SMM_SPMV_STREAM && family != SMM_SPMV_PATTERN && family != SMM_SPMV_BLOCKS) {
 		setError("csr_set_kernel: unknown family %d", family);
 		return SMM_HIP_ERR_INVALID;
 	}
@@ -1178,6 +1184,17 @@ int smm_hip_csr_set_kernel(smm_hip_csr* m, int family, int lanes_per_row) {
 			setError("csr_set_kernel: the PATTERN family takes 1, 2, 4 or 8 lanes per row");
 			return SMM_HIP_ERR_INVALID;
 		}
+	}
+	if (family == SMM_SPMV_BLOCKS) {
+		// opt-in, like PATTERN: a matrix that is not made of dense blocks is refused here and keeps its kernel
+		if (lanes_per_row != 0 && lanes_per_row != 1) {
+			setError("csr_set_kernel: the BLOCKS family runs one lane per block row: lanes_per_row must be 0 or 1");
+			return SMM_HIP_ERR_INVALID;
+		}
+		SMM_TRY(ensureBlocks(m));
+		m->setKernel(SMM_SPMV_BLOCKS, 1);
+		m->kernelForced = true;
+		return SMM_HIP_OK;
 	}
 	if (lanes_per_row != 0 && (lanes_per_row < 1 || lanes_per_row > 64 || (lanes_per_row & (lanes_per_row - 1)))) {
 		setError("csr_set_kernel: lanes_per_row must be 0 or a power of two in 1..64");
@@ -1240,6 +1257,8 @@ int smm_hip_csr_kernel_desc(const smm_hip_csr* m, char* name, int name_cap, long
 	const char* kernel = "spmvVectorKernel";
 	if (family == SMM_SPMV_PATTERN && m->pat_state.load(std::memory_order_acquire) > 0) {
 		kernel = patternKernelDesc(m, lanes, &bytes);
+	} else if (family == SMM_SPMV_BLOCKS) {
+		kernel = blocksKernelDesc(m, &bytes);
 	} else if (family == SMM_SPMV_STREAM || family == SMM_SPMV_PATTERN) {
 		kernel = (lanes == 1 || lanes == 2 || lanes == 4) && useTileKernel(lanes) ? "spmvTileKernel" : "spmvStreamKernel";
 	}

@@ -544,6 +544,16 @@ class _BlockView:
 
         return host.CSRMatrix.kernel_desc(self)
 
+    def find_blocks(self, block_size=0):
+        from . import host
+
+        return host.CSRMatrix.find_blocks(self, block_size)
+
+    def blocks_info(self):
+        from . import host
+
+        return host.CSRMatrix.blocks_info(self)
+
 
 class NativeDistMatrix:
     """smm_hip_dist_csr: this rank's rows of a row-partitioned matrix + the native solvers on it.  Collective."""

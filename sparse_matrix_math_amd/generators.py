@@ -247,6 +247,37 @@ def random_rows(rows, cols, min_len, max_len, seed=1, dtype=np.float64, empty_ev
     return start.astype(np.int32), positions, values
 
 
+def block_expand(start, positions, b, seed=1, dtype=np.float64, diag_dominant=False):
+    """The CSR of the matrix with a dense random b x b block (entries uniform in [-1, 1)) in place of every entry of the scalar pattern
+    (start, positions): block row R holds rows R b .. R b + b - 1, each with the columns c b .. c b + b - 1 of its blocks in stored order --
+    the layout the BLOCKS SpMV family asks for.  The pattern may be rectangular (the result then has b * (max column + 1) columns at
+    least: pass the wanted column count to CSRMatrix).  With diag_dominant (square patterns whose rows hold their diagonal) every
+    diagonal entry becomes 1 + the sum of the row's magnitudes, so the matrix is solvable."""
+    rng = np.random.default_rng(seed)
+    dtype = np.dtype(dtype).type
+    start = np.asarray(start, dtype=np.int64)
+    positions = np.asarray(positions, dtype=np.int64)
+    nbr = len(start) - 1
+    lens = np.diff(start)
+    row_len = np.repeat(lens * b, b)
+    out_start = np.zeros(nbr * b + 1, dtype=np.int64)
+    np.cumsum(row_len, out=out_start[1:])
+    out_pos = np.empty(out_start[-1], dtype=np.int32)
+    out_val = rng.uniform(-1.0, 1.0, size=out_start[-1]).astype(dtype)
+    for R in range(nbr):
+        cols = (positions[start[R]:start[R + 1], None] * b + np.arange(b)[None, :]).reshape(-1)
+        for i in range(b):
+            r = R * b + i
+            out_pos[out_start[r]:out_start[r + 1]] = cols
+            if diag_dominant and len(cols):
+                seg = out_val[out_start[r]:out_start[r + 1]]
+                at = np.flatnonzero(cols == r)
+                if len(at):
+                    seg[at[0]] = dtype(0)
+                    seg[at[0]] = dtype(np.abs(seg).sum() + 1.0)
+    return out_start.astype(np.int32), out_pos, out_val
+
+
 def row_sums(start, values):
     """RHS convention of the reference's solver tests: b = row sums of A, so the exact solution is all ones
     (sumColumsPerRow, test/include/test_common.h:13-21) -- accumulated left to right in the matrix dtype."""

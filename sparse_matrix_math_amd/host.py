@@ -49,7 +49,7 @@ class SolverPreconditioner(enum.IntEnum):
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
 MAX_RHS = 8  # SMM_HIP_MAX_RHS: the most right-hand sides one block holds
-SPMV_AUTO, SPMV_VECTOR, SPMV_STREAM, SPMV_PATTERN = 0, 1, 2, 3
+SPMV_AUTO, SPMV_VECTOR, SPMV_STREAM, SPMV_PATTERN, SPMV_BLOCKS = 0, 1, 2, 3, 4
 SWEEP_AUTO, SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD = 0, 1, 2, 3
 CHEB_BOUND_GERSHGORIN, CHEB_BOUND_POWER, CHEB_BOUND_USER = 0, 1, 2  # SMM_CHEB_BOUND_*: where a Chebyshev preconditioner's bounds come from
 _MULTICOLOR_BASE = {SolverPreconditioner.MULTICOLOR_SGS: SolverPreconditioner.SYMMETRIC_GAUS_SEIDEL, SolverPreconditioner.MULTICOLOR_ILU0: SolverPreconditioner.ILU0,
@@ -507,6 +507,19 @@ class CSRMatrix:
         enc, k = ctypes.c_int(), ctypes.c_int()
         check(_lib.load().smm_hip_csr_pattern_info(self._h, ctypes.byref(enc), ctypes.byref(k)))
         return enc.value, k.value
+
+    def find_blocks(self, block_size=0):
+        """the BLOCKS family's analysis (every entry checked on the device): block_size 2, 3 or 4 tests that size, 0 tries 4, 3, 2 and
+        keeps the first that fits.  Returns the size kept by this call, 0 when the matrix does not fit (not an error)."""
+        found = ctypes.c_int()
+        check(_lib.load().smm_hip_csr_find_blocks(self._h, int(block_size), ctypes.byref(found)))
+        return found.value
+
+    def blocks_info(self):
+        """(block size, blocks, most entries a row may hold at that size) of the kept BLOCKS analysis; (0, 0, 0) without one"""
+        b, n, cap = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
+        check(_lib.load().smm_hip_csr_blocks_info(self._h, ctypes.byref(b), ctypes.byref(n), ctypes.byref(cap)))
+        return b.value, n.value, cap.value
 
     def kernel_desc(self):
         """(kernel name without template arguments, bytes one launch of it moves by ITS data layout) for the next SpMV of this matrix"""
