@@ -495,6 +495,50 @@ int smm_hip_csr_permute_refresh_f32(smm_hip_csr* b, const smm_hip_csr* a, smm_hi
 int smm_hip_csr_permute_refresh_f64(smm_hip_csr* b, const smm_hip_csr* a, smm_hip_stream stream);
 int smm_hip_csr_get_pattern(const smm_hip_csr* m, int* start, int* positions);
 
+/* ---- a BANDWIDTH-REDUCING ORDERING: reverse Cuthill-McKee, computed on the device -- additions (csrc/smm_rcm.hip) ------------------------
+ * smm_hip_csr_rcm*: perm[] such that P a Pᵀ has its entries near the diagonal; perm[i] is the row of `a` that becomes row i -- the
+ *   convention of smm_hip_csr_permute_create, so the output goes straight into it.  What it is for: SMM_SPMV_PATTERN serves "band-numbered
+ *   mesh matrices", and whether a mesh matrix is band-numbered was decided by the program that wrote it out; after this ordering the
+ *   entries take their columns from about 2 x bandwidth offsets, which the CODES encoding accepts up to 65536, and x is gathered from a
+ *   band.  THE RULE, fixed so that the permutation is a function of the pattern alone (its definition, line by line, is
+ *   tests/rcm_restatement.py):
+ *     graph: the matrix must be square.  Vertices i != j are adjacent when (i, j) or (j, i) is stored (explicit zeros count; the
+ *       diagonal is ignored).  deg(v) = the number of distinct neighbours of v; key(v) = (deg(v), v), compared lexicographically.
+ *     Repeat 1 - 3 while unnumbered vertices remain; every breadth-first search visits unnumbered vertices only (one component):
+ *     1 start: s = the unnumbered vertex of smallest key.  (So all isolated vertices come first, in index order.)
+ *     2 root (George-Liu): r = s; let v be the vertex of smallest key in the LAST level of the search from r; if the search from v has
+ *       more levels than the one from r, r = v and repeat; otherwise keep r.
+ *     3 numbering (Cuthill-McKee): a queue holding r; pop u, append the still unnumbered neighbours of u in ascending key order; until
+ *       the queue is empty.  The component's vertices are appended to the order in queue order.
+ *     4 with reverse != 0 (RCM, what callers want) the whole concatenated order is reversed.
+ *   On the device step 3 runs level by level: a new vertex takes parent = the smallest rank among its neighbours in the current level
+ *   (a 32-bit integer atomicMin), the new level is numbered in ascending (parent, deg, index) -- exactly the queue's order.  Integer
+ *   atomics only: two calls give the same permutation.  The graph is `a`'s own pattern when it equals its transpose's (decided on the
+ *   device), else the union pattern from the library's transpose and sum; `a` is not changed.
+ *   COST: work per level is proportional to the edges of that level's vertices, but the host reads one small record per level of every
+ *   search -- a component costs (its levels) x (the root searches of step 2, usually 2 - 4, plus the numbering) round trips of some tens
+ *   of microseconds, plus one per component.  The isolated vertices are numbered by one launch.  Fine for meshes (a 40^3 grid has 118
+ *   levels); LONG THIN GRAPHS ARE SLOW: a band of half-width 24 with 10^7 rows has about 400 000 levels.  *levels and *components let
+ *   the caller see it.  A row of more than 64 entries is walked by a whole wavefront, shorter ones by 8 lanes.
+ *   count must be `rows`.  The four information outputs may be NULL: *components = the connected components, isolated vertices
+ *   included; *levels = the most levels among the searches from the kept roots (0 for a matrix without rows, 1 when every vertex is
+ *   isolated); *bandwidth_before / *bandwidth_after = max |i - j| over the stored entries of `a` / of P a Pᵀ, the latter computed from
+ *   the ordering without building the matrix (it does not depend on `reverse`).
+ *   SMM_HIP_ERR_INVALID, nothing written: a matrix that is not square, a wrong count, a null perm (rows == 0 is legal and needs none); a
+ *   column outside the matrix or a start[] that does not ascend from 0 -- found by a flag on the device, never a fault --; a pattern that
+ *   is not symmetric AND has a row whose columns do not ascend strictly (the sum's rule; every matrix the library builds does).
+ *   Both forms are set-up calls: the host form drains the device once; the _dev form writes d_perm (device, `count` ints) on `stream`
+ *   and synchronises it.  Distributed handles are not covered.
+ * smm_hip_csr_bandwidth (synchronous; any handle, rectangular included): *bandwidth = max |i - j| over the stored entries (0 for none),
+ *   *distinct_offsets = the exact number of distinct j - i, counted by a pass of its own over a bitmap of rows + cols - 1 bits (what
+ *   SMM_SPMV_PATTERN compares with 64 and 65536).  Either output may be NULL.  SMM_HIP_ERR_INVALID for a column outside the matrix or
+ *   a start[] that does not ascend from 0. */
+int smm_hip_csr_rcm(const smm_hip_csr* a, int* perm, size_t count, int reverse, int* components, int* levels, long long* bandwidth_before,
+                    long long* bandwidth_after);
+int smm_hip_csr_rcm_dev(const smm_hip_csr* a, int* d_perm, size_t count, int reverse, smm_hip_stream stream, int* components, int* levels,
+                        long long* bandwidth_before, long long* bandwidth_after);
+int smm_hip_csr_bandwidth(const smm_hip_csr* a, long long* bandwidth, long long* distinct_offsets);
+
 /* ---- the PRODUCT C = A B of two matrices, built on the device (csrc/smm_spgemm.hip); additions with no counterpart in the reference --------
  * `a` is m x k, `b` is k x n, same dtype; C is m x n.
  * Pattern: entry (i, j) is stored in C iff some p has (i, p) stored in `a` and (p, j) stored in `b` -- the structural product.  Terms that

@@ -1444,6 +1444,25 @@ template <typename T>
 inline int permuteRefresh(CSRMatrix<T>& b, const CSRMatrix<T>& a) noexcept {
 	return b.permuteRefresh(a);
 }
+// ---- additions: bandwidth-reducing ordering (smm_hip.h "a BANDWIDTH-REDUCING ORDERING") ----
+// perm becomes the reverse Cuthill-McKee ordering of a's adjacency graph (reverse == false: Cuthill-McKee): perm[i] is the row that becomes
+// row i, so SMM::permute(a, perm.data(), out) has its entries near the diagonal.  The information outputs may be null.  0, or the
+// SMM_HIP_* status with perm left empty
+template <typename T>
+inline int rcm(const CSRMatrix<T>& a, std::vector<int>& perm, bool reverse = true, int* components = nullptr, int* levels = nullptr,
+               long long* bandwidthBefore = nullptr, long long* bandwidthAfter = nullptr) {
+	const smm_hip_csr* d = a.device();
+	perm.assign(static_cast<size_t>(a.getDenseRowCount()), 0);
+	const int rc = detail::note(d ? smm_hip_csr_rcm(d, perm.data(), perm.size(), reverse ? 1 : 0, components, levels, bandwidthBefore, bandwidthAfter) : SMM_HIP_ERR_NO_DEVICE);
+	if (rc != SMM_HIP_OK) perm.clear();
+	return rc;
+}
+// max |i - j| over the stored entries of a and the number of distinct j - i (either may be null); 0, or the SMM_HIP_* status
+template <typename T>
+inline int bandwidth(const CSRMatrix<T>& a, long long* width, long long* distinctOffsets = nullptr) noexcept {
+	const smm_hip_csr* d = a.device();
+	return detail::note(d ? smm_hip_csr_bandwidth(d, width, distinctOffsets) : SMM_HIP_ERR_NO_DEVICE);
+}
 // out becomes the product a b, built on the GPU (CSRMatrix::initProductOf); 0, or the SMM_HIP_* status with out left empty
 template <typename T>
 inline int multiply(const CSRMatrix<T>& a, const CSRMatrix<T>& b, CSRMatrix<T>& out) noexcept {

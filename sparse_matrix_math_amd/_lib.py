@@ -147,6 +147,9 @@ _PLAIN = {
     "smm_hip_csr_color_dev": (c_int, [_P, _P, c_size_t, _P, POINTER(c_int)]),
     "smm_hip_csr_permute_create": (c_int, [_P, _P, c_size_t, _P, POINTER(_P)]),
     "smm_hip_csr_permute_create_dev": (c_int, [_P, _P, c_size_t, _P, POINTER(_P)]),
+    "smm_hip_csr_rcm": (c_int, [_P, _P, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_longlong), POINTER(c_longlong)]),
+    "smm_hip_csr_rcm_dev": (c_int, [_P, _P, c_size_t, c_int, _P, POINTER(c_int), POINTER(c_int), POINTER(c_longlong), POINTER(c_longlong)]),
+    "smm_hip_csr_bandwidth": (c_int, [_P, POINTER(c_longlong), POINTER(c_longlong)]),
     "smm_hip_csr_multiply_create": (c_int, [_P, _P, _P, POINTER(_P)]),
     "smm_hip_csr_convert_create": (c_int, [_P, c_int, _P, POINTER(_P)]),
     "smm_hip_csr_convert_refresh": (c_int, [_P, _P, _P]),

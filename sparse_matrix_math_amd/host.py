@@ -668,6 +668,32 @@ class CSRMatrix:
         check(_fn("smm_hip_csr_permute_refresh", self._suf)(self._h, A._h, _dptr(stream)))
         self._edited(stream)
 
+    # ---- bandwidth-reducing ordering, on the device (smm_hip.h "a BANDWIDTH-REDUCING ORDERING") ----
+    def rcm(self, reverse=True):
+        """(perm[rows], info): the reverse Cuthill-McKee ordering of the adjacency graph (reverse=False: Cuthill-McKee); perm[i] is the
+        row that becomes row i, so B = A.permute(perm) has its entries near the diagonal.  info: components, levels, bandwidth_before,
+        bandwidth_after.  One host round trip per level of every breadth-first search: long thin graphs are slow."""
+        perm = np.zeros(self.rows, dtype=np.int32)
+        comps, levels = ctypes.c_int(), ctypes.c_int()
+        before, after = ctypes.c_longlong(), ctypes.c_longlong()
+        check(_lib.load().smm_hip_csr_rcm(self._h, _host(perm, np.int32, "perm"), perm.size, 1 if reverse else 0, ctypes.byref(comps), ctypes.byref(levels),
+                                          ctypes.byref(before), ctypes.byref(after)))
+        return perm, {"components": comps.value, "levels": levels.value, "bandwidth_before": before.value, "bandwidth_after": after.value}
+
+    def rcm_dev(self, d_perm, reverse=True, stream=None):
+        """the same into an int32 device array of `rows` entries, on `stream` (synchronised); returns info"""
+        comps, levels = ctypes.c_int(), ctypes.c_int()
+        before, after = ctypes.c_longlong(), ctypes.c_longlong()
+        check(_lib.load().smm_hip_csr_rcm_dev(self._h, _dptr(d_perm), self.rows, 1 if reverse else 0, _dptr(stream), ctypes.byref(comps), ctypes.byref(levels),
+                                              ctypes.byref(before), ctypes.byref(after)))
+        return {"components": comps.value, "levels": levels.value, "bandwidth_before": before.value, "bandwidth_after": after.value}
+
+    def bandwidth(self):
+        """(max |i - j| over the stored entries, the number of distinct j - i)"""
+        width, offsets = ctypes.c_longlong(), ctypes.c_longlong()
+        check(_lib.load().smm_hip_csr_bandwidth(self._h, ctypes.byref(width), ctypes.byref(offsets)))
+        return width.value, offsets.value
+
     def isSymmetric(self):
         """(pattern, values): the pattern equals the transpose's; in addition every value equals its mirror image by IEEE == (a NaN never
         does).  (False, False) for a matrix that is not square."""
