@@ -179,6 +179,42 @@ extern "C" {
  * smm_hip_precond_create(a, 12 | 13, &M) means power 1. */
 #define SMM_PRECOND_FSAI 12
 #define SMM_PRECOND_SPAI 13
+/* JSWEEP_SGS / _ILU0 / _IC0 -- additions: the exact kind's factor in the NATURAL numbering, each of its two triangular solves replaced by
+ * a fixed number of JACOBI STEPS, i.e. a truncated Neumann series of the triangular factor (csrc/smm_precond_jsweep.hip; the definition,
+ * line by line, is tests/jsweep_restatement.py).  The factor, the create-time checks and the errors are the exact kind's.
+ *   row walk   the exact sweep's arithmetic of one row: acc = start(own); for the entries of the row's triangular part in the stored order
+ *              (lower: from the row's start while col < row; upper: from the row's end backwards while col > row)
+ *              acc = term(acc, value, y[col]); result = finish(acc, own, d), d the diagonal entry of the swept values:
+ *                SGS lower  start = own      term = _smm_fma(-value, y, acc)   finish = acc / d        (values: a)
+ *                SGS upper  start = 0        term = _smm_fma(value, y, acc)    finish = own - acc / d
+ *                ILU lower  start = own      term = _smm_fma(-value, y, acc)   finish = acc            (values: the ILU0 factor)
+ *                ILU upper  start = own      term = _smm_fma(-value, y, acc)   finish = acc / d
+ *                IC  both   start = own      term = acc - value * y            finish = acc / d        (values: the IC0 factor)
+ *   step       the row walk for ALL rows at once, every y[col] read from the PREVIOUS iterate.  Iterate 0 is the walk with no terms,
+ *              finish(start(own), own, d): own itself for ILU lower, own / d for SGS / IC lower and ILU / IC upper, own for SGS upper.
+ *   apply      lower phase: own = rhs, sweeps_lower steps.  Upper phase: own = the lower phase's last iterate, sweeps_upper steps.
+ * A fixed, linear, deterministic operator.  Two properties:
+ *   EXACTNESS  after k steps every row of dependency level <= k (levels counted from 0) holds the exact sweep's bits and keeps them, so
+ *              with sweeps_lower >= levels_lower - 1 and sweeps_upper >= levels_upper - 1 the apply equals the exact kind's bit for bit
+ *              (the levels are what smm_hip_precond_info reports for the exact kind, and for these kinds).
+ *   SYMMETRY   with sweeps_lower == sweeps_upper the IC0 form is P^T P and the SGS form is symmetric for symmetric a: smm_hip_cg_* takes
+ *              JSWEEP_IC0 and JSWEEP_SGS then, and refuses them (SMM_HIP_ERR_INVALID) with unequal counts.  Positive definiteness is
+ *              P^T P's for IC0; for SGS with few steps it is the caller's to judge (a truncated series of a definite operator).
+ * No in-kernel wait of any sort: an apply is sweeps_lower + sweeps_upper launches shaped like an SpMV over one triangle (one more for
+ * SGS / IC0, an element-wise pass), every launch honours the solver's done flag, every step writes every row exactly once.  A step reads
+ * its triangle only: nnz_tri (4 + sizeof T) bytes + 4 rows of row pointers + the vectors.
+ * smm_hip_bicgstab_*, smm_hip_gmres_*, smm_hip_idrs_*, smm_hip_cgs_*, smm_hip_bicg_* and the refinement driver's inner solves take
+ * JSWEEP_SGS and JSWEEP_ILU0 with any counts, and so does smm_hip_bicgstab_batch_* (every column goes through the apply on its own, the
+ * dot products the SpMM would have fused are formed afterwards).  The row-partitioned solvers, smm_hip_precond_apply_spmv_* and
+ * smm_hip_precond_set_sweep refuse the kinds (SMM_HIP_ERR_INVALID).  smm_hip_precond_values_* returns the ILU0 / IC0 factor on a's
+ * pattern (nnz values; JSWEEP_SGS holds none, like SGS).  The iterates live in two vectors per stream the handle is applied on (the exact
+ * kinds' rule: at most 8 streams are kept), so applies on several streams and from several host threads are allowed.
+ * Memory: the exact factor (nnz values, kept for the refresh), the split triangles (nnz - rows entries of 4 + sizeof T bytes, 2 rows + 2
+ * row pointers, rows diagonal values) and, for ILU0 / IC0, the lower sweep's level schedule (rows + levels integers: the refresh factorises over it).  It is a SNAPSHOT, JSWEEP_SGS included: it does not follow a
+ * value edit of `a` -- call smm_hip_precond_jsweep_refresh.  smm_hip_precond_create(a, 14 | 15 | 16, &M) means 3 / 3 steps. */
+#define SMM_PRECOND_JSWEEP_SGS 14
+#define SMM_PRECOND_JSWEEP_ILU0 15
+#define SMM_PRECOND_JSWEEP_IC0 16
 
 #define SMM_DTYPE_F32 0
 #define SMM_DTYPE_F64 1
@@ -760,7 +796,8 @@ int smm_hip_bicgstab_functor_f64(const smm_hip_csr* a, double* b, double* x, int
  * column.  The dot products add the rows in another (fixed) partition than the single loops, so x agrees with the single solve to the
  * rounding of re-ordered sums, not bit for bit.  The plain loops only: no resident, lazy-x or PATTERN form is entered from here.
  *   bicgstab_batch: M may be NULL or of kind SMM_PRECOND_NONE / SMM_PRECOND_JACOBI (created for `a`; its division is folded into the
- *   rows of the SpMM as in the single loop); every other kind returns SMM_HIP_ERR_INVALID.  cg_batch takes no preconditioner; a column
+ *   rows of the SpMM as in the single loop) or SMM_PRECOND_JSWEEP_SGS / _JSWEEP_ILU0 (applied column by column after the SpMM); every
+ *   other kind returns SMM_HIP_ERR_INVALID.  cg_batch takes no preconditioner; a column
  *   whose first residual already passes reports 0 iterations and its x(:, j) is not written (ref:2342-2344).
  * SMM_HIP_ERR_INVALID: k outside 1 .. SMM_HIP_MAX_RHS, null arrays, dtype mismatch, a matrix that is not square. */
 int smm_hip_bicgstab_batch_f32(const smm_hip_csr* a, int k, float* b, float* x, int maxIterations, float eps, const smm_hip_precond* M,
@@ -1128,6 +1165,23 @@ int smm_hip_precond_create_ainv(const smm_hip_csr* a, int kind, int power, smm_h
 int smm_hip_precond_ainv_refresh(smm_hip_precond* M);
 int smm_hip_precond_ainv_info(const smm_hip_precond* M, int* power, int* max_row, size_t* nnz);
 int smm_hip_precond_ainv_matrix(const smm_hip_precond* M, smm_hip_csr** g, smm_hip_csr** gt);
+/* The iterated-sweep kinds (SMM_PRECOND_JSWEEP_*, defined above) with chosen step counts.  base_kind: SMM_PRECOND_SGS, _ILU0 or _IC0.
+ * sweeps_lower / sweeps_upper: 0 for the default (SMM_JSWEEP_DEFAULT_SWEEPS), else 1 .. SMM_JSWEEP_MAX_SWEEPS; anything else, or another
+ * base_kind, is SMM_HIP_ERR_INVALID.  Other errors: the exact kind's.  A matrix with no rows gives a handle whose apply does nothing.
+ * jsweep_info: the base kind, the two step counts, and the dependency levels of the two exact sweeps (one level analysis at create time;
+ *   counts of levels - 1 make the apply exact); any pointer may be NULL.
+ * jsweep_set_sweeps: changes the counts (0: the default), no rebuild; applies enqueued earlier keep the counts they were enqueued with.
+ * jsweep_refresh: keeps the pattern, the split and the level counts; the ILU0 / IC0 factor is recomputed from the present values of `a`
+ *   and the triangles' values are rewritten: afterwards the handle equals a newly created one bit for bit.  Synchronous.  Errors as
+ *   create's; on an error the handle must not be applied any more (destroy it).  Like create it drains the device first, so value edits
+ *   enqueued on any stream before the call are seen.
+ * The three return SMM_HIP_ERR_INVALID for a handle of another kind. */
+#define SMM_JSWEEP_DEFAULT_SWEEPS 3
+#define SMM_JSWEEP_MAX_SWEEPS 1024
+int smm_hip_precond_create_jsweep(const smm_hip_csr* a, int base_kind, int sweeps_lower, int sweeps_upper, smm_hip_precond** out);
+int smm_hip_precond_jsweep_info(const smm_hip_precond* M, int* base_kind, int* sweeps_lower, int* sweeps_upper, int* levels_lower, int* levels_upper);
+int smm_hip_precond_jsweep_set_sweeps(smm_hip_precond* M, int sweeps_lower, int sweeps_upper);
+int smm_hip_precond_jsweep_refresh(smm_hip_precond* M);
 int smm_hip_precond_destroy(smm_hip_precond* M);
 int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower, int* levels_upper);
 /* How the two triangular sweeps of SGS / ILU0 / IC0 run (same numbers bit for bit either way):

@@ -401,7 +401,7 @@ public:
 	public:
 		PreconditionerBase(const PreconditionerBase&) = delete;
 		PreconditionerBase& operator=(const PreconditionerBase&) = delete;
-		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h), cheb(o.cheb), amg(o.amg), ainvPower(o.ainvPower) { o.h = nullptr; }
+		PreconditionerBase(PreconditionerBase&& o) noexcept : m(o.m), kind(o.kind), h(o.h), cheb(o.cheb), amg(o.amg), ainvPower(o.ainvPower), jsweep(o.jsweep) { o.h = nullptr; }
 		~PreconditionerBase() { smm_hip_precond_destroy(h); }
 		// non-zero on structural failure (missing / tiny diagonal, empty row, non-SPD pivot), like ref:1668-1693
 		// (every init / apply / handle goes through m->device(): entries queued by updateEntry / addEntry / setValue reach the matrix's
@@ -418,6 +418,9 @@ public:
 			}
 			if (kind == SMM_PRECOND_FSAI || kind == SMM_PRECOND_SPAI) {
 				return detail::note(smm_hip_precond_create_ainv(dev, kind, ainvPower, &h)) == SMM_HIP_OK ? 0 : 1;
+			}
+			if (kind >= SMM_PRECOND_JSWEEP_SGS && kind <= SMM_PRECOND_JSWEEP_IC0) {
+				return detail::note(smm_hip_precond_create_jsweep(dev, jsweep.baseKind, jsweep.lower, jsweep.upper, &h)) == SMM_HIP_OK ? 0 : 1;
 			}
 			return detail::note(smm_hip_precond_create(dev, kind, &h)) == SMM_HIP_OK ? 0 : 1;
 		}
@@ -444,6 +447,9 @@ public:
 			double eigRatio = 30.0;
 		} amg;
 		int ainvPower = 1;  // what smm_hip_precond_create_ainv takes (kinds FSAI / SPAI only)
+		struct JacobiSweepParameters {  // what smm_hip_precond_create_jsweep takes (kinds JSWEEP_* only); 0 steps: the default, 3
+			int baseKind = SMM_PRECOND_ILU0, lower = 0, upper = 0;
+		} jsweep;
 	};
 	class IDPreconditioner {  // ref:1166-1170
 	public:
@@ -594,6 +600,44 @@ public:
 			if (this->init()) return 1;
 			if (!this->m->device()) return 1;  // (queued entry edits reach the device first)
 			return detail::note(smm_hip_precond_multicolor_refresh(this->h)) == SMM_HIP_OK ? 0 : 1;
+		}
+	};
+
+	// addition: the exact SGS / ILU0 / IC0 factor in the natural numbering with each triangular solve replaced by a fixed number of Jacobi
+	// steps (smm_hip.h, SMM_PRECOND_JSWEEP_*): no dependent levels, an apply is sweepsLower + sweepsUpper launches shaped like an SpMV over
+	// one triangle.  baseKind: SMM_PRECOND_SGS, _ILU0 or _IC0; steps 0 (the default, 3) or 1 .. SMM_JSWEEP_MAX_SWEEPS.  Usable wherever the
+	// exact kind is (BiCGStab, GMRES: SGS and ILU0); ConjugateGradient takes IC0 and SGS with as many lower steps as upper ones.  With
+	// steps >= levels - 1 (info) the apply is the exact kind's bit for bit.  A snapshot of the matrix's values, SGS included: refresh()
+	// follows a value edit.  The iterates belong to the stream: one object serves any number of streams and host threads.
+	class JacobiSweepPreconditioner : public PreconditionerBase {
+		static constexpr int kindOf(int baseKind) noexcept {
+			return baseKind == SMM_PRECOND_SGS ? SMM_PRECOND_JSWEEP_SGS : baseKind == SMM_PRECOND_IC0 ? SMM_PRECOND_JSWEEP_IC0 : SMM_PRECOND_JSWEEP_ILU0;
+		}
+
+	public:
+		JacobiSweepPreconditioner(const CSRMatrix& m, int baseKind = SMM_PRECOND_ILU0, int sweepsLower = 0, int sweepsUpper = 0) noexcept
+		    : PreconditionerBase(m, kindOf(baseKind)) {
+			this->jsweep.baseKind = baseKind;  // (one that is none of the three is refused when the handle is made)
+			this->jsweep.lower = sweepsLower;
+			this->jsweep.upper = sweepsUpper;
+		}
+		JacobiSweepPreconditioner(JacobiSweepPreconditioner&&) noexcept = default;
+		int validate() noexcept { return this->init(); }
+		// the base kind, the step counts and the dependency levels of the two exact sweeps (any may be null); non-zero when it could not be made
+		int info(int* baseKind, int* sweepsLower, int* sweepsUpper, int* levelsLower, int* levelsUpper) const noexcept {
+			if (this->init()) return 1;
+			return detail::note(smm_hip_precond_jsweep_info(this->h, baseKind, sweepsLower, sweepsUpper, levelsLower, levelsUpper)) == SMM_HIP_OK ? 0 : 1;
+		}
+		// other step counts (0: the default), no rebuild
+		int setSweeps(int sweepsLower, int sweepsUpper) noexcept {
+			if (this->init()) return 1;
+			return detail::note(smm_hip_precond_jsweep_set_sweeps(this->h, sweepsLower, sweepsUpper)) == SMM_HIP_OK ? 0 : 1;
+		}
+		// the factor and the triangles' values again from the matrix's present values, pattern and split kept
+		int refresh() noexcept {
+			if (this->init()) return 1;
+			if (!this->m->device()) return 1;  // (queued entry edits reach the device first)
+			return detail::note(smm_hip_precond_jsweep_refresh(this->h)) == SMM_HIP_OK ? 0 : 1;
 		}
 	};
 
@@ -1279,6 +1323,20 @@ inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, c
 template <typename T>
 inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
                                       const typename CSRMatrix<T>::template MulticolorPreconditioner<typename CSRMatrix<T>::SGSPreconditioner>& M) {
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = M.handle();
+	const int rc = d && h ? detail::Abi<T>::cg(d, b, x0, x, maxIterations, eps, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// addition: ... and with the iterated sweeps of IC0 / SGS at equal step counts (other bases and unequal counts are refused: DIVERGED,
+// lastHipStatus() != 0)
+template <typename T>
+using JacobiSweepPreconditioner = typename CSRMatrix<T>::JacobiSweepPreconditioner;
+template <typename T>
+inline SolverStatus ConjugateGradient(const CSRMatrix<T>& a, const T* const b, const T* const x0, T* const x, int maxIterations, T eps,
+                                      const typename CSRMatrix<T>::JacobiSweepPreconditioner& M) {
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const smm_hip_precond* h = M.handle();

@@ -187,6 +187,10 @@ _PLAIN = {
     "smm_hip_precond_multicolor_info": (c_int, [_P, POINTER(c_int), _P, c_size_t]),
     "smm_hip_precond_multicolor_perm": (c_int, [_P, _P, c_size_t]),
     "smm_hip_precond_multicolor_matrix": (c_int, [_P, POINTER(_P)]),
+    "smm_hip_precond_create_jsweep": (c_int, [_P, c_int, c_int, c_int, POINTER(_P)]),
+    "smm_hip_precond_jsweep_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "smm_hip_precond_jsweep_set_sweeps": (c_int, [_P, c_int, c_int]),
+    "smm_hip_precond_jsweep_refresh": (c_int, [_P]),
     "smm_hip_precond_destroy": (c_int, [_P]),
     "smm_hip_precond_set_sweep": (c_int, [_P, c_int]),
     "smm_hip_precond_take_error": (c_int, [_P, _P]),

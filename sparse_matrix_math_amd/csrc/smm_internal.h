@@ -248,8 +248,10 @@ struct smm_hip_precond {
 	struct smm_precond_cheb* cheb = nullptr;  // CHEBYSHEV: degree, bounds, coefficients and the two scratch vectors (smm_precond_cheb.hip)
 	struct smm_precond_mc* mc = nullptr;      // MULTICOLOR_*: the colouring, the permuted matrix B and the colour-by-colour sweeps (smm_precond_mc.hip); d_values: the factor on B's pattern
 	struct smm_precond_amg* amg = nullptr;    // AMG: the levels, their operators, smoothers and vectors, the dense coarse inverse (smm_precond_amg.hip); d_values: level 0's diag[rows]
+	struct smm_precond_jsweep* jsw = nullptr;  // JSWEEP_*: the split triangles, the step counts and the per-stream iterates (smm_precond_jsweep.hip); plan: the level counts; d_values: the exact factor on A's pattern
 	struct smm_precond_ainv* ainv = nullptr;  // FSAI / SPAI: the pattern, G (and Gt) or M as matrices, the kept a^T and a a^T (smm_precond_ainv.hip); d_values: G's / M's values [nnz of it]
-	// CHEBYSHEV / AMG / MULTICOLOR_* / FSAI keep ONE set of work vectors in the handle and an apply is several launches: they are enqueued
+	// CHEBYSHEV / AMG / MULTICOLOR_* / FSAI keep ONE set of work vectors in the handle and an apply is several launches (JSWEEP_*: one set per
+	// stream, and the step counts an apply reads): they are enqueued
 	// under this lock, so applies issued by several host threads on one stream stay whole (the stream then runs them one after the
 	// other), as the exact kinds' are under their plan's enqueueMutex.  Order: an AMG handle's lock, then a level's Chebyshev handle's
 	// (amgCycle); a level's handle never reaches the AMG handle, so the order cannot invert.  After the first use of the matrices involved (a first SpMV builds
@@ -620,14 +622,20 @@ constexpr PrecondKind PRECOND_KINDS[] = {
     {"MULTICOLOR_IC0",  true,  true,  false, false, false, true},
     {"FSAI",            true,  false, false, false, false, false},
     {"SPAI",            false, false, false, false, false, false},
+    {"JSWEEP_SGS",      true,  false, false, true,  false, false},
+    {"JSWEEP_ILU0",     false, false, false, true,  false, false},
+    {"JSWEEP_IC0",      true,  true,  false, false, false, false},
 };
 constexpr int N_PRECOND_KINDS = static_cast<int>(sizeof(PRECOND_KINDS) / sizeof(PRECOND_KINDS[0]));
 static_assert(SMM_PRECOND_NONE == 0 && SMM_PRECOND_JACOBI == 1 && SMM_PRECOND_ILU0 == 2 && SMM_PRECOND_SGS == 3 && SMM_PRECOND_IC0 == 4 && SMM_PRECOND_BLOCK_ILU0 == 5 &&
                   SMM_PRECOND_BLOCK_SGS == 6 && SMM_PRECOND_CHEBYSHEV == 7 && SMM_PRECOND_AMG == 8 && SMM_PRECOND_MULTICOLOR_SGS == 9 &&
-                  SMM_PRECOND_MULTICOLOR_ILU0 == 10 && SMM_PRECOND_MULTICOLOR_IC0 == 11 && SMM_PRECOND_FSAI == 12 && SMM_PRECOND_SPAI == 13 && N_PRECOND_KINDS == 14,
+                  SMM_PRECOND_MULTICOLOR_ILU0 == 10 && SMM_PRECOND_MULTICOLOR_IC0 == 11 && SMM_PRECOND_FSAI == 12 && SMM_PRECOND_SPAI == 13 &&
+                  SMM_PRECOND_JSWEEP_SGS == 14 && SMM_PRECOND_JSWEEP_ILU0 == 15 && SMM_PRECOND_JSWEEP_IC0 == 16 && N_PRECOND_KINDS == 17,
               "PRECOND_KINDS is indexed by the SMM_PRECOND_* values");
 inline bool isBlockKind(int kind) { return kind >= 0 && kind < N_PRECOND_KINDS && PRECOND_KINDS[kind].block; }
 inline bool isMulticolorKind(int kind) { return kind >= 0 && kind < N_PRECOND_KINDS && PRECOND_KINDS[kind].multicolor; }
+inline bool isJsweepKind(int kind) { return kind >= SMM_PRECOND_JSWEEP_SGS && kind <= SMM_PRECOND_JSWEEP_IC0; }
+bool jsweepSymmetric(const smm_hip_precond* M);  // (smm_precond_jsweep.hip) as many lower steps as upper ones
 
 // Which kinds a class of solver takes.  CG takes a handle of kind NONE for what it is (and refuses it); to the other classes such a handle
 // means "no preconditioner", like a null M.
@@ -641,13 +649,18 @@ inline bool precondKindTaken(int kind, SolverClass c) {
 // the kinds the class does take, from the table.
 inline int precondAdmissible(const char* who, const smm_hip_precond* M, const smm_hip_csr* a, SolverClass c) {
 	if (!M || (c != SOLVER_CG && M->kind == SMM_PRECOND_NONE)) return SMM_HIP_OK;
-	if (precondKindTaken(M->kind, c) && M->a == a) return SMM_HIP_OK;
-	std::string names, inverses;  // (the approximate inverses come in a clause of their own: they take a parameter, the power)
+	if (precondKindTaken(M->kind, c) && M->a == a) {
+		if (c != SOLVER_CG || !isJsweepKind(M->kind) || jsweepSymmetric(M)) return SMM_HIP_OK;
+		setError("%s: a %s preconditioner is symmetric only with as many lower steps as upper ones (smm_hip_precond_jsweep_set_sweeps)", who, PRECOND_KINDS[M->kind].name);
+		return SMM_HIP_ERR_INVALID;
+	}
+	std::string names, inverses, iterated;  // (the approximate inverses and the iterated sweeps come in clauses of their own: they take a parameter)
 	for (int kind = SMM_PRECOND_NONE + 1; kind < N_PRECOND_KINDS; ++kind) {
-		std::string& list = kind == SMM_PRECOND_FSAI || kind == SMM_PRECOND_SPAI ? inverses : names;
+		std::string& list = kind == SMM_PRECOND_FSAI || kind == SMM_PRECOND_SPAI ? inverses : isJsweepKind(kind) ? iterated : names;
 		if (precondKindTaken(kind, c)) list += std::string(list.empty() ? "" : " / ") + PRECOND_KINDS[kind].name;
 	}
 	if (!inverses.empty()) names += ", or " + inverses + " of any power,";
+	if (!iterated.empty()) names += std::string(inverses.empty() ? "," : "") + " or " + iterated + (c == SOLVER_CG ? " with equal step counts," : " with any step counts,");
 	setError("%s: preconditioner must be %s %s", who, names.c_str(),
 	         c == SOLVER_DIST_LOCAL ? "of the local diagonal block (smm_hip_dist_csr_local_block)" : "created for this matrix");
 	return SMM_HIP_ERR_INVALID;
@@ -683,6 +696,20 @@ void amgDestroy(struct smm_precond_amg* G);
 template <typename T>
 int ainvApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
 void ainvDestroy(struct smm_precond_ainv* A);
+
+// iterated triangular sweeps, JSWEEP_* (smm_precond_jsweep.hip): sweeps_lower + sweeps_upper (+ 1) launches, no waits
+template <typename T>
+int jsweepApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* doneFlag, hipStream_t s);
+void jsweepDestroy(struct smm_precond_jsweep* J);
+// the exact kinds' set-up for them (smm_precond.hip): the create-time checks, the level analysis into M->plan and the ILU0 / IC0 factor into
+// M->d_values, as for a handle of kind `baseKind`; exactRefactor: the checks and the factor again from the present values of the matrix
+template <typename T>
+int exactCreateTyped(const smm_hip_csr* a, int baseKind, smm_hip_precond* M);
+template <typename T>
+int exactRefactor(smm_hip_precond* M, int baseKind, hipStream_t s);
+// frees the device arrays of the level schedules such a handle does not need (the upper sweep's; the lower one's too when no factor is
+// kept): the level counts stay
+void exactDropSchedules(smm_hip_precond* M, bool keepLower);
 
 // graph colouring and symmetric permutation of a handle (smm_color.hip); include/smm_hip.h states both rules
 // colours of the rows of a square, ready matrix into d_colors[rows] (device), *ncolors on the host; synchronises `s`

@@ -609,6 +609,7 @@ int precondApplyDev(const smm_hip_precond* M, const T* rhs, T* x, const int* don
 	if (M->kind == SMM_PRECOND_AMG) return amgApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (isMulticolorKind(M->kind)) return mcApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_FSAI || M->kind == SMM_PRECOND_SPAI) return ainvApplyDev<T>(M, rhs, x, doneFlag, s);
+	if (isJsweepKind(M->kind)) return jsweepApplyDev<T>(M, rhs, x, doneFlag, s);
 	if (M->kind == SMM_PRECOND_JACOBI) {
 		jacobiApplyKernel<T><<<sweepGrid(n), TPB, 0, s>>>(n, static_cast<const T*>(M->d_values), rhs, x, doneFlag);
 		SMM_HIP_TRY(hipGetLastError());
@@ -793,6 +794,28 @@ static int createTyped(const smm_hip_csr* a, int kind, smm_hip_precond* M) {
 	return SMM_HIP_OK;
 }
 
+// the exact kinds' set-up and re-factorisation for the iterated-sweep kinds (smm_precond_jsweep.hip), which keep the exact factor
+template <typename T>
+int exactCreateTyped(const smm_hip_csr* a, int baseKind, smm_hip_precond* M) {
+	return createTyped<T>(a, baseKind, M);
+}
+template int exactCreateTyped<float>(const smm_hip_csr*, int, smm_hip_precond*);
+template int exactCreateTyped<double>(const smm_hip_csr*, int, smm_hip_precond*);
+
+template <typename T>
+int exactRefactor(smm_hip_precond* M, int baseKind, hipStream_t s) {
+	SMM_TRY(precondRowCheck<T>(M->a, baseKind == SMM_PRECOND_SGS, nullptr, s));
+	if (baseKind == SMM_PRECOND_SGS) return SMM_HIP_OK;
+	return factorOn<T>(M->a, baseKind, M->plan->lo, static_cast<T*>(M->d_values), s);
+}
+void exactDropSchedules(smm_hip_precond* M, bool keepLower) {
+	if (!M->plan) return;
+	M->plan->up.release();  // (the host copy of the bounds stays: levels() counts them)
+	if (!keepLower) M->plan->lo.release();
+}
+template int exactRefactor<float>(smm_hip_precond*, int, hipStream_t);
+template int exactRefactor<double>(smm_hip_precond*, int, hipStream_t);
+
 template <typename T>
 static int applyHost(const smm_hip_precond* M, const T* rhs, T* x) {
 	if (!M) {
@@ -825,6 +848,10 @@ static int applySpmvDev(const smm_hip_precond* M, const T* v, T* x, hipStream_t 
 	}
 	if (isMulticolorKind(M->kind)) {
 		setError("precond_apply_spmv: the multicolour kinds have no fused form (run the SpMV, then smm_hip_precond_apply_*)");
+		return SMM_HIP_ERR_INVALID;
+	}
+	if (isJsweepKind(M->kind)) {
+		setError("precond_apply_spmv: the iterated-sweep kinds have no fused form (run the SpMV, then smm_hip_precond_apply_*)");
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int n = M->a->rows;
@@ -896,6 +923,7 @@ static int precondCreate(const smm_hip_csr* a, int kind, int blockRows, int leve
 	if (kind == SMM_PRECOND_AMG) return smm_hip_precond_create_amg(a, 0.08, 10, 256, 2, 30.0, out);  // the defaults
 	if (isMulticolorKind(kind)) return smm_hip_precond_create_multicolor(a, kind == SMM_PRECOND_MULTICOLOR_SGS ? SMM_PRECOND_SGS : kind == SMM_PRECOND_MULTICOLOR_ILU0 ? SMM_PRECOND_ILU0 : SMM_PRECOND_IC0, nullptr, 0, out);  // the library's own colouring
 	if (kind == SMM_PRECOND_FSAI || kind == SMM_PRECOND_SPAI) return smm_hip_precond_create_ainv(a, kind, 1, out);  // the pattern of a itself
+	if (isJsweepKind(kind)) return smm_hip_precond_create_jsweep(a, kind == SMM_PRECOND_JSWEEP_SGS ? SMM_PRECOND_SGS : kind == SMM_PRECOND_JSWEEP_ILU0 ? SMM_PRECOND_ILU0 : SMM_PRECOND_IC0, 0, 0, out);  // 3 / 3 steps
 	if (kind < SMM_PRECOND_NONE || kind > SMM_PRECOND_BLOCK_SGS) {
 		setError("precond_create: unknown kind %d", kind);
 		return SMM_HIP_ERR_INVALID;
@@ -969,6 +997,7 @@ int smm_hip_precond_destroy(smm_hip_precond* M) {
 	amgDestroy(M->amg);
 	mcDestroy(M->mc);
 	ainvDestroy(M->ainv);  // (before d_values, which its matrix wraps)
+	jsweepDestroy(M->jsw);
 	planDestroy(M->plan);
 	devFree(M->d_values);
 	delete M;
@@ -997,6 +1026,10 @@ int smm_hip_precond_info(const smm_hip_precond* M, int* kind, int* levels_lower,
 int smm_hip_precond_set_sweep(smm_hip_precond* M, int mode) {
 	if (!M || mode < SMM_SWEEP_AUTO || mode > SMM_SWEEP_SYNCFREE_XCD) {
 		setError("precond_set_sweep: null handle or unknown mode");
+		return SMM_HIP_ERR_INVALID;
+	}
+	if (isJsweepKind(M->kind)) {  // (they keep a plan for its level counts only)
+		setError("precond_set_sweep: the iterated-sweep kinds have no sweep mode (smm_hip_precond_jsweep_set_sweeps sets their step counts)");
 		return SMM_HIP_ERR_INVALID;
 	}
 	if (M->plan) M->plan->sweep = mode;  // Jacobi / NONE have no sweeps: accepted, no effect

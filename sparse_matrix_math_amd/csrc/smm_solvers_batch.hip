@@ -13,6 +13,8 @@
 //     or zeros cannot reach another column;
 //   * the host stops enqueueing when ALL columns are done: the device raises one all-done word that the DonePoller watches and that the
 //     SpMM launches test.
+//   * BiCGStab takes JACOBI (folded into the SpMM's rows) and the iterated sweeps JSWEEP_SGS / _ILU0, which work on one vector: the SpMM
+//     writes a temporary, each column is gathered, applied and scattered, and batchDot forms the sums the epilogue would have.
 // No resident, lazy-x, PATTERN-adoption or autotune path is entered from here.
 #include <algorithm>
 #include <cmath>
@@ -105,6 +107,16 @@ __global__ __launch_bounds__(TPB) void batchDot(int n, const T* __restrict__ a, 
 	for (int j = 0; j < KC; ++j) {
 		const T s = blockSum256(acc[j], red);
 		if (threadIdx.x == 0) parts[static_cast<size_t>(j) * COLPARTS + blockIdx.x] = s;
+	}
+}
+
+// column j of an interleaved n x k block and a contiguous vector: gather (block -> vec) or scatter (vec -> block)
+template <typename T>
+__global__ __launch_bounds__(TPB) void batchColumnCopy(int n, int k, int j, T* block, int gather, T* vec, const int* __restrict__ doneFlag) {
+	if (doneFlag && *doneFlag) return;
+	for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * TPB) {
+		if (gather) vec[i] = block[i * k + j];
+		else block[i * k + j] = vec[i];
 	}
 }
 
@@ -354,7 +366,26 @@ int bicgstabBatchDev(const smm_hip_csr* a, int k, const T* b, T* x, int maxItera
 	}
 	SMM_TRY(ensureCsrReady(a, s, true));
 	// the Jacobi apply x = rhs / diag is folded into the rows of the SpMM that precedes it, exactly as the single loop folds it into its SpMV
-	const T* diag = precondition ? static_cast<const T*>(M->d_values) : nullptr;
+	const bool sweeps = precondition && isJsweepKind(M->kind);
+	const T* diag = precondition && !sweeps ? static_cast<const T*>(M->d_values) : nullptr;
+	// The iterated sweeps (JSWEEP_SGS / _ILU0) work on one vector: the SpMM leaves A v in t, every column of t goes through the apply by
+	// way of two contiguous vectors, and the dot products the SpMM would have fused are formed by batchDot afterwards.  A frozen column's
+	// apply writes a temporary only (ap / as), which no update reads for that column.
+	DevBuf<T> t, cin, cout;
+	if (sweeps) {
+		SMM_TRY(t.alloc(static_cast<size_t>(n) * k));
+		SMM_TRY(cin.alloc(n));
+		SMM_TRY(cout.alloc(n));
+	}
+	auto sweepColumns = [&](T* dst, const int* flag) -> int {
+		for (int j = 0; j < k && n > 0; ++j) {
+			batchColumnCopy<T><<<solverGrid(n), TPB, 0, s>>>(n, k, j, t.p, 1, cin.p, flag);
+			SMM_TRY(precondApplyDev<T>(M, cin.p, cout.p, flag, s));
+			batchColumnCopy<T><<<solverGrid(n), TPB, 0, s>>>(n, k, j, dst, 0, cout.p, flag);
+		}
+		SMM_HIP_TRY(hipGetLastError());
+		return SMM_HIP_OK;
+	};
 	maxIterations = std::min(maxIterations, n);  // ref:2200
 	if (maxIterations == -1) maxIterations = n;  // ref:2201-2203
 	const size_t nk = static_cast<size_t>(n) * k;
@@ -373,7 +404,12 @@ int bicgstabBatchDev(const smm_hip_csr* a, int k, const T* b, T* x, int maxItera
 	SMM_TRY(allDone.alloc(1));
 
 	// r = M^-1 (b - A x), ref:2215-2224
-	SMM_TRY(launchSpmm<T>(a, diag ? SPMM_OP_SUB_DIV : SMM_OP_SUB, k, b, x, r, 0, nullptr, nullptr, nullptr, s, diag));
+	if (sweeps) {
+		SMM_TRY(launchSpmm<T>(a, SMM_OP_SUB, k, b, x, t.p, 0, nullptr, nullptr, nullptr, s));
+		SMM_TRY(sweepColumns(r, nullptr));
+	} else {
+		SMM_TRY(launchSpmm<T>(a, diag ? SPMM_OP_SUB_DIV : SMM_OP_SUB, k, b, x, r, 0, nullptr, nullptr, nullptr, s, diag));
+	}
 	if (nk) {
 		SMM_HIP_TRY(hipMemcpyAsync(r0, r, sizeof(T) * nk, hipMemcpyDeviceToDevice, s));  // ref:2225-2226
 		SMM_HIP_TRY(hipMemcpyAsync(p, r, sizeof(T) * nk, hipMemcpyDeviceToDevice, s));
@@ -387,9 +423,22 @@ int bicgstabBatchDev(const smm_hip_csr* a, int k, const T* b, T* x, int maxItera
 	LoopWatch watch;
 	SMM_TRY(watch.begin(s, doneFlag, 1));
 	for (int i = 0; i < planned && !watch.leave(i); ++i) {
-		SMM_TRY(launchSpmm<T>(a, spmmOp, k, nullptr, p, ap, 1, r0, parts, doneFlag, s, diag));  // ref:2234-2235 + 2243 fused
+		if (sweeps) {
+			SMM_TRY(launchSpmm<T>(a, SMM_OP_ASSIGN, k, nullptr, p, t.p, 0, nullptr, nullptr, doneFlag, s));
+			SMM_TRY(sweepColumns(ap, doneFlag));
+			SMM_BATCH_LAUNCH(batchDot, k, NPART, s, n, ap, r0, parts);  // ap.r0
+		} else {
+			SMM_TRY(launchSpmm<T>(a, spmmOp, k, nullptr, p, ap, 1, r0, parts, doneFlag, s, diag));  // ref:2234-2235 + 2243 fused
+		}
 		SMM_BATCH_LAUNCH(bicgBatchS, k, solverGrid(n), s, n, sc, i & 1, parts, ap, r, sv);
-		SMM_TRY(launchSpmm<T>(a, spmmOp, k, nullptr, sv, as, 2, sv, parts, doneFlag, s, diag));  // ref:2250-2251 + 2256-2261 fused
+		if (sweeps) {
+			SMM_TRY(launchSpmm<T>(a, SMM_OP_ASSIGN, k, nullptr, sv, t.p, 0, nullptr, nullptr, doneFlag, s));
+			SMM_TRY(sweepColumns(as, doneFlag));
+			SMM_BATCH_LAUNCH(batchDot, k, NPART, s, n, as, as, parts);           // [as.as | as.s]
+			SMM_BATCH_LAUNCH(batchDot, k, NPART, s, n, as, sv, parts.p + NPART);
+		} else {
+			SMM_TRY(launchSpmm<T>(a, spmmOp, k, nullptr, sv, as, 2, sv, parts, doneFlag, s, diag));  // ref:2250-2251 + 2256-2261 fused
+		}
 		SMM_BATCH_LAUNCH(bicgBatchXR, k, NPART, s, n, sc, parts, p, sv, as, r0, x, r, parts2);
 		SMM_BATCH_LAUNCH(bicgBatchP, k, solverGrid(n), s, n, sc, allDone, i & 1, parts2, eps, ap, r, p);
 	}

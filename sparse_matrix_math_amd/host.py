@@ -30,7 +30,9 @@ class SolverPreconditioner(enum.IntEnum):
     block-diagonal part of A, one wavefront per block) are additions, and so is CHEBYSHEV (a polynomial in D^-1 A: SpMVs and
     element-wise passes only), AMG (smoothed-aggregation multigrid, a symmetric V-cycle) and the MULTICOLOR_ forms (SGS / ILU0 / IC0 of the
     matrix renumbered colour by colour: a handful of dependent levels per sweep) and FSAI / SPAI (approximate inverses that are sparse
-    matrices themselves: an apply is one or two SpMVs).  Values are the SMM_PRECOND_* codes of the C ABI."""
+    matrices themselves: an apply is one or two SpMVs) and the JSWEEP_ forms (the exact SGS / ILU0 / IC0 factor in the natural numbering,
+    each triangular solve replaced by a fixed number of Jacobi steps: no dependent levels at all).  Values are the SMM_PRECOND_* codes of
+    the C ABI."""
     NONE = 0
     JACOBI = 1
     ILU0 = 2
@@ -45,6 +47,9 @@ class SolverPreconditioner(enum.IntEnum):
     MULTICOLOR_IC0 = 11
     FSAI = 12
     SPAI = 13
+    JSWEEP_SGS = 14
+    JSWEEP_ILU0 = 15
+    JSWEEP_IC0 = 16
 
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
@@ -54,6 +59,8 @@ SWEEP_AUTO, SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD = 0, 1, 2, 3
 CHEB_BOUND_GERSHGORIN, CHEB_BOUND_POWER, CHEB_BOUND_USER = 0, 1, 2  # SMM_CHEB_BOUND_*: where a Chebyshev preconditioner's bounds come from
 _MULTICOLOR_BASE = {SolverPreconditioner.MULTICOLOR_SGS: SolverPreconditioner.SYMMETRIC_GAUS_SEIDEL, SolverPreconditioner.MULTICOLOR_ILU0: SolverPreconditioner.ILU0,
                     SolverPreconditioner.MULTICOLOR_IC0: SolverPreconditioner.IC0}
+_JSWEEP_BASE = {SolverPreconditioner.JSWEEP_SGS: SolverPreconditioner.SYMMETRIC_GAUS_SEIDEL, SolverPreconditioner.JSWEEP_ILU0: SolverPreconditioner.ILU0,
+                SolverPreconditioner.JSWEEP_IC0: SolverPreconditioner.IC0}
 _AINV_KINDS = (SolverPreconditioner.FSAI, SolverPreconditioner.SPAI)
 _CHEB_BOUNDS = {"GERSHGORIN": CHEB_BOUND_GERSHGORIN, "POWER": CHEB_BOUND_POWER, "USER": CHEB_BOUND_USER}
 
@@ -170,7 +177,7 @@ def profile_read_waits(reset=True):
 class Preconditioner:
     """`int apply(const T* rhs, T* x) const` (ref:1173-1235).  Created by CSRMatrix.getPreconditioner."""
 
-    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None, colors=None, power=None):
+    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None, colors=None, power=None, sweeps=None):
         self.matrix = matrix  # keeps the matrix alive (the reference holds a const CSRMatrix&)
         self.kind = SolverPreconditioner(kind)
         self._h = ctypes.c_void_p()
@@ -181,6 +188,8 @@ class Preconditioner:
         elif amg is not None:  # (theta, max_levels, coarse_rows, smooth_degree, eig_ratio): AMG with chosen parameters
             theta, max_levels, coarse_rows, smooth_degree, ratio = amg
             check(_lib.load().smm_hip_precond_create_amg(matrix._h, float(theta), int(max_levels), int(coarse_rows), int(smooth_degree), float(ratio), ctypes.byref(self._h)))
+        elif sweeps is not None:  # JSWEEP_ kinds with chosen step counts (lower, upper); 0 = the default
+            check(_lib.load().smm_hip_precond_create_jsweep(matrix._h, int(_JSWEEP_BASE[self.kind]), int(sweeps[0]), int(sweeps[1]), ctypes.byref(self._h)))
         elif power is not None:  # FSAI / SPAI on the pattern of the power-th structural power of the matrix
             check(_lib.load().smm_hip_precond_create_ainv(matrix._h, int(kind), int(power), ctypes.byref(self._h)))
         elif colors is not None:  # MULTICOLOR_ kinds with the caller's colouring (one colour per row)
@@ -347,6 +356,22 @@ class Preconditioner:
     def ainv_refresh(self):
         """FSAI / SPAI: keep every pattern, redo the values from the matrix's present values (after a value edit).  Synchronous."""
         check(_lib.load().smm_hip_precond_ainv_refresh(self._h))
+
+    def jsweep_info(self):
+        """JSWEEP_ kinds: {base (the exact kind), sweeps_lower, sweeps_upper, levels_lower, levels_upper}; sweeps of levels - 1 make the
+        apply the exact kind's bit for bit"""
+        v = [ctypes.c_int() for _ in range(5)]
+        check(_lib.load().smm_hip_precond_jsweep_info(self._h, *[ctypes.byref(c) for c in v]))
+        return {"base": SolverPreconditioner(v[0].value), "sweeps_lower": v[1].value, "sweeps_upper": v[2].value, "levels_lower": v[3].value,
+                "levels_upper": v[4].value}
+
+    def jsweep_set_sweeps(self, lower, upper=None):
+        """JSWEEP_ kinds: change the step counts (upper None: the same as lower), no rebuild"""
+        check(_lib.load().smm_hip_precond_jsweep_set_sweeps(self._h, int(lower), int(lower if upper is None else upper)))
+
+    def jsweep_refresh(self):
+        """JSWEEP_ kinds: keep the pattern and its split, redo the factor and the triangles' values from the matrix's present values.  Synchronous."""
+        check(_lib.load().smm_hip_precond_jsweep_refresh(self._h))
 
     def values(self):
         """factor values: diag (JACOBI, CHEBYSHEV, AMG) or the ILU0 / IC0 / BLOCK_ILU0 values on A's pattern (MULTICOLOR_ILU0 / _IC0: on
@@ -784,13 +809,22 @@ class CSRMatrix:
         check(_fn(name, self._suf)(self._h, int(op), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), int(dot_mode), _dptr(d_w1), _dptr(d_partials), _dptr(stream)))
 
     def getPreconditioner(self, kind, block_rows=None, level_cap=None, partition=None, degree=None, bound=None, eig_ratio=None, power_steps=None,
-                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None, colors=None, power=None):
+                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None, colors=None, power=None, sweeps=None):
         """ref:1643-1651.  kind: a SolverPreconditioner or its name ("CHEBYSHEV").  block_rows / level_cap / partition: BLOCK_ kinds only;
         degree (3) / bound ("GERSHGORIN", "POWER", "USER" or a CHEB_BOUND_* code) / eig_ratio (30) / power_steps (10) / lambda_min /
         lambda_max (USER): CHEBYSHEV only; theta (0.08) / max_levels (10) / coarse_rows (256) / smooth_degree (2) and eig_ratio (30): AMG only.
-        colors (one per row; None = CSRMatrix.color's): MULTICOLOR_ kinds only; power (1 .. 4; 1): FSAI / SPAI only.  None = the default."""
+        colors (one per row; None = CSRMatrix.color's): MULTICOLOR_ kinds only; power (1 .. 4; 1): FSAI / SPAI only;
+        sweeps (an int, or a (lower, upper) pair; 1 .. 1024; 3): JSWEEP_ kinds only.  None = the default."""
         if isinstance(kind, str):
             kind = SolverPreconditioner[kind]
+        if sweeps is not None:
+            if SolverPreconditioner(kind) not in _JSWEEP_BASE:
+                raise ValueError("sweeps belongs to the JSWEEP_ preconditioners")
+            if any(v is not None for v in (block_rows, level_cap, partition, degree, bound, eig_ratio, power_steps, lambda_min, lambda_max, theta, max_levels,
+                                           coarse_rows, smooth_degree, colors, power)):
+                raise ValueError("the JSWEEP_ preconditioners take sweeps only")
+            lower, upper = (sweeps, sweeps) if isinstance(sweeps, (int, np.integer)) else sweeps
+            return Preconditioner(self, kind, sweeps=(int(lower), int(upper)))
         if power is not None:
             if SolverPreconditioner(kind) not in _AINV_KINDS:
                 raise ValueError("power belongs to the FSAI / SPAI preconditioners")
@@ -970,7 +1004,7 @@ def _batch_result(k, st, it, res, info, resname, dtype):
 
 def BiCGStabBatch(a, B, X, maxIterations, eps, M=None, info=None):
     """BiCGStab (ref:2191-2303) for the k columns of B at once -- an addition: B and X are C-contiguous (n, k) arrays, k <= MAX_RHS; X
-    holds the initial guesses and receives the results.  M: None or a NONE / JACOBI preconditioner.  Column j is solved as BiCGStab
+    holds the initial guesses and receives the results.  M: None or a NONE / JACOBI / JSWEEP_SGS / JSWEEP_ILU0 preconditioner.  Column j is solved as BiCGStab
     solves it alone (its own iteration count, status and NaN behaviour).  Returns a list of k SolverStatus; `info`, when a dict,
     receives `iterations` and `resnorm` as arrays of length k."""
     suf = a._suf
