@@ -922,6 +922,51 @@ int smm_hip_gmres_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, in
 int smm_hip_gmres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, int restart, const smm_hip_precond* M,
                           smm_hip_stream stream, int* solver_status, int* iterations, double* resnorm2);
 
+/* smm_hip_minres_*: MINRES (Paige and Saunders 1975) with a symmetric positive definite preconditioner -- an addition, the reference
+ * has no MINRES (csrc/smm_solvers_minres.hip; the definition, line by line, is tests/minres_restatement.py).
+ * For SYMMETRIC matrices, indefinite ones included (shifted operators, saddle-point / KKT systems), where smm_hip_cg_* divides by a
+ * p.Ap that can be zero or negative.  One SpMV and two inner products per step, seven vectors (eight with M), no transpose, and a
+ * residual norm that never grows.  Symmetry of `a` is the caller's business, as with smm_hip_cg_*: smm_hip_csr_is_symmetric tells.
+ * Semantics (x in/out: the start is read from it; `iterations` counts steps):
+ *   maxIterations == -1 means rows; otherwise it is clamped to 0 .. rows
+ *   r1 = b - A x;  y = M^-1 r1;  beta1 = sqrt(r1.y);  r2 = r1
+ *   oldb = 0; beta = beta1; dbar = 0; epsln = 0; phibar = beta1; cs = -1; sn = 0; w = w2 = 0
+ *   while (phibar^2 > eps*eps && iterations < maxIterations) {
+ *     v = y / beta;  Av = A v;  alfa = v.Av
+ *     t = Av;  from the second step on: t = _smm_fma(-(beta / oldb), r1, t);  t = _smm_fma(-(alfa / beta), r2, t);  r1 = r2;  r2 = t
+ *     y = M^-1 r2;  oldb = beta;  beta = sqrt(r2.y)
+ *     r2.y < 0 (M is not positive definite), or beta not finite: DIVERGED, the step is not taken, x keeps its last value
+ *     oldeps = epsln; delta = cs dbar + sn alfa; gbar = sn dbar - cs alfa; epsln = sn beta; dbar = -cs beta
+ *     gamma = max(sqrt(gbar^2 + beta^2), machine epsilon of T); cs = gbar / gamma; sn = beta / gamma; phi = cs phibar; phibar = sn phibar
+ *     phibar not finite: DIVERGED, likewise
+ *     w1 = w2; w2 = w;  w = _smm_fma(-delta, w2, _smm_fma(-oldeps, w1, v)) / gamma;  x = _smm_fma(phi, w, x);  iterations++
+ *     beta == 0: the Krylov space is exhausted (phibar is 0 now): the loop ends
+ *   }
+ *   status: DIVERGED on the tests above; else SUCCESS if phibar^2 <= eps*eps; else MAX_ITERATIONS_REACHED
+ * (alfa is formed from A v before r1 is subtracted: v.r1 = 0 in exact arithmetic, so it is the textbook alfa up to rounding.)
+ * The stop test is smm_hip_cg_*'s: absolute, on the squared norm.  WHICH NORM: with M == NULL y and r2 are one vector and phibar is
+ * ||b - A x||_2 (up to rounding).  With M, phibar is the M^-1-norm of the residual, sqrt(r.M^-1 r): a caller who needs the 2-norm
+ * recomputes it.  resnorm2 returns the last phibar^2.
+ * A solve that starts with phibar^2 <= eps*eps (an exact x included) returns x untouched, 0 iterations, SUCCESS; maxIterations == 0
+ * takes no step either.  rows == 0: SUCCESS, 0 iterations, nothing is read or written through b / x.  The zero start of the other
+ * drivers applies (an x of zeros and finite values: r1 = b with no SpMV).
+ * M: NULL, or a handle of T's dtype on a matrix with as many rows as `a`, of a kind smm_hip_cg_* takes (IC0 / CHEBYSHEV / AMG /
+ *   MULTICOLOR_SGS / MULTICOLOR_IC0 / FSAI / JSWEEP_SGS / JSWEEP_IC0; the JSWEEP kinds with as many lower steps as upper ones).  It
+ *   need NOT be created for `a`: a preconditioner of an indefinite `a` is refused at create or is not positive definite, so M is built on
+ *   a positive definite relative of `a` -- the unshifted operator, the (1,1) block plus a mass matrix.  A handle of kind NONE is refused.
+ * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one solve give the same bits.
+ * SMM_HIP_ERR_INVALID (the message starts with "minres:"): a null or dtype-mismatched matrix, a matrix that is not square, null vectors
+ * with rows > 0, an M that fails the check above.
+ * Additive outputs (may be NULL, like solver_status): iterations, resnorm2. */
+int smm_hip_minres_f32(const smm_hip_csr* a, float* b, float* x, int maxIterations, float eps, const smm_hip_precond* M, int* solver_status, int* iterations,
+                       float* resnorm2);
+int smm_hip_minres_f64(const smm_hip_csr* a, double* b, double* x, int maxIterations, double eps, const smm_hip_precond* M, int* solver_status, int* iterations,
+                       double* resnorm2);
+int smm_hip_minres_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, int maxIterations, float eps, const smm_hip_precond* M, smm_hip_stream stream,
+                           int* solver_status, int* iterations, float* resnorm2);
+int smm_hip_minres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, const smm_hip_precond* M, smm_hip_stream stream,
+                           int* solver_status, int* iterations, double* resnorm2);
+
 /* smm_hip_idrs_*: IDR(s) in the biorthogonal form (Sonneveld and van Gijzen 2008; van Gijzen and Sonneveld 2011) with right
  * preconditioning -- an addition, the reference has no IDR(s) (csrc/smm_solvers_idrs.hip; the definition, line by line, is
  * tests/idrs_restatement.py).  For general matrices: transpose-free, one SpMV per step, recurrences of the fixed length s with no

@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::IDRs, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
 //
@@ -74,6 +74,9 @@ struct Abi<float> {
 	static int gmres(const smm_hip_csr* a, float* b, float* x, int it, float eps, int restart, const smm_hip_precond* M, int* st) {
 		return smm_hip_gmres_f32(a, b, x, it, eps, restart, M, st, nullptr, nullptr);
 	}
+	static int minres(const smm_hip_csr* a, float* b, float* x, int it, float eps, const smm_hip_precond* M, int* st) {
+		return smm_hip_minres_f32(a, b, x, it, eps, M, st, nullptr, nullptr);
+	}
 	static int idrs(const smm_hip_csr* a, float* b, float* x, int it, float eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f32(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
 	}
@@ -113,6 +116,9 @@ struct Abi<double> {
 	static int cgs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int* st) { return smm_hip_cgs_f64(a, b, x, it, eps, st, nullptr, nullptr); }
 	static int gmres(const smm_hip_csr* a, double* b, double* x, int it, double eps, int restart, const smm_hip_precond* M, int* st) {
 		return smm_hip_gmres_f64(a, b, x, it, eps, restart, M, st, nullptr, nullptr);
+	}
+	static int minres(const smm_hip_csr* a, double* b, double* x, int it, double eps, const smm_hip_precond* M, int* st) {
+		return smm_hip_minres_f64(a, b, x, it, eps, M, st, nullptr, nullptr);
 	}
 	static int idrs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f64(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
@@ -1445,6 +1451,29 @@ inline SolverStatus GMRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, 
 template <typename T>
 inline SolverStatus GMRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps, int restart = 30) {
 	return GMRES(a, b, x, maxIterations, eps, restart, typename CSRMatrix<T>::IDPreconditioner());
+}
+
+// ---- an addition with no counterpart in the reference: MINRES with a symmetric positive definite preconditioner (smm_hip.h states the loop) ----
+// For symmetric matrices, indefinite ones included (symmetry is the caller's business, as with ConjugateGradient); x is the initial guess and
+// receives the result; maxIterations == -1 means rows, otherwise it is clamped to rows.  Takes the IDPreconditioner or one of CSRMatrix<T>'s own
+// preconditioner classes of a kind ConjugateGradient takes -- built on a positive definite matrix of the same size, which need not be `a` (a
+// preconditioner of an indefinite `a` is not positive definite).  With a preconditioner the stop test reads the residual's M^-1-norm.
+template <typename Preconditioner, typename T>
+inline SolverStatus MINRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps, const Preconditioner& preconditioner) {
+	static_assert(std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value ||
+	                  std::is_base_of<typename CSRMatrix<T>::PreconditionerBase, Preconditioner>::value,
+	              "MINRES runs the library's own preconditioners only");
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = preconditioner.handle();
+	constexpr bool precondition = !std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value;
+	if (d && precondition && !h) return SolverStatus::DIVERGED;  // (the preconditioner could not be built: lastHipStatus() says why)
+	const int rc = d ? detail::Abi<T>::minres(d, b, x, maxIterations, eps, h, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+template <typename T>
+inline SolverStatus MINRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps) {
+	return MINRES(a, b, x, maxIterations, eps, typename CSRMatrix<T>::IDPreconditioner());
 }
 
 // ---- an addition with no counterpart in the reference: IDR(s), biorthogonal form, with right preconditioning (smm_hip.h states the loop) ----

@@ -25,6 +25,7 @@ from .host import (  # noqa: F401
     BiCG,
     ConjugateGradientSquared,
     GMRES,
+    MINRES,
     IDRs,
     IDRS_MAX_S,
     IterativeRefinement,
@@ -39,6 +40,7 @@ from .host import (  # noqa: F401
     bicg_dev,
     cgs_dev,
     gmres_dev,
+    minres_dev,
     idrs_dev,
     idrs_shadow_dev,
     refine_dev,

@@ -63,6 +63,8 @@ _TYPED = {
     "smm_hip_cgs_dev": (c_int, [_P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_gmres": (c_int, [_P, _P, _P, c_int, "T", c_int, _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_gmres_dev": (c_int, [_P, _P, _P, c_int, "T", c_int, _P, _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_minres": (c_int, [_P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_minres_dev": (c_int, [_P, _P, _P, c_int, "T", _P, _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_idrs": (c_int, [_P, _P, _P, c_int, "T", c_int, _P, c_ulonglong, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_idrs_dev": (c_int, [_P, _P, _P, c_int, "T", c_int, _P, _P, c_longlong, c_ulonglong, _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_idrs_shadow_dev": (c_int, [c_int, c_int, c_ulonglong, _P, c_longlong, _P]),

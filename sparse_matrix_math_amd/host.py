@@ -1101,6 +1101,30 @@ def gmres_dev(a, d_b, d_x, maxIterations, eps, restart=30, M=None, stream=None):
     return SolverStatus(st.value), it.value, res.value
 
 
+def MINRES(a, b, x, maxIterations, eps, M=None, info=None):
+    """MINRES with a symmetric positive definite preconditioner -- an addition (include/smm_hip.h states the loop).  For symmetric
+    matrices, indefinite ones included; x is the initial guess and receives the result; maxIterations == -1 means rows, otherwise it is
+    clamped to rows.  M: None or a preconditioner of a kind ConjugateGradient takes, created on a positive definite matrix of the same size
+    (it need not be `a`).  `info`, when a dict, receives iterations and resnorm2 (the last phibar^2: the squared residual norm, in the
+    M^-1-norm when M is given)."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_minres", suf)(a._h, _host(b, a.dtype, "b", a.rows), _host(x, a.dtype, "x", a.rows, True), int(maxIterations),
+                                     a.dtype.type(eps), _mh(M), ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+    if info is not None:
+        info.update(iterations=it.value, resnorm2=res.value)
+    return SolverStatus(st.value)
+
+
+def minres_dev(a, d_b, d_x, maxIterations, eps, M=None, stream=None):
+    """device-pointer MINRES; returns (SolverStatus, iterations, resnorm2).  Synchronises `stream`."""
+    suf = a._suf
+    st, it, res = ctypes.c_int(), ctypes.c_int(), _CT[suf]()
+    check(_fn("smm_hip_minres_dev", suf)(a._h, _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), _mh(M), _dptr(stream),
+                                         ctypes.byref(st), ctypes.byref(it), ctypes.byref(res)))
+    return SolverStatus(st.value), it.value, res.value
+
+
 IDRS_MAX_S = 8  # SMM_IDRS_MAX_S
 
 
