@@ -967,6 +967,63 @@ int smm_hip_minres_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, i
 int smm_hip_minres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, const smm_hip_precond* M, smm_hip_stream stream,
                            int* solver_status, int* iterations, double* resnorm2);
 
+/* smm_hip_eigsh_*: the k algebraically LARGEST or SMALLEST eigenvalues of a symmetric matrix, with their eigenvectors, by thick-restart
+ * Lanczos (Wu and Simon 2000) with full reorthogonalisation -- an addition, the reference has no eigensolver
+ * (csrc/smm_solvers_eigsh.hip; the definition, line by line, is tests/eigsh_restatement.py).  Symmetry of `a` is the caller's business,
+ * as with smm_hip_cg_* and smm_hip_minres_*: smm_hip_csr_is_symmetric tells.
+ * Parameters: k >= 1 wanted pairs; which = SMM_EIGSH_LARGEST or SMM_EIGSH_SMALLEST; ncv basis columns with
+ *   k + 2 <= ncv <= min(rows, SMM_EIGSH_MAX_NCV), ncv == 0 meaning min(rows, max(2k + 1, 20)); maxRestarts >= 0; tol, with tol <= 0
+ *   meaning the machine epsilon of T; a start vector v0, or NULL for the hash vector of `seed`.
+ * The basis V has ncv + 1 columns (leading dimension rounded up to 64); its first l columns are kept Ritz vectors, l = 0 at first.
+ *   v_0 = v0 / ||v0||.  The hash vector of (seed, col) has the elements of smm_hip_idrs_shadow_dev_*: ((h >> 40) + 0.5) 2^-23 - 1 with
+ *     h = sm(sm(sm(seed) ^ col) ^ row); the start is col = 0, and every later fresh vector takes the next col.
+ *   a cycle, for j = l .. ncv-1:
+ *     w = A v_j
+ *     twice (classical Gram-Schmidt): h_i = v_i.w for all i <= j from the same w; w = _smm_fma(-h_i, v_i, w), i ascending
+ *     alpha_j = the sum of the two passes' h_j;  beta_j = sqrt(w.w);  scale = max(scale, |alpha_j|, beta_j)
+ *     beta_j <= eps(T) * scale: a BREAKDOWN at j -- v_{j+1} is not formed, nothing divides by beta_j, the cycle ends with m = j + 1
+ *     v_{j+1} = w / beta_j
+ *   (scale: the largest |alpha|, beta or kept |theta| seen so far in the solve.  All of this runs on the device without a host read.)
+ *   the Ritz step, once per cycle, on the host in fp64 for both dtypes (cyclic Jacobi): with m = ncv, or j + 1 after a breakdown,
+ *     T (m x m) = diag(theta_kept), the arrow s in row and column l, alpha on the rest of the diagonal, beta beside it;  T = Y diag(theta) Y^T
+ *     rho_i = |beta_{m-1} Y[m-1][i]|, 0 after a breakdown
+ *   the k wanted pairs have converged when rho_i <= tol * max_i |theta_i| for each of them (the maximum over all m Ritz values: an
+ *     estimate of ||A||_2 from below, so that an eigenvalue at 0 can be tested)
+ *   the solve ends on convergence, on a breakdown with m >= k (an exact invariant subspace) or when maxRestarts restarts were made:
+ *     X = V[:, 0..m-1] Y[:, wanted];  eigenvalues in the order of `which`: descending for LARGEST, ascending for SMALLEST
+ *   otherwise a restart: l = k + (ncv - k) / 2;  V[:, 0..l-1] = V[:, 0..m-1] Y[:, best l] in place (smm_hip_multi_rotate_dev_*);
+ *     v_l = v_m;  theta_kept = those Ritz values;  s_i = beta_{m-1} Y[m-1][i]
+ *   a breakdown with m < k: all m Ritz vectors are kept (l = m), s = 0, and v_m = the next hash vector, orthogonalised twice against
+ *     the kept columns and normalised; this counts as a restart.  Copies of a multiple eigenvalue are found this way.
+ * Outputs: eigenvalues[k]; eigenvectors (may be NULL: none are formed) column-major, vector i at eigenvectors + i * ldx, ldx >= rows.
+ *   smm_hip_eigsh_* takes host arrays; smm_hip_eigsh_dev_* takes d_v0, d_eigenvalues and d_eigenvectors in device memory (element
+ *   alignment suffices) and synchronises `stream`.  The additive outputs are host words and may each be NULL: residuals[k] (rho_i),
+ *   nconv (wanted pairs that passed the test), restarts, matvecs (SpMVs: ncv + restarts * (ncv - l) when nothing broke down),
+ *   solver_status: SUCCESS if all k converged, MAX_ITERATIONS_REACHED if not -- the pairs returned are then the best available, with
+ *   their rho_i (only min(k, m) of them when a breakdown left fewer) --, DIVERGED if an alpha, a beta, a theta or a start vector's norm
+ *   is not finite (or that norm is 0): the eigenpairs are not written then.
+ * rows == 0 or k == 0: SUCCESS, nothing is touched.
+ * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one call give the same bits.
+ * Memory: (ncv + 1) * rows elements for the basis, nothing else of that size.
+ * WHAT THIS IS NOT: no shift-invert, no preconditioning, no interior eigenvalues.  The smallest eigenvalues of a large Laplacian
+ *   converge slowly, as with any plain Lanczos.  From a start vector that lies in an invariant subspace the pairs returned are that
+ *   subspace's: the method cannot leave it.
+ * SMM_HIP_ERR_INVALID (the message starts with "eigsh:"; checked before the device is touched, the outputs are not written): a null or
+ * dtype-mismatched matrix, a matrix that is not square, k < 0, another `which`, maxRestarts < 0, an ncv (after the default) outside
+ * k + 2 .. min(rows, SMM_EIGSH_MAX_NCV) -- so k > rows - 2 always --, null eigenvalues, ldx < rows with eigenvectors. */
+#define SMM_EIGSH_LARGEST 0
+#define SMM_EIGSH_SMALLEST 1
+#define SMM_EIGSH_MAX_NCV 64
+int smm_hip_eigsh_f32(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, float tol, const float* v0, unsigned long long seed, float* eigenvalues,
+                      float* eigenvectors, long long ldx, float* residuals, int* nconv, int* restarts, int* matvecs, int* solver_status);
+int smm_hip_eigsh_f64(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, double tol, const double* v0, unsigned long long seed, double* eigenvalues,
+                      double* eigenvectors, long long ldx, double* residuals, int* nconv, int* restarts, int* matvecs, int* solver_status);
+int smm_hip_eigsh_dev_f32(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, float tol, const float* d_v0, unsigned long long seed, float* d_eigenvalues,
+                          float* d_eigenvectors, long long ldx, smm_hip_stream stream, float* residuals, int* nconv, int* restarts, int* matvecs, int* solver_status);
+int smm_hip_eigsh_dev_f64(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, double tol, const double* d_v0, unsigned long long seed,
+                          double* d_eigenvalues, double* d_eigenvectors, long long ldx, smm_hip_stream stream, double* residuals, int* nconv, int* restarts,
+                          int* matvecs, int* solver_status);
+
 /* smm_hip_idrs_*: IDR(s) in the biorthogonal form (Sonneveld and van Gijzen 2008; van Gijzen and Sonneveld 2011) with right
  * preconditioning -- an addition, the reference has no IDR(s) (csrc/smm_solvers_idrs.hip; the definition, line by line, is
  * tests/idrs_restatement.py).  For general matrices: transpose-free, one SpMV per step, recurrences of the fixed length s with no
@@ -1078,6 +1135,21 @@ int smm_hip_multi_dot_dev_f32(int n, int k, const float* d_V, long long ld, cons
 int smm_hip_multi_dot_dev_f64(int n, int k, const double* d_V, long long ld, const double* d_w, double* d_out, smm_hip_stream stream);
 int smm_hip_multi_axpy_dev_f32(int n, int k, const float* d_V, long long ld, const float* d_coef, const float* d_w, float* d_out, smm_hip_stream stream);
 int smm_hip_multi_axpy_dev_f64(int n, int k, const double* d_V, long long ld, const double* d_coef, const double* d_w, double* d_out, smm_hip_stream stream);
+
+/* multi_rotate: the in-place basis compression of smm_hip_eigsh_*: V[:, 0..l-1] = V[:, 0..m-1] Y, with d_V as above (m columns of n
+ * elements, column i at d_V + i * ld) and h_Y an m x l matrix in HOST memory, column-major, element (i, c) at h_Y[i + c * ldY]
+ * (ldY >= m); 1 <= l <= m <= SMM_EIGSH_MAX_NCV.  Rows are independent: a lane loads the m values of its rows, forms the l outputs one
+ * after the other -- out_c = V_0 Y[0][c], then _smm_fma(Y[j][c], V_j, out_c) for j = 1 .. m-1 ascending -- and stores each as it is formed;
+ * it holds its whole row by then, so column c may be overwritten.  n m elements are read and n l written, none twice; the columns
+ * l .. m-1 keep their bits, and what lies between n and ld is neither read nor written.  m is padded to 16 / 32 / 64 by zero rows of
+ * Y (the padding columns of V are not loaded).  16-byte loads and stores (four fp32 or two fp64 rows per lane) are used when d_V is
+ * 16-byte aligned, ld keeps the columns so and the padded m is at most 32; otherwise -- and always for the padding 64, where a pack of
+ * rows would need 256 registers a lane -- a lane owns one row, and a wavefront's load of a column is still one contiguous run.
+ * Synchronises `stream` (the staged copy of Y is released on return).
+ * SMM_HIP_ERR_INVALID: n < 0, l < 1, m < l, m > SMM_EIGSH_MAX_NCV, ld < n, ldY < m, a null h_Y, a null d_V with n > 0; checked before
+ * the device is touched. */
+int smm_hip_multi_rotate_dev_f32(int n, int m, int l, float* d_V, long long ld, const float* h_Y, long long ldY, smm_hip_stream stream);
+int smm_hip_multi_rotate_dev_f64(int n, int m, int l, double* d_V, long long ld, const double* h_Y, long long ldY, smm_hip_stream stream);
 
 /* ---- preconditioners: `int apply(const T* rhs, T* x) const noexcept` (ref:1173-1235) --------------------------
  * create: replaces CSRMatrix<T>::getPreconditioner<kind>() (ref:1643-1651) / IC0Preconditioner::init (ref:1798).

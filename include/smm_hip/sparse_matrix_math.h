@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::IDRs, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::eigsh, SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
 //
@@ -77,6 +77,10 @@ struct Abi<float> {
 	static int minres(const smm_hip_csr* a, float* b, float* x, int it, float eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_minres_f32(a, b, x, it, eps, M, st, nullptr, nullptr);
 	}
+	static int eigsh(const smm_hip_csr* a, int k, int which, int ncv, int restarts, float tol, const float* v0, unsigned long long seed, float* w, float* x, long long ldx,
+	                 float* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
+		return smm_hip_eigsh_f32(a, k, which, ncv, restarts, tol, v0, seed, w, x, ldx, rho, nconv, nrestarts, matvecs, st);
+	}
 	static int idrs(const smm_hip_csr* a, float* b, float* x, int it, float eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f32(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
 	}
@@ -119,6 +123,10 @@ struct Abi<double> {
 	}
 	static int minres(const smm_hip_csr* a, double* b, double* x, int it, double eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_minres_f64(a, b, x, it, eps, M, st, nullptr, nullptr);
+	}
+	static int eigsh(const smm_hip_csr* a, int k, int which, int ncv, int restarts, double tol, const double* v0, unsigned long long seed, double* w, double* x, long long ldx,
+	                 double* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
+		return smm_hip_eigsh_f64(a, k, which, ncv, restarts, tol, v0, seed, w, x, ldx, rho, nconv, nrestarts, matvecs, st);
 	}
 	static int idrs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f64(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
@@ -1474,6 +1482,28 @@ inline SolverStatus MINRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations,
 template <typename T>
 inline SolverStatus MINRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps) {
 	return MINRES(a, b, x, maxIterations, eps, typename CSRMatrix<T>::IDPreconditioner());
+}
+
+// ---- an addition with no counterpart in the reference: the k algebraically largest or smallest eigenpairs of a symmetric matrix by
+// thick-restart Lanczos on the device (smm_hip.h states the algorithm) ----
+// which: SMM_EIGSH_LARGEST or SMM_EIGSH_SMALLEST.  eigenvalues[k] come out in the order of `which` (descending / ascending); eigenvectors
+// (may be null) receives vector i at eigenvectors + i * rows.  ncv == 0 means min(rows, max(2k + 1, 20)); tol <= 0 the machine epsilon of T;
+// v0 == nullptr the hash vector of `seed`.  SUCCESS: all k converged; MAX_ITERATIONS_REACHED: the pairs are the best available; DIVERGED:
+// a value that is not finite, or the call failed (lastHipStatus() says why).  No shift-invert, no preconditioning, no interior eigenvalues.
+struct EigshInfo {
+	int nconv = 0, restarts = 0, matvecs = 0;
+};
+template <typename T>
+inline SolverStatus eigsh(const CSRMatrix<T>& a, int k, int which, T* eigenvalues, T* eigenvectors = nullptr, int ncv = 0, T tol = T(0), int maxRestarts = 300,
+                          const T* v0 = nullptr, unsigned long long seed = 0, T* residuals = nullptr, EigshInfo* info = nullptr) {
+	int st = 0;
+	EigshInfo local;
+	EigshInfo* o = info ? info : &local;
+	const smm_hip_csr* d = a.device();
+	const int rc = d ? detail::Abi<T>::eigsh(d, k, which, ncv, maxRestarts, tol, v0, seed, eigenvalues, eigenvectors, static_cast<long long>(a.getDenseRowCount()),
+	                                         residuals, &o->nconv, &o->restarts, &o->matvecs, &st)
+	                 : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
 }
 
 // ---- an addition with no counterpart in the reference: IDR(s), biorthogonal form, with right preconditioning (smm_hip.h states the loop) ----

@@ -70,6 +70,11 @@ _TYPED = {
     "smm_hip_idrs_shadow_dev": (c_int, [c_int, c_int, c_ulonglong, _P, c_longlong, _P]),
     "smm_hip_multi_dot_dev": (c_int, [c_int, c_int, _P, c_longlong, _P, _P, _P]),
     "smm_hip_multi_axpy_dev": (c_int, [c_int, c_int, _P, c_longlong, _P, _P, _P, _P]),
+    "smm_hip_multi_rotate_dev": (c_int, [c_int, c_int, c_int, _P, c_longlong, _P, c_longlong, _P]),
+    "smm_hip_eigsh": (c_int, [_P, c_int, c_int, c_int, c_int, "T", _P, c_ulonglong, _P, _P, c_longlong, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                              POINTER(c_int)]),
+    "smm_hip_eigsh_dev": (c_int, [_P, c_int, c_int, c_int, c_int, "T", _P, c_ulonglong, _P, _P, c_longlong, _P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                  POINTER(c_int)]),
     "smm_hip_bicg": (c_int, [_P, _P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicg_dev": (c_int, [_P, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_precond_apply": (c_int, [_P, _P, _P]),

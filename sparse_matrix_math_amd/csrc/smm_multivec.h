@@ -178,4 +178,101 @@ inline int gridMV(long long n, size_t elemBytes) {
 	return static_cast<int>(std::max<long long>(1, std::min<long long>((n + tile - 1) / tile, NPART)));
 }
 
+// multiRotate: V[:, 0..l-1] = V[:, 0..m-1] Y in place (smm_solvers_eigsh.hip: a Lanczos basis compressed onto its Ritz vectors).  Rows are
+// independent: a lane loads the m values of its R rows (R consecutive rows: one load of R elements per column), forms the l outputs one
+// after the other -- j ascending, smmFma nesting, from the plain product of column 0 -- and stores each as it is formed: the lane holds its
+// whole row by then, so writing column c over a column that was read is safe.  n m elements read, n l written, none twice.
+// The row lives in registers under static indices: MP is m rounded up to 16 / 32 / 64, the columns m .. MP-1 are not loaded (zeros stand
+// in for them) and Y's rows m .. MP-1 are zero.  Y (MP x l, column-major, leading dimension MP) is staged in LDS once per workgroup and
+// read from there at wave-uniform addresses.  MR_MAX_HELD: the row values a lane may hold, in 32-bit registers -- 128 of the 512 a SIMD
+// lane has, so that with the accumulators and addresses three waves per SIMD stay resident.
+constexpr int MR_MAX = 64;
+constexpr int MR_MAX_HELD = 128;
+
+template <typename T, int MP, int R>
+__device__ __forceinline__ void multiRotateRows(T* row, long long ld, int m, int l, const T* Ys) {
+	using P = typename Pack16<T>::V;
+	static_assert(R == 1 || R == Pack16<T>::N, "one row per lane, or one 16-byte pack of rows");
+	T v[MP][R];
+#pragma unroll
+	for (int j = 0; j < MP; ++j) {
+		if (j < m) {  // (uniform)
+			if constexpr (R == 1) {
+				v[j][0] = row[j * ld];
+			} else {
+				const P p = *reinterpret_cast<const P*>(row + j * ld);
+#pragma unroll
+				for (int e = 0; e < R; ++e) v[j][e] = p[e];
+			}
+		} else {
+#pragma unroll
+			for (int e = 0; e < R; ++e) v[j][e] = T(0);
+		}
+	}
+	for (int c = 0; c < l; ++c) {
+		const T* y = Ys + c * MP;
+		T acc[R];
+#pragma unroll
+		for (int e = 0; e < R; ++e) acc[e] = y[0] * v[0][e];
+#pragma unroll
+		for (int j = 1; j < MP; ++j) {
+			const T yj = y[j];
+#pragma unroll
+			for (int e = 0; e < R; ++e) acc[e] = smmFma(yj, v[j][e], acc[e]);
+		}
+		if constexpr (R == 1) {
+			row[c * ld] = acc[0];
+		} else {
+			P p;
+#pragma unroll
+			for (int e = 0; e < R; ++e) p[e] = acc[e];
+			*reinterpret_cast<P*>(row + c * ld) = p;
+		}
+	}
+}
+
+// R > 1 needs V 16-byte aligned and ld a multiple of R (the launcher checks); the last n % R rows take one lane each.
+template <typename T, int MP, int R>
+__global__ __launch_bounds__(MV_TPB) void multiRotateKernel(long long n, int m, int l, T* V, long long ld, const T* __restrict__ Y) {
+	__shared__ T Ys[MP * MP];
+	for (int i = threadIdx.x; i < MP * l; i += MV_TPB) Ys[i] = Y[i];
+	__syncthreads();
+	const long long packs = n / R;
+	for (long long i = static_cast<long long>(blockIdx.x) * MV_TPB + threadIdx.x; i < packs; i += static_cast<long long>(gridDim.x) * MV_TPB) {
+		multiRotateRows<T, MP, R>(V + i * R, ld, m, l, Ys);
+	}
+	if (R > 1 && blockIdx.x == 0) {
+		const long long i = packs * R + threadIdx.x;
+		if (i < n) multiRotateRows<T, MP, 1>(V + i, ld, m, l, Ys);
+	}
+}
+
+template <typename T, int MP>
+inline void multiRotateLaunchMP(long long n, int m, int l, T* V, long long ld, const T* dY, hipStream_t s) {
+	constexpr int N = Pack16<T>::N;
+	constexpr bool fits = MP * N * static_cast<int>(sizeof(T) / 4) <= MR_MAX_HELD;  // a pack of rows per lane only where its values fit the budget
+	const bool vec = fits && (reinterpret_cast<unsigned long long>(V) & 15ull) == 0 && ld % N == 0;
+	const long long lanes = vec ? (n / N > 0 ? n / N : 1) : n;
+	const int g = static_cast<int>(std::max<long long>(1, std::min<long long>((lanes + MV_TPB - 1) / MV_TPB, 4 * NPART)));
+	if constexpr (fits) {
+		if (vec) {
+			multiRotateKernel<T, MP, N><<<g, MV_TPB, 0, s>>>(n, m, l, V, ld, dY);
+			return;
+		}
+	}
+	multiRotateKernel<T, MP, 1><<<g, MV_TPB, 0, s>>>(n, m, l, V, ld, dY);
+}
+
+inline int multiRotatePad(int m) { return m <= 16 ? 16 : m <= 32 ? 32 : MR_MAX; }
+
+// dY: multiRotatePad(m) x l, column-major, zero rows below row m.  1 <= l <= m <= MR_MAX, n > 0 (the caller checks).
+template <typename T>
+inline void multiRotateLaunch(long long n, int m, int l, T* V, long long ld, const T* dY, hipStream_t s) {
+	switch (multiRotatePad(m)) {
+		case 16: multiRotateLaunchMP<T, 16>(n, m, l, V, ld, dY, s); break;
+		case 32: multiRotateLaunchMP<T, 32>(n, m, l, V, ld, dY, s); break;
+		default: multiRotateLaunchMP<T, 64>(n, m, l, V, ld, dY, s); break;
+	}
+}
+
 }  // namespace smm

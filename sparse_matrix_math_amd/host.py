@@ -10,6 +10,7 @@ callers that keep their data in HBM (bench.py, the multi-GPU driver).
 
 Everything here runs on the GPU through libsmm_hip.so.  There is no CPU implementation in this package.
 """
+import collections
 import ctypes
 import enum
 
@@ -1220,6 +1221,66 @@ def multi_dot_dev(n, k, d_V, ld, d_w, d_out, dtype, stream=None):
 def multi_axpy_dev(n, k, d_V, ld, d_coef, d_w, d_out, dtype, stream=None):
     """d_out = d_w + sum_i d_coef[i] v_i, i ascending through _smm_fma, on device pointers; d_out may alias d_w; asynchronous"""
     check(_fn("smm_hip_multi_axpy_dev", _suffix(dtype))(int(n), int(k), _dptr(d_V), int(ld), _dptr(d_coef), _dptr(d_w), _dptr(d_out), _dptr(stream)))
+
+
+def multi_rotate_dev(n, m, l, d_V, ld, Y, dtype, stream=None):
+    """V[:, :l] = V[:, :m] @ Y in place on a device pointer (m columns of n elements, column i at d_V + i * ld); Y: an (m, l) HOST array
+    of `dtype`.  Each output is formed j ascending through _smm_fma; the columns l .. m-1 keep their bits.  Synchronises `stream`."""
+    Y = np.asarray(Y)
+    if Y.dtype != np.dtype(dtype) or Y.shape != (int(m), int(l)):
+        raise TypeError(f"Y must be an ({m}, {l}) array of {np.dtype(dtype)}")
+    Yf = np.asfortranarray(Y)  # element (i, c) at i + c * m
+    check(_fn("smm_hip_multi_rotate_dev", _suffix(dtype))(int(n), int(m), int(l), _dptr(d_V), int(ld), Yf.ctypes.data_as(ctypes.c_void_p), int(m), _dptr(stream)))
+
+
+EIGSH_LARGEST, EIGSH_SMALLEST = 0, 1  # SMM_EIGSH_LARGEST, SMM_EIGSH_SMALLEST
+EIGSH_MAX_NCV = 64  # SMM_EIGSH_MAX_NCV
+_EIGSH_WHICH = {"LA": EIGSH_LARGEST, "SA": EIGSH_SMALLEST}
+EigshInfo = collections.namedtuple("EigshInfo", "residuals nconv restarts matvecs status")
+
+
+def _eigsh_which(which):
+    if isinstance(which, str):
+        try:
+            return _EIGSH_WHICH[which.upper()]
+        except KeyError:
+            raise ValueError(f"which must be 'LA' (largest algebraic) or 'SA' (smallest algebraic), got {which!r}")
+    return int(which)
+
+
+def eigsh(a, k=6, which="LA", ncv=None, tol=0.0, max_restarts=300, v0=None, seed=0, return_eigenvectors=True):
+    """The k algebraically largest ("LA") or smallest ("SA") eigenvalues of the symmetric CSRMatrix `a`, with their eigenvectors, by
+    thick-restart Lanczos on the device -- an addition (include/smm_hip.h states the algorithm).  ncv: basis columns, k + 2 <= ncv <=
+    min(rows, EIGSH_MAX_NCV); None means min(rows, max(2k + 1, 20)).  tol <= 0 means the machine epsilon of the dtype; the test is
+    rho_i <= tol * max|theta|.  v0: a start vector, or None for the hash vector of `seed`.  Returns (w, X, info), or (w, info) with
+    return_eigenvectors=False: w in the order of `which` (descending for "LA", ascending for "SA"), X of shape (rows, k) with the
+    eigenvectors in its columns, info an EigshInfo(residuals, nconv, restarts, matvecs, status).  When status is not SUCCESS the pairs are
+    the best available.  No shift-invert, no preconditioning, no interior eigenvalues."""
+    suf = a._suf
+    k = int(k)
+    w = np.zeros(max(k, 0), dtype=a.dtype)
+    res = np.zeros(max(k, 0), dtype=a.dtype)
+    X = np.zeros((max(k, 0), a.rows), dtype=a.dtype) if return_eigenvectors else None  # row i: eigenvector i (column-major (rows, k))
+    nconv, restarts, matvecs, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_fn("smm_hip_eigsh", suf)(a._h, k, _eigsh_which(which), 0 if ncv is None else int(ncv), int(max_restarts), a.dtype.type(tol),
+                                    None if v0 is None else _host(v0, a.dtype, "v0", a.rows), int(seed), w.ctypes.data_as(ctypes.c_void_p),
+                                    None if X is None else X.ctypes.data_as(ctypes.c_void_p), a.rows, res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
+                                    ctypes.byref(restarts), ctypes.byref(matvecs), ctypes.byref(st)))
+    info = EigshInfo(res, nconv.value, restarts.value, matvecs.value, SolverStatus(st.value))
+    return (w, X.T, info) if return_eigenvectors else (w, info)
+
+
+def eigsh_dev(a, k, which, d_w, d_X, ldx, ncv=None, tol=0.0, max_restarts=300, d_v0=None, seed=0, stream=None):
+    """device-pointer eigsh: d_w receives the k eigenvalues, d_X (may be None) eigenvector i at d_X + i * ldx; d_v0: None or a start
+    vector on the device.  Returns an EigshInfo (residuals: a host array).  Synchronises `stream`."""
+    suf = a._suf
+    k = int(k)
+    res = np.zeros(max(k, 0), dtype=a.dtype)
+    nconv, restarts, matvecs, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_fn("smm_hip_eigsh_dev", suf)(a._h, k, _eigsh_which(which), 0 if ncv is None else int(ncv), int(max_restarts), a.dtype.type(tol), _dptr(d_v0), int(seed),
+                                        _dptr(d_w), _dptr(d_X), int(ldx), _dptr(stream), res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
+                                        ctypes.byref(restarts), ctypes.byref(matvecs), ctypes.byref(st)))
+    return EigshInfo(res, nconv.value, restarts.value, matvecs.value, SolverStatus(st.value))
 
 
 def BiCG(a, b, x, maxIterations, eps, at=None, info=None):
