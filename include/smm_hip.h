@@ -1005,9 +1005,10 @@ int smm_hip_minres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x,
  * rows == 0 or k == 0: SUCCESS, nothing is touched.
  * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one call give the same bits.
  * Memory: (ncv + 1) * rows elements for the basis, nothing else of that size.
- * WHAT THIS IS NOT: no shift-invert, no preconditioning, no interior eigenvalues.  The smallest eigenvalues of a large Laplacian
- *   converge slowly, as with any plain Lanczos.  From a start vector that lies in an invariant subspace the pairs returned are that
- *   subspace's: the method cannot leave it.
+ * WHAT THIS IS NOT: no shift-invert, no interior eigenvalues, and no preconditioning -- smm_hip_lobpcg_* (below) is the preconditioned
+ *   method, and a block one.  The smallest eigenvalues of a large Laplacian converge slowly here, as with any plain Lanczos: they are
+ *   what smm_hip_lobpcg_* with an AMG or incomplete-factorisation preconditioner is for.  From a start vector that lies in an invariant
+ *   subspace the pairs returned are that subspace's: the method cannot leave it.
  * SMM_HIP_ERR_INVALID (the message starts with "eigsh:"; checked before the device is touched, the outputs are not written): a null or
  * dtype-mismatched matrix, a matrix that is not square, k < 0, another `which`, maxRestarts < 0, an ncv (after the default) outside
  * k + 2 .. min(rows, SMM_EIGSH_MAX_NCV) -- so k > rows - 2 always --, null eigenvalues, ldx < rows with eigenvectors. */
@@ -1023,6 +1024,73 @@ int smm_hip_eigsh_dev_f32(const smm_hip_csr* a, int k, int which, int ncv, int m
 int smm_hip_eigsh_dev_f64(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, double tol, const double* d_v0, unsigned long long seed,
                           double* d_eigenvalues, double* d_eigenvectors, long long ldx, smm_hip_stream stream, double* residuals, int* nconv, int* restarts,
                           int* matvecs, int* solver_status);
+
+/* smm_hip_lobpcg_*: the k algebraically LARGEST or SMALLEST eigenvalues of a symmetric matrix, with their eigenvectors, by LOBPCG
+ * (Knyazev 2001), the locally optimal block preconditioned conjugate gradient method, with the SVQB orthonormalisation of the search
+ * block (Stathopoulos and Wu 2002) -- an addition, the reference has no eigensolver (csrc/smm_solvers_lobpcg.hip; the definition,
+ * line by line, is tests/lobpcg_restatement.py).  Where smm_hip_eigsh_* is plain Lanczos, this takes a PRECONDITIONER -- the smallest
+ * eigenpairs of a stiffness or Laplacian matrix with the AMG V-cycle or an incomplete factorisation are what it is for -- and it is a
+ * block method: a cluster or a multiple eigenvalue inside the block is an ordinary input.  Symmetry of `a` is the caller's business.
+ * Parameters: 1 <= k <= SMM_LOBPCG_MAX_K wanted pairs, the block size, with 3k <= rows; which = SMM_EIGSH_LARGEST or SMM_EIGSH_SMALLEST;
+ *   maxIterations >= 0; tol, with tol <= 0 meaning the machine epsilon of T; M, NULL or a symmetric positive definite preconditioner
+ *   (below); a start block X0 of k columns, column j at X0 + j * ldx0 (ldx0 >= rows), or NULL for the hash columns (seed, col = 0..k-1)
+ *   of smm_hip_idrs_shadow_dev_* as they are before that routine's orthonormalisation.
+ * The loop.  S = [X P W] and AS = [AX AP AW] are two bases of 3k columns (leading dimension rounded up to 64); Z = [P W]:
+ *   X = the start block, made orthonormal column by column: classical Gram-Schmidt twice against the columns before, then a division by
+ *       the norm d.  A d, or the column's norm d0 before the two passes, that is not finite, or d <= sqrt(eps(T)) d0 (the block has
+ *       rank below k to working precision): DIVERGED.
+ *   AX = A X (k SpMVs);  T = X^T AX;  on the host in fp64 for both dtypes: 1/2 (T + T^T) = C diag(theta) C^T by cyclic Jacobi, ordered
+ *       by `which`;  X = X C, AX = AX C (smm_hip_multi_rotate_dev_*);  P, AP empty;  scale = 0
+ *   for it = 0, 1, ...:
+ *     R_j = AX_j - theta_j X_j,  rn_j = ||R_j||_2 for all j < k                            (rn comes to the host)
+ *     scale = max(scale, |theta_i|) over EVERY Ritz value of the last Rayleigh-Ritz step (an estimate of ||A||_2 from below, as in eigsh)
+ *     active = the j with !(rn_j <= tol * scale);  none: SUCCESS;  it == maxIterations: MAX_ITERATIONS_REACHED
+ *     W = M^-1 R[:, active], column by column (smm_hip_precond_apply_dev_*), or R[:, active] without M;  AW = A W, column by column
+ *     twice:
+ *       H = X^T Z (smm_hip_multi_gram_dev_*);  Z = Z - X H;  AZ = AZ - AX H (smm_hip_multi_block_axpy_dev_*; H stays on the device)
+ *       G = Z^T Z -> host, 1/2 (G + G^T), fp64;  d = sqrt(diag G), the columns with d == 0 dropped;  G / (d d^T) = Q diag(w) Q^T
+ *       kept: the w_i > (columns left) * eps(T) * max w, the largest first
+ *       Y = diag(1 / d) Q[:, kept] diag(w_kept^-1/2);  Z = Z Y, AZ = AZ Y              (SVQB: a rank-deficient direction is dropped,
+ *                                                                                       nothing divides by a vanishing norm)
+ *     T = S^T AS over S = [X Z] -> host, 1/2 (T + T^T) = C diag(theta) C^T;  C = the k eigenvectors wanted by `which`
+ *     P = Z C_Z[:, the first min(|active|, columns of Z) active columns], AP likewise (C_Z: the rows of C below the first k)
+ *     X = S C,  AX = AS C                                (one in-place multi_rotate per basis forms [X P]; AX and AP are never recomputed)
+ *   The host reads four things per iteration: rn, the two G and T.
+ * Outputs: eigenvalues[k] in the order of `which` (descending for LARGEST, ascending for SMALLEST); eigenvectors (may be NULL)
+ *   column-major, vector j at eigenvectors + j * ldx, ldx >= rows.  smm_hip_lobpcg_* takes host arrays; smm_hip_lobpcg_dev_* takes d_X0,
+ *   d_eigenvalues and d_eigenvectors in device memory (element alignment suffices) and synchronises `stream`.  The additive outputs are
+ *   host words and may each be NULL: residuals[k] (the last rn_j), nconv (columns that passed the test), iterations, matvecs
+ *   (k + the sum of |active|), applies (the sum of |active| with M, 0 without), solver_status: SUCCESS, MAX_ITERATIONS_REACHED -- the
+ *   pairs returned are then the best available -- or DIVERGED: a theta, an rn, a Gram entry or a start column's norm that is not finite, or
+ *   a start block of rank below k; the eigenpairs are not written then.
+ * rows == 0 or k == 0: SUCCESS, nothing is touched.
+ * M: NULL, or any kind smm_hip_cg_* accepts (an iterated sweep needs equal step counts), or JACOBI or SGS -- symmetric positive definite
+ *   for a positive definite matrix too; smm_hip_cg_*'s fused loop has no path for them, here every kind runs through its apply.  As with
+ *   smm_hip_minres_* it must FIT `a` (same dtype, same rows), it need not be created for it: a shifted L - sigma I takes the
+ *   preconditioner of L.  With SMM_EIGSH_LARGEST an M is legal but seldom useful: a preconditioner that approximates A^-1 damps the
+ *   very directions wanted.
+ * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one call give the same bits.
+ * Memory: 6k vectors plus the preconditioner's own.
+ * WHAT THIS IS NOT: no generalised problem A x = lambda B x, no interior eigenvalues, no hard locking (a converged column stays in the
+ *   Rayleigh-Ritz basis and only stops producing a residual direction), no column-major SpMM: A W is |active| SpMVs.
+ * SMM_HIP_ERR_INVALID (the message starts with "lobpcg:"; checked before the device is touched, the outputs are not written): a null or
+ * dtype-mismatched matrix, a matrix that is not square, k < 0 or k > SMM_LOBPCG_MAX_K, 3k > rows (a matrix that small is dense work, or
+ * smm_hip_eigsh_*'s), another `which`, maxIterations < 0, null eigenvalues, ldx < rows with eigenvectors, ldx0 < rows with X0, a
+ * preconditioner of a kind smm_hip_cg_* refuses other than JACOBI and SGS, of the other dtype or of another size. */
+#define SMM_LOBPCG_MAX_K 8
+#define SMM_LOBPCG_MAX_BASIS 24
+int smm_hip_lobpcg_f32(const smm_hip_csr* a, int k, int which, int maxIterations, float tol, const smm_hip_precond* M, const float* X0, long long ldx0,
+                       unsigned long long seed, float* eigenvalues, float* eigenvectors, long long ldx, float* residuals, int* nconv, int* iterations, int* matvecs,
+                       int* applies, int* solver_status);
+int smm_hip_lobpcg_f64(const smm_hip_csr* a, int k, int which, int maxIterations, double tol, const smm_hip_precond* M, const double* X0, long long ldx0,
+                       unsigned long long seed, double* eigenvalues, double* eigenvectors, long long ldx, double* residuals, int* nconv, int* iterations, int* matvecs,
+                       int* applies, int* solver_status);
+int smm_hip_lobpcg_dev_f32(const smm_hip_csr* a, int k, int which, int maxIterations, float tol, const smm_hip_precond* M, const float* d_X0, long long ldx0,
+                           unsigned long long seed, float* d_eigenvalues, float* d_eigenvectors, long long ldx, smm_hip_stream stream, float* residuals, int* nconv,
+                           int* iterations, int* matvecs, int* applies, int* solver_status);
+int smm_hip_lobpcg_dev_f64(const smm_hip_csr* a, int k, int which, int maxIterations, double tol, const smm_hip_precond* M, const double* d_X0, long long ldx0,
+                           unsigned long long seed, double* d_eigenvalues, double* d_eigenvectors, long long ldx, smm_hip_stream stream, double* residuals, int* nconv,
+                           int* iterations, int* matvecs, int* applies, int* solver_status);
 
 /* smm_hip_idrs_*: IDR(s) in the biorthogonal form (Sonneveld and van Gijzen 2008; van Gijzen and Sonneveld 2011) with right
  * preconditioning -- an addition, the reference has no IDR(s) (csrc/smm_solvers_idrs.hip; the definition, line by line, is
@@ -1150,6 +1218,29 @@ int smm_hip_multi_axpy_dev_f64(int n, int k, const double* d_V, long long ld, co
  * the device is touched. */
 int smm_hip_multi_rotate_dev_f32(int n, int m, int l, float* d_V, long long ld, const float* h_Y, long long ldY, smm_hip_stream stream);
 int smm_hip_multi_rotate_dev_f64(int n, int m, int l, double* d_V, long long ld, const double* h_Y, long long ldY, smm_hip_stream stream);
+
+/* The two block x block kernels of smm_hip_lobpcg_* on device pointers (csrc/smm_multiblock.h).  d_V holds m columns and d_W l columns of
+ * n elements, column i at d_V + i * ldV (ldV, ldW >= n; what lies between n and ld is neither read nor written); 1 <= m, l <=
+ * SMM_LOBPCG_MAX_BASIS.  Every pointer may be element-aligned; 16-byte accesses are used when both blocks are 16-byte aligned and both
+ * leading dimensions keep the columns so.  Asynchronous on `stream`.
+ *   multi_gram:  d_G (m x l, column-major, element (i, j) at d_G[i + j * ldG], ldG >= m, DEVICE memory) = V^T W.  d_V == d_W with m == l
+ *     and ldV == ldW is legal: the symmetric case, every element is then loaded once.  On the matrix cores (v_mfma_f64_16x16x4_f64 /
+ *     v_mfma_f32_16x16x4_f32, fp32 in and out, no reduced precision): a lane loads the one element it feeds as operand, so every element
+ *     of V and of W is read from memory ONCE per call; accumulation in T, per-workgroup partial sums and a finishing pass in a fixed
+ *     order, no floating-point atomics: two calls give the same bits.  n == 0 gives zeros.
+ *   multi_block_axpy:  W[:, c] = W[:, c] - sum_j d_H[j + c * ldH] V[:, j] for all c < l, j ascending, each term
+ *     _smm_fma(-H[j][c], V_j, W_c).  d_H is m x l, column-major, ldH >= m, in DEVICE memory: a multi_gram result feeds it with no host
+ *     read in between.  V and W must not overlap.  A lane holds its rows of V: each element of V is read once, each of W read and
+ *     written once.
+ * SMM_HIP_ERR_INVALID (checked before the device is touched): n < 0, m or l outside 1 .. SMM_LOBPCG_MAX_BASIS, ldV < n, ldW < n,
+ * ldG / ldH < m, a null d_G / d_H, a null d_V or d_W with n > 0. */
+int smm_hip_multi_gram_dev_f32(int n, int m, int l, const float* d_V, long long ldV, const float* d_W, long long ldW, float* d_G, long long ldG, smm_hip_stream stream);
+int smm_hip_multi_gram_dev_f64(int n, int m, int l, const double* d_V, long long ldV, const double* d_W, long long ldW, double* d_G, long long ldG,
+                               smm_hip_stream stream);
+int smm_hip_multi_block_axpy_dev_f32(int n, int m, int l, const float* d_V, long long ldV, const float* d_H, long long ldH, float* d_W, long long ldW,
+                                     smm_hip_stream stream);
+int smm_hip_multi_block_axpy_dev_f64(int n, int m, int l, const double* d_V, long long ldV, const double* d_H, long long ldH, double* d_W, long long ldW,
+                                     smm_hip_stream stream);
 
 /* ---- preconditioners: `int apply(const T* rhs, T* x) const noexcept` (ref:1173-1235) --------------------------
  * create: replaces CSRMatrix<T>::getPreconditioner<kind>() (ref:1643-1651) / IC0Preconditioner::init (ref:1798).

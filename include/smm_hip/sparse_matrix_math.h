@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::eigsh, SMM::IDRs, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::eigsh, SMM::lobpcg, SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
 //
@@ -81,6 +81,10 @@ struct Abi<float> {
 	                 float* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
 		return smm_hip_eigsh_f32(a, k, which, ncv, restarts, tol, v0, seed, w, x, ldx, rho, nconv, nrestarts, matvecs, st);
 	}
+	static int lobpcg(const smm_hip_csr* a, int k, int which, int it, float tol, const smm_hip_precond* M, const float* x0, long long ldx0, unsigned long long seed, float* w,
+	                  float* x, long long ldx, float* rn, int* nconv, int* iterations, int* matvecs, int* applies, int* st) {
+		return smm_hip_lobpcg_f32(a, k, which, it, tol, M, x0, ldx0, seed, w, x, ldx, rn, nconv, iterations, matvecs, applies, st);
+	}
 	static int idrs(const smm_hip_csr* a, float* b, float* x, int it, float eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f32(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
 	}
@@ -127,6 +131,10 @@ struct Abi<double> {
 	static int eigsh(const smm_hip_csr* a, int k, int which, int ncv, int restarts, double tol, const double* v0, unsigned long long seed, double* w, double* x, long long ldx,
 	                 double* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
 		return smm_hip_eigsh_f64(a, k, which, ncv, restarts, tol, v0, seed, w, x, ldx, rho, nconv, nrestarts, matvecs, st);
+	}
+	static int lobpcg(const smm_hip_csr* a, int k, int which, int it, double tol, const smm_hip_precond* M, const double* x0, long long ldx0, unsigned long long seed, double* w,
+	                  double* x, long long ldx, double* rn, int* nconv, int* iterations, int* matvecs, int* applies, int* st) {
+		return smm_hip_lobpcg_f64(a, k, which, it, tol, M, x0, ldx0, seed, w, x, ldx, rn, nconv, iterations, matvecs, applies, st);
 	}
 	static int idrs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f64(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
@@ -1489,7 +1497,7 @@ inline SolverStatus MINRES(const CSRMatrix<T>& a, T* b, T* x, int maxIterations,
 // which: SMM_EIGSH_LARGEST or SMM_EIGSH_SMALLEST.  eigenvalues[k] come out in the order of `which` (descending / ascending); eigenvectors
 // (may be null) receives vector i at eigenvectors + i * rows.  ncv == 0 means min(rows, max(2k + 1, 20)); tol <= 0 the machine epsilon of T;
 // v0 == nullptr the hash vector of `seed`.  SUCCESS: all k converged; MAX_ITERATIONS_REACHED: the pairs are the best available; DIVERGED:
-// a value that is not finite, or the call failed (lastHipStatus() says why).  No shift-invert, no preconditioning, no interior eigenvalues.
+// a value that is not finite, or the call failed (lastHipStatus() says why).  No shift-invert, no interior eigenvalues; not preconditioned: SMM::lobpcg is.
 struct EigshInfo {
 	int nconv = 0, restarts = 0, matvecs = 0;
 };
@@ -1504,6 +1512,42 @@ inline SolverStatus eigsh(const CSRMatrix<T>& a, int k, int which, T* eigenvalue
 	                                         residuals, &o->nconv, &o->restarts, &o->matvecs, &st)
 	                 : SMM_HIP_ERR_NO_DEVICE;
 	return detail::toStatus(rc, st);
+}
+
+// ---- an addition with no counterpart in the reference: the k algebraically largest or smallest eigenpairs of a symmetric matrix by LOBPCG,
+// the preconditioned block method (smm_hip.h states the loop) ----
+// 1 <= k <= SMM_LOBPCG_MAX_K with 3k <= rows; which: SMM_EIGSH_LARGEST or SMM_EIGSH_SMALLEST.  eigenvalues[k] come out in the order of `which`;
+// eigenvectors (may be null) receives vector j at eigenvectors + j * rows.  Takes the IDPreconditioner or one of CSRMatrix<T>'s own
+// preconditioner classes of a kind ConjugateGradient takes (or JACOBI / SGS), built on a positive definite matrix of the same size, which need not be `a` (a
+// shifted L - sigma I takes the preconditioner of L).  tol <= 0 means the machine epsilon of T; X0 == nullptr the hash columns of `seed`,
+// otherwise k start columns, column j at X0 + j * rows.  SUCCESS: all k converged; MAX_ITERATIONS_REACHED: the pairs are the best available;
+// DIVERGED: a value that is not finite, a start block of rank below k, or the call failed (lastHipStatus() says why).
+struct LobpcgInfo {
+	int nconv = 0, iterations = 0, matvecs = 0, applies = 0;
+};
+template <typename Preconditioner, typename T>
+inline SolverStatus lobpcg(const CSRMatrix<T>& a, int k, int which, T* eigenvalues, T* eigenvectors, const Preconditioner& preconditioner, T tol = T(0),
+                           int maxIterations = 1000, const T* X0 = nullptr, unsigned long long seed = 0, T* residuals = nullptr, LobpcgInfo* info = nullptr) {
+	static_assert(std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value ||
+	                  std::is_base_of<typename CSRMatrix<T>::PreconditionerBase, Preconditioner>::value,
+	              "lobpcg runs the library's own preconditioners only");
+	int st = 0;
+	LobpcgInfo local;
+	LobpcgInfo* o = info ? info : &local;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_precond* h = preconditioner.handle();
+	constexpr bool precondition = !std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value;
+	if (d && precondition && !h) return SolverStatus::DIVERGED;  // (the preconditioner could not be built: lastHipStatus() says why)
+	const long long rows = static_cast<long long>(a.getDenseRowCount());
+	const int rc = d ? detail::Abi<T>::lobpcg(d, k, which, maxIterations, tol, h, X0, rows, seed, eigenvalues, eigenvectors, rows, residuals, &o->nconv, &o->iterations,
+	                                          &o->matvecs, &o->applies, &st)
+	                 : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+template <typename T>
+inline SolverStatus lobpcg(const CSRMatrix<T>& a, int k, int which, T* eigenvalues, T* eigenvectors = nullptr, T tol = T(0), int maxIterations = 1000,
+                           const T* X0 = nullptr, unsigned long long seed = 0, T* residuals = nullptr, LobpcgInfo* info = nullptr) {
+	return lobpcg(a, k, which, eigenvalues, eigenvectors, typename CSRMatrix<T>::IDPreconditioner(), tol, maxIterations, X0, seed, residuals, info);
 }
 
 // ---- an addition with no counterpart in the reference: IDR(s), biorthogonal form, with right preconditioning (smm_hip.h states the loop) ----

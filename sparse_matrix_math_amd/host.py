@@ -1255,7 +1255,7 @@ def eigsh(a, k=6, which="LA", ncv=None, tol=0.0, max_restarts=300, v0=None, seed
     rho_i <= tol * max|theta|.  v0: a start vector, or None for the hash vector of `seed`.  Returns (w, X, info), or (w, info) with
     return_eigenvectors=False: w in the order of `which` (descending for "LA", ascending for "SA"), X of shape (rows, k) with the
     eigenvectors in its columns, info an EigshInfo(residuals, nconv, restarts, matvecs, status).  When status is not SUCCESS the pairs are
-    the best available.  No shift-invert, no preconditioning, no interior eigenvalues."""
+    the best available.  No shift-invert, no interior eigenvalues, and not preconditioned: lobpcg is."""
     suf = a._suf
     k = int(k)
     w = np.zeros(max(k, 0), dtype=a.dtype)
@@ -1281,6 +1281,64 @@ def eigsh_dev(a, k, which, d_w, d_X, ldx, ncv=None, tol=0.0, max_restarts=300, d
                                         _dptr(d_w), _dptr(d_X), int(ldx), _dptr(stream), res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
                                         ctypes.byref(restarts), ctypes.byref(matvecs), ctypes.byref(st)))
     return EigshInfo(res, nconv.value, restarts.value, matvecs.value, SolverStatus(st.value))
+
+
+LOBPCG_MAX_K, LOBPCG_MAX_BASIS = 8, 24  # SMM_LOBPCG_MAX_K, SMM_LOBPCG_MAX_BASIS
+LobpcgInfo = collections.namedtuple("LobpcgInfo", "residuals nconv iterations matvecs applies status")
+
+
+def lobpcg(a, k=4, which="SA", M=None, X0=None, tol=0.0, max_iterations=1000, seed=0, return_eigenvectors=True):
+    """The k algebraically smallest ("SA") or largest ("LA") eigenvalues of the symmetric CSRMatrix `a`, with their eigenvectors, by
+    LOBPCG on the device -- the preconditioned block method, an addition (include/smm_hip.h states the loop).  1 <= k <= LOBPCG_MAX_K
+    with 3k <= rows.  M: None or a symmetric positive definite preconditioner (any kind ConjugateGradient takes, or JACOBI or SGS) of a matrix of the same
+    size, which need not be `a`: a shifted L - sigma I takes the preconditioner of L; with "LA" an M is legal but seldom useful.  X0:
+    None for the hash columns of `seed`, or a (rows, k) start block.  tol <= 0 means the machine epsilon of the dtype; column j has
+    converged when ||A x_j - theta_j x_j|| <= tol * max|theta|.  Returns (w, X, info), or (w, info) with return_eigenvectors=False: w in
+    the order of `which`, X of shape (rows, k), info a LobpcgInfo(residuals, nconv, iterations, matvecs, applies, status).  When status
+    is MAX_ITERATIONS_REACHED the pairs are the best available; when it is DIVERGED they are not written."""
+    suf = a._suf
+    k = int(k)
+    w = np.zeros(max(k, 0), dtype=a.dtype)
+    res = np.zeros(max(k, 0), dtype=a.dtype)
+    X = np.zeros((max(k, 0), a.rows), dtype=a.dtype) if return_eigenvectors else None  # row j: eigenvector j (column-major (rows, k))
+    start = None
+    if X0 is not None:
+        X0 = np.asarray(X0)
+        if X0.dtype != a.dtype or X0.shape != (a.rows, k):
+            raise TypeError(f"X0 must be a ({a.rows}, {k}) array of {a.dtype}")
+        start = np.ascontiguousarray(X0.T)  # row j: start column j
+    nconv, its, matvecs, applies, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_fn("smm_hip_lobpcg", suf)(a._h, k, _eigsh_which(which), int(max_iterations), a.dtype.type(tol), _mh(M),
+                                     None if start is None else start.ctypes.data_as(ctypes.c_void_p), a.rows, int(seed), w.ctypes.data_as(ctypes.c_void_p),
+                                     None if X is None else X.ctypes.data_as(ctypes.c_void_p), a.rows, res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
+                                     ctypes.byref(its), ctypes.byref(matvecs), ctypes.byref(applies), ctypes.byref(st)))
+    info = LobpcgInfo(res, nconv.value, its.value, matvecs.value, applies.value, SolverStatus(st.value))
+    return (w, X.T, info) if return_eigenvectors else (w, info)
+
+
+def lobpcg_dev(a, k, which, d_w, d_X, ldx, M=None, d_X0=None, ldx0=0, tol=0.0, max_iterations=1000, seed=0, stream=None):
+    """device-pointer lobpcg: d_w receives the k eigenvalues, d_X (may be None) eigenvector j at d_X + j * ldx; d_X0: None or k start
+    columns on the device, column j at d_X0 + j * ldx0.  Returns a LobpcgInfo (residuals: a host array).  Synchronises `stream`."""
+    suf = a._suf
+    k = int(k)
+    res = np.zeros(max(k, 0), dtype=a.dtype)
+    nconv, its, matvecs, applies, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_fn("smm_hip_lobpcg_dev", suf)(a._h, k, _eigsh_which(which), int(max_iterations), a.dtype.type(tol), _mh(M), _dptr(d_X0), int(ldx0), int(seed), _dptr(d_w),
+                                         _dptr(d_X), int(ldx), _dptr(stream), res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv), ctypes.byref(its),
+                                         ctypes.byref(matvecs), ctypes.byref(applies), ctypes.byref(st)))
+    return LobpcgInfo(res, nconv.value, its.value, matvecs.value, applies.value, SolverStatus(st.value))
+
+
+def multi_gram_dev(n, m, l, d_V, ldV, d_W, ldW, d_G, ldG, dtype, stream=None):
+    """d_G (m x l, column-major, leading dimension ldG, on the device) = V^T W for m columns of V and l of W (column i at d_V + i * ldV);
+    d_W may be d_V (the symmetric case).  Fixed-order sums: two calls give the same bits.  Asynchronous."""
+    check(_fn("smm_hip_multi_gram_dev", _suffix(dtype))(int(n), int(m), int(l), _dptr(d_V), int(ldV), _dptr(d_W), int(ldW), _dptr(d_G), int(ldG), _dptr(stream)))
+
+
+def multi_block_axpy_dev(n, m, l, d_V, ldV, d_H, ldH, d_W, ldW, dtype, stream=None):
+    """W[:, c] -= sum_j H[j][c] V[:, j], j ascending through _smm_fma, for the l columns of W; d_H: m x l, column-major, on the device.
+    V and W must not overlap.  Asynchronous."""
+    check(_fn("smm_hip_multi_block_axpy_dev", _suffix(dtype))(int(n), int(m), int(l), _dptr(d_V), int(ldV), _dptr(d_H), int(ldH), _dptr(d_W), int(ldW), _dptr(stream)))
 
 
 def BiCG(a, b, x, maxIterations, eps, at=None, info=None):
