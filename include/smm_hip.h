@@ -967,6 +967,64 @@ int smm_hip_minres_dev_f32(const smm_hip_csr* a, const float* d_b, float* d_x, i
 int smm_hip_minres_dev_f64(const smm_hip_csr* a, const double* d_b, double* d_x, int maxIterations, double eps, const smm_hip_precond* M, smm_hip_stream stream,
                            int* solver_status, int* iterations, double* resnorm2);
 
+/* smm_hip_lsqr_*: LSQR (Paige and Saunders 1982) for min ||A x - b||_2 with a matrix of ANY shape, with Tikhonov damping -- an addition,
+ * the reference has no LSQR (csrc/smm_solvers_lsqr.hip; the definition, line by line, is tests/lsqr_restatement.py).
+ * For overdetermined systems (data fitting: the least-squares answer), underdetermined ones (from x = 0: the minimum-norm answer),
+ * rank-deficient ones (from x = 0: the minimum-norm least-squares answer) and square ones that are not symmetric.  It works on A, never
+ * on AtA, whose condition number is the square.  Two SpMVs per step -- one on `a`, one on `at` -- and two inner products; five work
+ * vectors (two of rows, three of cols elements).
+ * Operands: `a` is rows x cols; b has rows elements, x has cols (in/out: the start is read from it).  `at` is the transpose of `a`:
+ *   NULL     the library builds one for the duration of the solve (a device sort per call: keep one when solving more than once)
+ *   a handle from smm_hip_csr_transpose_create_* or the caller's own.  Checked: its dtype, at.rows == a.cols, at.cols == a.rows, equal
+ *            entry counts.  That it IS the transpose is the caller's contract.
+ *   `a`      the caller asserts symmetry; legal only for a square `a`.
+ * Semantics (`iterations` counts steps; the sums are those of smm_hip_minres_*):
+ *   maxIterations < 0 means cols; there is no other clamp (LSQR in floating point may need more than cols steps)
+ *   ub = b - A x  (the zero start of the other drivers applies: an x of zeros and finite values, ub = b with no SpMV)
+ *   bb = ub.ub;  beta = sqrt(bb)                                   -- ub stays UNNORMALISED in memory: u = ub / beta
+ *   t = At ub;  vb = t / beta  (beta == 0: vb = 0);  aa = vb.vb;  alpha = sqrt(aa)
+ *   beta or alpha not finite: DIVERGED, 0 iterations, x untouched
+ *   bb == 0: SUCCESS, 0 iterations, reason 1, x untouched
+ *   aa == 0: SUCCESS, 0 iterations, reason 2, x untouched (b - A x is orthogonal to the range of A)
+ *   v = vb / alpha;  w = v;  phibar = beta; rhobar = alpha; psi2 = 0; res = bb; arn = (alpha beta)^2
+ *   while (res > eps*eps && arn > eps*eps && iterations < maxIterations) {
+ *     q = A v;  ub = _smm_fma(-(alpha / beta), ub, q);  bb = ub.ub;  beta = sqrt(bb)
+ *     t = At ub;  vb = _smm_fma(-beta, v, t / beta)  (beta == 0: vb = 0, nothing is divided);  aa = vb.vb;  alpha = sqrt(aa)
+ *     damp == 0: rb1 = rhobar; psi = 0  (the first rotation is the identity, bit for bit)
+ *     otherwise: rb1 = sqrt(rhobar^2 + damp^2); c1 = rhobar / rb1; s1 = damp / rb1; psi = s1 phibar; phibar = c1 phibar
+ *     rho = sqrt(rb1^2 + bb); c = rb1 / rho; s = beta / rho; theta = s alpha; rhobar = -c alpha; phi = c phibar; phibar = s phibar
+ *     beta, alpha, rho or phibar not finite, or rho == 0: DIVERGED, the step is not taken, x keeps its last value
+ *     x = _smm_fma(phi / rho, w, x);  v = vb / alpha  (alpha == 0: v = 0);  w = _smm_fma(-(theta / rho), w, v)
+ *     psi2 += psi^2;  res = phibar^2 + psi2;  arn = (alpha |c| phibar)^2;  iterations++
+ *     beta == 0 or alpha == 0: the bidiagonalisation has ended (res or arn is 0 now): the loop ends
+ *   }
+ *   status: DIVERGED on the tests above; else SUCCESS if res <= eps*eps (reason 1) or arn <= eps*eps (reason 2; reason 1 wins when both
+ *   hold); else MAX_ITERATIONS_REACHED (reason 0).  maxIterations == 0 takes no step: the status is that of the start values.
+ * x IS UPDATED IN PLACE.  The solve is for the correction dx = x - x0 of A dx = b - A x0, and each step adds its term to x itself; no
+ *   separate dx is kept, so from x0 = 0 x holds dx's bits.  With damp > 0 the problem solved is min ||A dx - (b - A x0)||^2 + damp^2 ||dx||^2:
+ *   it is the CORRECTION that is damped, not x.  Start from x = 0 to damp x.
+ * THE STOP TESTS ARE ABSOLUTE and on squared norms, as in smm_hip_cg_* and smm_hip_minres_*: res estimates ||b - A x||^2 + damp^2 ||dx||^2
+ *   and arn estimates ||At (b - A x) - damp^2 dx||^2; both come from the recurrence, not from a residual that is formed.  There are no
+ *   relative atol / btol tests and no condition estimate.
+ * AN INCONSISTENT SYSTEM ENDS BY REASON 2 WITH A RESIDUAL THAT IS NOT SMALL: that is what least squares means.  resnorm2 then tells how
+ *   far b is from the range of A.
+ * Edges, none of them a fault or a NaN: rows == 0 (SUCCESS, reason 1) or cols == 0 (SUCCESS, reason 2): 0 iterations, resnorm2 =
+ *   arnorm2 = 0, nothing is read or written through b / x.  A matrix without entries: reason 2 at once (reason 1 for b == 0), no SpMV and
+ *   no transpose.  Empty rows and empty columns are legal; an x element of an empty column keeps its start value.
+ * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one solve give the same bits.
+ * SMM_HIP_ERR_INVALID (the message starts with "lsqr:"): a null or dtype-mismatched matrix, an `at` of the other dtype, of another shape
+ * or entry count, `a` as `at` when `a` is not square, null vectors when rows > 0 and cols > 0, an eps or damp that is negative or not
+ * finite.  Nothing is written then.
+ * Additive outputs (may be NULL, like solver_status): iterations, reason, resnorm2 = the last res, arnorm2 = the last arn. */
+int smm_hip_lsqr_f32(const smm_hip_csr* a, const smm_hip_csr* at, float* b, float* x, int maxIterations, float eps, float damp, int* solver_status, int* iterations,
+                     int* reason, float* resnorm2, float* arnorm2);
+int smm_hip_lsqr_f64(const smm_hip_csr* a, const smm_hip_csr* at, double* b, double* x, int maxIterations, double eps, double damp, int* solver_status,
+                     int* iterations, int* reason, double* resnorm2, double* arnorm2);
+int smm_hip_lsqr_dev_f32(const smm_hip_csr* a, const smm_hip_csr* at, const float* d_b, float* d_x, int maxIterations, float eps, float damp, smm_hip_stream stream,
+                         int* solver_status, int* iterations, int* reason, float* resnorm2, float* arnorm2);
+int smm_hip_lsqr_dev_f64(const smm_hip_csr* a, const smm_hip_csr* at, const double* d_b, double* d_x, int maxIterations, double eps, double damp,
+                         smm_hip_stream stream, int* solver_status, int* iterations, int* reason, double* resnorm2, double* arnorm2);
+
 /* smm_hip_eigsh_*: the k algebraically LARGEST or SMALLEST eigenvalues of a symmetric matrix, with their eigenvectors, by thick-restart
  * Lanczos (Wu and Simon 2000) with full reorthogonalisation -- an addition, the reference has no eigensolver
  * (csrc/smm_solvers_eigsh.hip; the definition, line by line, is tests/eigsh_restatement.py).  Symmetry of `a` is the caller's business,

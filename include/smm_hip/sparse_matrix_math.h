@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::eigsh, SMM::lobpcg, SMM::IDRs, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::LSQR, SMM::eigsh, SMM::lobpcg, SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
 //
@@ -89,6 +89,9 @@ struct Abi<float> {
 		return smm_hip_idrs_f32(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
 	}
 	static int bicg(const smm_hip_csr* a, const smm_hip_csr* at, float* b, float* x, int it, float eps, int* st) { return smm_hip_bicg_f32(a, at, b, x, it, eps, st, nullptr, nullptr); }
+	static int lsqr(const smm_hip_csr* a, const smm_hip_csr* at, float* b, float* x, int it, float eps, float damp, int* st, int* steps, int* reason) {
+		return smm_hip_lsqr_f32(a, at, b, x, it, eps, damp, st, steps, reason, nullptr, nullptr);
+	}
 	static int apply(const smm_hip_precond* M, const float* r, float* x) { return smm_hip_precond_apply_f32(M, r, x); }
 	static int scale(smm_hip_csr* m, float a) { return smm_hip_csr_scale_f32(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, float a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f32(m, a, o, nullptr); }
@@ -140,6 +143,9 @@ struct Abi<double> {
 		return smm_hip_idrs_f64(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
 	}
 	static int bicg(const smm_hip_csr* a, const smm_hip_csr* at, double* b, double* x, int it, double eps, int* st) { return smm_hip_bicg_f64(a, at, b, x, it, eps, st, nullptr, nullptr); }
+	static int lsqr(const smm_hip_csr* a, const smm_hip_csr* at, double* b, double* x, int it, double eps, double damp, int* st, int* steps, int* reason) {
+		return smm_hip_lsqr_f64(a, at, b, x, it, eps, damp, st, steps, reason, nullptr, nullptr);
+	}
 	static int apply(const smm_hip_precond* M, const double* r, double* x) { return smm_hip_precond_apply_f64(M, r, x); }
 	static int scale(smm_hip_csr* m, double a) { return smm_hip_csr_scale_f64(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, double a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f64(m, a, o, nullptr); }
@@ -1664,6 +1670,22 @@ inline SolverStatus BiCG(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T
 	int st = 0;
 	const smm_hip_csr* d = a.device();
 	const int rc = d ? detail::Abi<T>::bicg(d, nullptr, b, x, maxIterations, eps, &st) : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// ---- an addition with no counterpart in the reference: LSQR for least-squares and rectangular systems (smm_hip.h states the loop) ----
+// min ||a x - b||_2 for a matrix of any shape: b has a.denseRowCount elements, x has a.denseColCount, is the initial guess and receives
+// the result.  The stop tests are absolute (eps against the estimates of ||b - a x|| and of ||at (b - a x)||: an inconsistent system ends
+// by the second, SUCCESS with *reason == 2 and a residual that is not small); damp > 0 damps the correction x - x0.  `at`: the transpose
+// (SMM::transpose) kept by the caller, null to have one built for the duration of the solve, or &a to assert symmetry of a square matrix.
+template <typename T>
+inline SolverStatus LSQR(const CSRMatrix<T>& a, T* b, T* x, int maxIterations, T eps, typename std::enable_if<true, T>::type damp = T(0),
+                         const CSRMatrix<typename std::enable_if<true, T>::type>* at = nullptr, int* iterations = nullptr, int* reason = nullptr) {
+	// (damp and at are not deduced: LSQR(a, b, x, -1, eps, 0.5, nullptr) works for float and double)
+	int st = 0;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_csr* dt = !at ? nullptr : (at == &a ? d : at->device());
+	const int rc = d && (!at || dt) ? detail::Abi<T>::lsqr(d, dt, b, x, maxIterations, eps, damp, &st, iterations, reason) : SMM_HIP_ERR_NO_DEVICE;
 	return detail::toStatus(rc, st);
 }
 

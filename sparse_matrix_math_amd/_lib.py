@@ -83,6 +83,8 @@ _TYPED = {
     "smm_hip_multi_block_axpy_dev": (c_int, [c_int, c_int, c_int, _P, c_longlong, _P, c_longlong, _P, c_longlong, _P]),
     "smm_hip_bicg": (c_int, [_P, _P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicg_dev": (c_int, [_P, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
+    "smm_hip_lsqr": (c_int, [_P, _P, _P, _P, c_int, "T", "T", POINTER(c_int), POINTER(c_int), POINTER(c_int), "PT", "PT"]),
+    "smm_hip_lsqr_dev": (c_int, [_P, _P, _P, _P, c_int, "T", "T", _P, POINTER(c_int), POINTER(c_int), POINTER(c_int), "PT", "PT"]),
     "smm_hip_precond_apply": (c_int, [_P, _P, _P]),
     "smm_hip_precond_apply_dev": (c_int, [_P, _P, _P, _P]),
     "smm_hip_precond_apply_spmv": (c_int, [_P, _P, _P]),

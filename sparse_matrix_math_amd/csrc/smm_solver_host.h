@@ -30,6 +30,21 @@ int solverCheck(const char* who, const smm_hip_csr* a, const V*... vectors) {
 	return SMM_HIP_OK;
 }
 
+// The rectangular sibling (LSQR): `a` is rows x cols with any rows and cols, `b` has rows elements and `x` has cols; a vector may be null
+// only when it has no element.
+template <typename T>
+int solverCheckRect(const char* who, const smm_hip_csr* a, const T* b, const T* x) {
+	if (!a || a->dtype != dtypeOf<T>()) {
+		setError("%s: null matrix or dtype mismatch", who);
+		return SMM_HIP_ERR_INVALID;
+	}
+	if ((a->rows > 0 && a->cols > 0) && (!b || !x)) {
+		setError("%s: null vector", who);
+		return SMM_HIP_ERR_INVALID;
+	}
+	return SMM_HIP_OK;
+}
+
 // Synchronises `s` when the scope is left while still armed.  Declared after whatever the queued work touches (staging buffers, a
 // transpose built for the solve) and disarmed on the path that has synchronised anyway: no error return releases them under queued work.
 struct SyncOnExit {
@@ -95,16 +110,17 @@ struct LoopWatch {
 // the host knows both, so the driver launches no SpMV for the set-up and copies b instead.  x0 is read once (n elements); values[] is read
 // once per version of the values (smm_hip_csr::values_finite), the first time a start is found to be zero.  Each look is one word through
 // the watch's mailbox and a stream synchronise, before the set-up is enqueued.  SMM_HIP_ZERO_START=0: never (the SpMV runs).
+// `count`: the elements of x0 -- a->cols, which a square matrix's driver may write as a->rows (the form without it).
 template <typename T>
-int zeroStart(const smm_hip_csr* a, const T* x0, LoopWatch& watch, hipStream_t s, bool* skip) {
+int zeroStart(const smm_hip_csr* a, const T* x0, long long count, LoopWatch& watch, hipStream_t s, bool* skip) {
 	*skip = false;
-	if (a->rows <= 0 || !env::flagOr(env::ZERO_START, true)) return SMM_HIP_OK;
+	if (count <= 0 || !env::flagOr(env::ZERO_START, true)) return SMM_HIP_OK;
 	int finite = a->values_finite.load(std::memory_order_acquire);
 	if (finite == 0) return SMM_HIP_OK;
 	DevBuf<int> word;
 	SMM_TRY(word.alloc(1));
 	int zero = 0;
-	SMM_TRY(launchScanFlag<T>(a->rows, x0, false, word, s));
+	SMM_TRY(launchScanFlag<T>(count, x0, false, word, s));
 	SMM_TRY(watch.fetch(word, &zero));
 	if (!zero) return SMM_HIP_OK;
 	if (finite < 0) {
@@ -114,6 +130,11 @@ int zeroStart(const smm_hip_csr* a, const T* x0, LoopWatch& watch, hipStream_t s
 	}
 	*skip = finite != 0;
 	return SMM_HIP_OK;
+}
+
+template <typename T>
+int zeroStart(const smm_hip_csr* a, const T* x0, LoopWatch& watch, hipStream_t s, bool* skip) {
+	return zeroStart<T>(a, x0, a->rows, watch, s, skip);
 }
 
 // The end of every loop: the watch's or a launch's error, else `bytes` of the loop's device scalars on the host; synchronises `s`.
@@ -161,6 +182,24 @@ int solveFromHost(size_t count, const T* b, const T* x0, T* x, Run&& run, const 
 		SetupTrace trace(tr.out);
 		SMM_TRY(devToHost(x, dx, sizeof(T) * count, s));
 	}
+	drain.armed = false;  // (the driver's read-back and devToHost have synchronised)
+	return SMM_HIP_OK;
+}
+
+// The host-pointer form of a driver whose two vectors differ in length (LSQR: b has the matrix's rows, x its columns): b (`countB`
+// elements) and x (`countX`, in / out) are staged, run(d_b, d_x, stream) is the driver on the copies, and x comes back.
+template <typename T, typename Run>
+int solveFromHost2(size_t countB, size_t countX, const T* b, T* x, Run&& run) {
+	SMM_TRY(ensureInit());
+	hipStream_t s = libStream();
+	DevBuf<T> db, dx;
+	SyncOnExit drain{s};
+	SMM_TRY(db.alloc(countB));
+	SMM_TRY(dx.alloc(countX));
+	if (countB) SMM_TRY(hostToDev(db, b, sizeof(T) * countB, s));
+	if (countX) SMM_TRY(hostToDev(dx, x, sizeof(T) * countX, s));
+	SMM_TRY(run(static_cast<const T*>(db), static_cast<T*>(dx), s));
+	if (countX) SMM_TRY(devToHost(x, dx, sizeof(T) * countX, s));
 	drain.armed = false;  // (the driver's read-back and devToHost have synchronised)
 	return SMM_HIP_OK;
 }

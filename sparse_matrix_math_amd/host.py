@@ -1363,6 +1363,33 @@ def bicg_dev(a, d_b, d_x, maxIterations, eps, at=None, stream=None):
     return SolverStatus(st.value), it.value, res.value
 
 
+def LSQR(a, b, x, maxIterations, eps, damp=0.0, at=None, info=None):
+    """LSQR for min ||a x - b|| with a matrix of any shape -- an addition (include/smm_hip.h states the loop).  b has a.rows elements, x
+    has a.cols, is the initial guess and receives the result; maxIterations < 0 means cols, with no other clamp.  The stop tests are
+    absolute: eps against the estimates of ||b - a x|| (reason 1) and of ||at (b - a x)|| (reason 2, how an inconsistent system ends).
+    damp > 0 damps the correction x - x0.  at=None builds a transpose for the duration of the solve, at=a.transpose() keeps one, at=a
+    asserts symmetry (square matrices only); that `at` is the transpose is trusted.  `info`, when a dict, receives iterations, reason,
+    resnorm2 and arnorm2 (the two squared estimates)."""
+    suf = a._suf
+    st, it, why, res, arn = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), _CT[suf](), _CT[suf]()
+    check(_fn("smm_hip_lsqr", suf)(a._h, _mh(at), _host(b, a.dtype, "b", a.rows), _host(x, a.dtype, "x", a.cols, True), int(maxIterations),
+                                   a.dtype.type(eps), a.dtype.type(damp), ctypes.byref(st), ctypes.byref(it), ctypes.byref(why), ctypes.byref(res),
+                                   ctypes.byref(arn)))
+    if info is not None:
+        info.update(iterations=it.value, reason=why.value, resnorm2=res.value, arnorm2=arn.value)
+    return SolverStatus(st.value)
+
+
+def lsqr_dev(a, d_b, d_x, maxIterations, eps, damp=0.0, at=None, stream=None):
+    """device-pointer LSQR (d_b: a.rows elements, d_x: a.cols); returns (SolverStatus, iterations, reason, resnorm2, arnorm2).
+    Synchronises `stream`."""
+    suf = a._suf
+    st, it, why, res, arn = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), _CT[suf](), _CT[suf]()
+    check(_fn("smm_hip_lsqr_dev", suf)(a._h, _mh(at), _dptr(d_b), _dptr(d_x), int(maxIterations), a.dtype.type(eps), a.dtype.type(damp), _dptr(stream),
+                                       ctypes.byref(st), ctypes.byref(it), ctypes.byref(why), ctypes.byref(res), ctypes.byref(arn)))
+    return SolverStatus(st.value), it.value, why.value, res.value, arn.value
+
+
 def cg_dev(a, d_b, d_x0, d_x, maxIterations, eps, M=None, stream=None):
     """device-pointer CG; returns (SolverStatus, iterations, resnorm2).  Synchronises `stream`."""
     suf = a._suf
