@@ -259,6 +259,32 @@ extern "C" {
  * keeps its kernel -- when no size fits. */
 #define SMM_SPMV_BLOCKS 4
 
+/* For matrices with a few very long rows among ordinary ones (a dense constraint row of a KKT system, the dense row the transpose of a
+ * global regressor column is, the hub rows of a graph Laplacian).  The other families give such a row to one wavefront; this one cuts it
+ * into segments that all compute units sum at once, and a second launch adds the segment sums up.  One lane per short row.
+ * THE ARITHMETIC IS A FIXED FUNCTION OF THE ROW'S ENTRIES, split_len AND segment_len (smm_hip_csr_longrows_info) and of nothing else --
+ * not of where the row sits in values[], the grid, the device, op, dot_mode or which workgroup ends first; no floating-point atomics:
+ *   a row of at most split_len entries   d = 0; d = fma(v[k], x[p[k]], d) for k in stored order -- the reference's sum (ref:1484-1489), the
+ *                                        bits of STREAM at one lane per row;
+ *   a longer row                         is cut into segments of segment_len entries counted from the row's own first entry (the last one
+ *                                        may be shorter).  Segment: 64 chains c[l] = 0; c[l] = fma(v[j], x[p[j]], c[l]) over the segment's
+ *                                        entries j = l, l + 64, l + 128, ... in ascending order (a chain without entries stays 0); then
+ *                                        six butterfly steps o = 32, 16, 8, 4, 2, 1: c[l] = c[l] + c[l xor o] for all l at once; the
+ *                                        segment's sum is c[0].  Row: d = 0; d = d + (sum of segment i) for i ascending.
+ * fma(a, x, b) is a * x + b with two roundings in libsmm_hip.so and one in libsmm_hip_fma.so, as everywhere.  The three ops, the fused dot
+ * products with their partial-sum slots and the device-pointer contract are STREAM's.  values[] is read in place and the analysis
+ * depends on start[] only: value edits need no refresh.  Opt-in only: AUTO and smm_hip_csr_autotune never choose it.
+ * smm_hip_csr_set_kernel(m, SMM_SPMV_LONGROWS, 0 or 1) runs the analysis if none is kept and succeeds for every valid matrix (one
+ * without long rows is served too: it costs one launch, like STREAM); another lane count is SMM_HIP_ERR_INVALID and the handle keeps
+ * its kernel. */
+#define SMM_SPMV_LONGROWS 5
+#define SMM_LONGROWS_SPLIT_MIN 1
+#define SMM_LONGROWS_SPLIT_MAX 2045 /* what the row kernel's tile of one lane per row holds in both precisions */
+#define SMM_LONGROWS_SPLIT_DEFAULT 1024
+#define SMM_LONGROWS_SEGMENT_MIN 64 /* segment_len is a multiple of 64 */
+#define SMM_LONGROWS_SEGMENT_MAX 2048
+#define SMM_LONGROWS_SEGMENT_DEFAULT 1024
+
 typedef struct smm_hip_csr smm_hip_csr;         /* device-resident CSRMatrix<T> (ref:1243-1259) */
 typedef struct smm_hip_precond smm_hip_precond; /* device-resident preconditioner */
 typedef void* smm_hip_stream;                   /* hipStream_t with HIP's own meaning: NULL = the null (default) stream */
@@ -328,6 +354,17 @@ int smm_hip_csr_find_blocks(smm_hip_csr* m, int block_size, int* found);
 /* The kept analysis: block size, number of blocks (nnz / b^2) and the most entries a row may hold at that size; 0 / 0 / 0 before an
  * analysis or when the matrix did not fit.  kernel_desc prices a BLOCKS launch as nnz s + (nnz / b^2) 4 + (rows / b + 1) 4 + cols s + rows s. */
 int smm_hip_csr_blocks_info(const smm_hip_csr* m, int* block_size, long long* blocks, int* max_row_entries);
+/* The LONGROWS family's two lengths (SMM_SPMV_LONGROWS above).  A tuning and test knob, in the spirit of smm_hip_set_march_min_rows:
+ * split_len in SMM_LONGROWS_SPLIT_MIN .. SMM_LONGROWS_SPLIT_MAX, segment_len a multiple of 64 in SMM_LONGROWS_SEGMENT_MIN ..
+ * SMM_LONGROWS_SEGMENT_MAX, 0 = the default of either; anything else is SMM_HIP_ERR_INVALID and changes nothing.  A kept analysis is
+ * replaced at once (a synchronous set-up call; launches already enqueued finish with the old one); without one the lengths are kept
+ * for the analysis smm_hip_csr_set_kernel(m, SMM_SPMV_LONGROWS, ..) runs.  The kernel choice of the handle is not changed.  The lengths
+ * change the bits of the long rows (the order above), never those of the short ones. */
+int smm_hip_csr_longrows_configure(smm_hip_csr* m, int split_len, int segment_len);
+/* The kept analysis: the two lengths in force, the rows longer than split_len and the segments they are cut into (the sum of
+ * ceil(len / segment_len) over them); 0 / 0 / 0 / 0 before an analysis.  Any pointer may be NULL.  kernel_desc prices a LONGROWS SpMV as
+ * B_spmv + 2 segments s + (long_rows + 1) 8: the segment sums written once and read once, and the long-row list. */
+int smm_hip_csr_longrows_info(const smm_hip_csr* m, int* split_len, int* segment_len, int* long_rows, long long* segments);
 /* From how many rows grid-shaped matrices are served by the 2.5-D kernels (csrc/smm_spmv_march.hip): constant diagonals (default
  * 2^21) and values read (default 6 x 2^20 fp64 / 2^24 fp32) -- below, the gather / wave kernels are as fast or faster
  * (profiles/r04/march_threshold.txt).

@@ -1141,6 +1141,18 @@ public:
 		(void)device();
 		return dev ? smm_hip_csr_blocks_info(dev, blockSize, blocks, maxRowEntries) : SMM_HIP_ERR_NO_DEVICE;
 	}
+	// The LONGROWS family (SMM_SPMV_LONGROWS: rows of more than splitLen entries are cut into segments of segmentLen that the whole device
+	// sums; smm_hip.h states the order and the legal lengths).  configureLongRows sets the two lengths (0 = the default; it replaces a kept
+	// analysis) and returns the ABI status; setSpmvKernel(SMM_SPMV_LONGROWS) selects the family and runs the analysis if none is kept.
+	// longRowsInfo reports the kept analysis (0 / 0 / 0 / 0 without one); any argument may be null.
+	int configureLongRows(const int splitLen = 0, const int segmentLen = 0) const noexcept {
+		(void)device();
+		return detail::note(dev ? smm_hip_csr_longrows_configure(dev, splitLen, segmentLen) : static_cast<int>(SMM_HIP_ERR_NO_DEVICE));
+	}
+	int longRowsInfo(int* splitLen, int* segmentLen, int* longRows, long long* segments) const noexcept {
+		(void)device();
+		return dev ? smm_hip_csr_longrows_info(dev, splitLen, segmentLen, longRows, segments) : SMM_HIP_ERR_NO_DEVICE;
+	}
 	// call after editing values/positions in place through the raw accessors below
 	void invalidateDevice() noexcept {
 		refreshHost();  // (a device-side edit not yet copied back would be lost with the mirror)

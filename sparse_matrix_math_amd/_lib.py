@@ -148,6 +148,8 @@ _PLAIN = {
     "smm_hip_csr_kernel_desc": (c_int, [_P, c_char_p, c_int, POINTER(c_longlong)]),
     "smm_hip_csr_find_blocks": (c_int, [_P, c_int, POINTER(c_int)]),
     "smm_hip_csr_blocks_info": (c_int, [_P, POINTER(c_int), POINTER(c_longlong), POINTER(c_int)]),
+    "smm_hip_csr_longrows_configure": (c_int, [_P, c_int, c_int]),
+    "smm_hip_csr_longrows_info": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_longlong)]),
     "smm_hip_set_march_min_rows": (c_int, [c_longlong, c_longlong]),
     "smm_hip_set_cg_lazy_x_min_bytes": (c_int, [c_longlong]),
     "smm_hip_set_cg_fuse_p": (c_int, [c_int]),

@@ -209,6 +209,17 @@ struct smm_hip_csr {
 	int* d_blk_tiles = nullptr;  // tile table cut on block-row boundaries: {first block row, its first block}, blk_n_tiles + 1 entries
 	int blk_n_tiles = 0;
 	int blk_blocks = 0;
+	// LONGROWS family (opt-in, smm_spmv_longrows.hip): rows of more than lr_split entries are cut into segments of lr_seg entries, summed by
+	// all CUs into a per-call scratch and added up by the row kernel.  0 not analysed, 1 usable.  Every lr_* field below except the two
+	// requests is written under tileMutex BEFORE the state turns 1 (release); launches and queries read them under tileMutex.  A replaced
+	// analysis is written over the kept one under that lock, the old arrays go to the allocator's quarantine.  The analysis reads start[] only
+	std::atomic<int> lr_state{0};
+	int lr_req_split = 0, lr_req_seg = 0;  // smm_hip_csr_longrows_configure: what the next analysis uses (0 = the default), under tileMutex
+	int lr_split = 0, lr_seg = 0;          // ... what the kept one used
+	int* d_lr_rows = nullptr;              // {row, its first segment} per long row, ascending rows; lr_long + 1 entries, the last one {rows, lr_segments}
+	int* d_lr_tiles = nullptr;             // tile table {first row, start[first row]}: a long row is a tile of its own; lr_n_tiles + 1 entries
+	int lr_long = 0, lr_segments = 0, lr_n_tiles = 0;
+	int lr_cap = 0;                        // entries the row kernel's LDS stage holds (a multiple of 1024)
 	// one-launch form of the row-partitioned SpMV (smm_spmv_split.hip): the most entries any run of 256 / 128 / 64 consecutive rows (cut at
 	// multiples of that) holds -- its fixed row tiles are staged whole, so their LDS is sized from this; -1: not counted yet (under tileMutex)
 	int split_tile_max[3] = {-1, -1, -1};
@@ -449,6 +460,15 @@ template <typename T>
 int launchSpmvBlocks(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials, const int* doneFlag,
                      hipStream_t s);
 const char* blocksKernelDesc(const smm_hip_csr* m, long long* bytes);
+// LONGROWS family (smm_spmv_longrows.hip): the analysis if none is kept (on the library's stream; never refuses a valid matrix), the two
+// launches behind launchSpmv (`op` carries the flags; the analysis runs on `s` when a concurrent configure dropped it), and the row
+// kernel's name with what the family adds to *bytes (B_spmv on entry)
+int ensureLongRows(smm_hip_csr* m);
+template <typename T>
+int launchSpmvLongRows(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials, const int* doneFlag,
+                       hipStream_t s);
+const char* longRowsKernelDesc(const smm_hip_csr* m, long long* bytes);
+void preloadLongRowsUnit();
 void chooseSpmvConfig(smm_hip_csr* m);
 // The row-partitioned SpMV in ONE launch (smm_spmv_split.hip): out = op(lhs, A_loc own) (+|-) A_rem ext [/ divisor], the local half while the
 // halo is in flight, the remote half once `landed` (a device word, raised on the exchange's stream by launchSplitSignal) has reached `seq`

@@ -411,6 +411,7 @@ int cgResidentTry(const smm_hip_csr* a, const T* b, const T* x0, T* x, int maxIt
 	const int n = a->rows;
 	if (n <= 0 || maxIterations == 0) return SMM_HIP_OK;  // nothing to iterate: the general path handles the corner cases
 	if (a->family() == SMM_SPMV_BLOCKS) return notApplicable("the matrix is served by the BLOCKS family (the loop runs its kernel)");
+	if (a->family() == SMM_SPMV_LONGROWS) return notApplicable("the matrix is served by the LONGROWS family (the loop runs its kernels)");
 	const int cus = numCUs();
 	if (static_cast<long long>(n) > static_cast<long long>(cus) * 8 * RTPB) return notApplicable("the matrix has too many rows");
 	int longest = 0;

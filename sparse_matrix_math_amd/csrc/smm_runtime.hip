@@ -71,6 +71,7 @@ static int initLocked(int device) {
 		preloadCgsUnit();
 		preloadGmresUnit();
 		preloadIdrsUnit();
+		preloadLongRowsUnit();
 		{
 			// (r05: the first single-launch solve of a process paid 5-7 ms for its code object -- config 5's stand-in 20.4 ms instead of 13.6)
 			SetupTrace traceRes("init:   of which the single-launch solvers");
@@ -757,6 +758,8 @@ int smm_hip_csr_destroy(smm_hip_csr* m) {
 	devFree(m->d_blk_col);
 	devFree(m->d_blk_start);
 	devFree(m->d_blk_tiles);
+	devFree(m->d_lr_rows);
+	devFree(m->d_lr_tiles);
 	devFree(m->d_tperm);
 	devFree(m->d_pperm);
 	delete m;

@@ -1066,6 +1066,12 @@ int launchSpmv(const smm_hip_csr* m, int op, const T* lhs, const T* x, T* out, i
 		profEnd(profSlot, s);
 		return st;
 	}
+	if (family == SMM_SPMV_LONGROWS) {  // long rows cut into segments summed by the whole chip (smm_spmv_longrows.hip): two launches, its own tile table
+		const int profSlot = profBegin(s);
+		const int st = launchSpmvLongRows<T>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s);
+		profEnd(profSlot, s);
+		return st;
+	}
 	if (family == SMM_SPMV_STREAM) {
 		const int capNnz = streamCap<T>(m, L) - 3;
 		const int maxRows = useTileKernel(L) ? tileRows(L) : TPB / std::min(L, WAVE);
@@ -1171,7 +1177,8 @@ int smm_hip_csr_set_kernel(smm_hip_csr* m, int family, int lanes_per_row) {
 		setError("csr_set_kernel: null matrix");
 		return SMM_HIP_ERR_INVALID;
 	}
-	if (family != SMM_SPMV_AUTO && family != SMM_SPMV_VECTOR && family != SMM_SPMV_STREAM && family != SMM_SPMV_PATTERN && family != SMM_SPMV_BLOCKS) {
+	if (family != SMM_SPMV_AUTO && family != SMM_SPMV_VECTOR && family != SMM_SPMV_STREAM && family != SMM_SPMV_PATTERN && family != SMM_SPMV_BLOCKS &&
+	    family != SMM_SPMV_LONGROWS) {
 		setError("csr_set_kernel: unknown family %d", family);
 		return SMM_HIP_ERR_INVALID;
 	}
@@ -1193,6 +1200,17 @@ int smm_hip_csr_set_kernel(smm_hip_csr* m, int family, int lanes_per_row) {
 		}
 		SMM_TRY(ensureBlocks(m));
 		m->setKernel(SMM_SPMV_BLOCKS, 1);
+		m->kernelForced = true;
+		return SMM_HIP_OK;
+	}
+	if (family == SMM_SPMV_LONGROWS) {
+		// opt-in; every valid matrix is served (one without long rows too)
+		if (lanes_per_row != 0 && lanes_per_row != 1) {
+			setError("csr_set_kernel: the LONGROWS family runs one lane per short row: lanes_per_row must be 0 or 1");
+			return SMM_HIP_ERR_INVALID;
+		}
+		SMM_TRY(ensureLongRows(m));
+		m->setKernel(SMM_SPMV_LONGROWS, 1);
 		m->kernelForced = true;
 		return SMM_HIP_OK;
 	}
@@ -1259,6 +1277,8 @@ int smm_hip_csr_kernel_desc(const smm_hip_csr* m, char* name, int name_cap, long
 		kernel = patternKernelDesc(m, lanes, &bytes);
 	} else if (family == SMM_SPMV_BLOCKS) {
 		kernel = blocksKernelDesc(m, &bytes);
+	} else if (family == SMM_SPMV_LONGROWS) {
+		kernel = longRowsKernelDesc(m, &bytes);
 	} else if (family == SMM_SPMV_STREAM || family == SMM_SPMV_PATTERN) {
 		kernel = (lanes == 1 || lanes == 2 || lanes == 4) && useTileKernel(lanes) ? "spmvTileKernel" : "spmvStreamKernel";
 	}

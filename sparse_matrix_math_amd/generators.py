@@ -278,6 +278,36 @@ def block_expand(start, positions, b, seed=1, dtype=np.float64, diag_dominant=Fa
     return out_start.astype(np.int32), out_pos, out_val
 
 
+def with_long_rows(start, positions, cols, long_rows, long_lens, seed=1, dtype=np.float64, integer=False):
+    """The CSR pattern (start, positions) with the rows `long_rows` replaced by rows of `long_lens` entries each (at most `cols`):
+    strictly ascending random columns.  Values are uniform in [-1, 1), or with integer=True integers in [-4, 4] -- in every row, the
+    kept ones included, so that with an integer x every summation order is exact.  Returns (start, positions, values)."""
+    rng = np.random.default_rng(seed)
+    dtype = np.dtype(dtype).type
+    start = np.asarray(start, dtype=np.int64)
+    positions = np.asarray(positions, dtype=np.int32)
+    rows = len(start) - 1
+    lens = np.diff(start)
+    wanted = dict(zip((int(r) for r in long_rows), (int(n) for n in long_lens)))
+    for r, n in wanted.items():
+        if not (0 <= r < rows and 0 <= n <= cols):
+            raise ValueError(f"row {r} with {n} entries does not fit a {rows} x {cols} matrix")
+        lens[r] = n
+    out_start = np.zeros(rows + 1, dtype=np.int64)
+    np.cumsum(lens, out=out_start[1:])
+    out_pos = np.empty(out_start[-1], dtype=np.int32)
+    for r in range(rows):
+        if r in wanted:
+            out_pos[out_start[r]:out_start[r + 1]] = np.sort(rng.choice(cols, size=wanted[r], replace=False))
+        else:
+            out_pos[out_start[r]:out_start[r + 1]] = positions[start[r]:start[r + 1]]
+    if integer:
+        values = rng.integers(-4, 5, size=out_start[-1]).astype(dtype)
+    else:
+        values = rng.uniform(-1.0, 1.0, size=out_start[-1]).astype(dtype)
+    return out_start.astype(np.int32), out_pos, values
+
+
 def row_sums(start, values):
     """RHS convention of the reference's solver tests: b = row sums of A, so the exact solution is all ones
     (sumColumsPerRow, test/include/test_common.h:13-21) -- accumulated left to right in the matrix dtype."""

@@ -55,7 +55,7 @@ class SolverPreconditioner(enum.IntEnum):
 
 OP_ASSIGN, OP_ADD, OP_SUB = 0, 1, 2
 MAX_RHS = 8  # SMM_HIP_MAX_RHS: the most right-hand sides one block holds
-SPMV_AUTO, SPMV_VECTOR, SPMV_STREAM, SPMV_PATTERN, SPMV_BLOCKS = 0, 1, 2, 3, 4
+SPMV_AUTO, SPMV_VECTOR, SPMV_STREAM, SPMV_PATTERN, SPMV_BLOCKS, SPMV_LONGROWS = 0, 1, 2, 3, 4, 5
 SWEEP_AUTO, SWEEP_LEVELS, SWEEP_SYNCFREE, SWEEP_SYNCFREE_XCD = 0, 1, 2, 3
 CHEB_BOUND_GERSHGORIN, CHEB_BOUND_POWER, CHEB_BOUND_USER = 0, 1, 2  # SMM_CHEB_BOUND_*: where a Chebyshev preconditioner's bounds come from
 _MULTICOLOR_BASE = {SolverPreconditioner.MULTICOLOR_SGS: SolverPreconditioner.SYMMETRIC_GAUS_SEIDEL, SolverPreconditioner.MULTICOLOR_ILU0: SolverPreconditioner.ILU0,
@@ -546,6 +546,18 @@ class CSRMatrix:
         b, n, cap = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
         check(_lib.load().smm_hip_csr_blocks_info(self._h, ctypes.byref(b), ctypes.byref(n), ctypes.byref(cap)))
         return b.value, n.value, cap.value
+
+    def longrows_configure(self, split_len=0, segment_len=0):
+        """the LONGROWS family's two lengths (0 = the default of either; SmmHipError outside the ranges include/smm_hip.h states): rows of
+        more than split_len entries are cut into segments of segment_len.  Replaces a kept analysis at once; without one the lengths are
+        kept for the analysis set_kernel(SPMV_LONGROWS) runs."""
+        check(_lib.load().smm_hip_csr_longrows_configure(self._h, int(split_len), int(segment_len)))
+
+    def longrows_info(self):
+        """(split_len, segment_len, long rows, segments) of the kept LONGROWS analysis; (0, 0, 0, 0) without one"""
+        s, g, n, segs = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        check(_lib.load().smm_hip_csr_longrows_info(self._h, ctypes.byref(s), ctypes.byref(g), ctypes.byref(n), ctypes.byref(segs)))
+        return s.value, g.value, n.value, segs.value
 
     def kernel_desc(self):
         """(kernel name without template arguments, bytes one launch of it moves by ITS data layout) for the next SpMV of this matrix"""
