@@ -690,6 +690,74 @@ int smm_hip_csr_add_create_f64(const smm_hip_csr* a, double alpha, const smm_hip
 int smm_hip_csr_add_into_f32(smm_hip_csr* c, const smm_hip_csr* a, float alpha, const smm_hip_csr* b, float beta, smm_hip_stream stream);
 int smm_hip_csr_add_into_f64(smm_hip_csr* c, const smm_hip_csr* a, double alpha, const smm_hip_csr* b, double beta, smm_hip_stream stream);
 
+/* ---- COMPOSING and SLICING matrices on the device (csrc/smm_compose.hip); additions with no counterpart in the reference ------------------
+ * The block matrix of a table of handles, the submatrix of chosen rows and columns, the diagonal as a vector, rows and columns scaled by
+ * vectors.  Every created matrix owns its three arrays, does not depend on its operands' lifetime, holds its columns ascending strictly
+ * inside every row and is an smm_hip_csr like any other (AUTO kernel choice, PATTERN analysis on first use, edits, preconditioners,
+ * solvers, transpose, product, sum).  No floating-point atomics: the result depends on the operands alone, two calls give the same bits.
+ * Operands whose arrays steer addresses (the blocks, a submatrix's source) must hold strictly ascending columns and pass the device check
+ * of smm_hip_csr_add_* first (SMM_HIP_ERR_INVALID, never a fault; kept in the handle once passed).  The creates synchronise `stream`.
+ *
+ * block_create_*: `blocks` is a row-major p x q table of handles, p q <= 64; NULL is a zero block and one handle may fill several slots.
+ *   `coef` is NULL (all ones) or p q scalars.  Block row I is as high as its blocks, block column J as wide as its blocks; row_sizes[p] /
+ *   col_sizes[q] (either may be NULL; an entry < 0 says nothing) are needed only for a block row / column that holds nothing but NULLs.
+ *   Entry (i, j) of block (I, J) lands at (row offset of I + i, column offset of J + j): inside an output row the segments follow in
+ *   ascending block column.  Its value is coef * v rounded once; a coef of exactly 1 copies the bits (-0.0, NaN payloads); a coef of 0
+ *   keeps the entries as stored zeros -- nothing is dropped by value, as in add.  0 x n, m x 0 and entry-free blocks are legal.
+ *   SMM_HIP_ERR_INVALID, *out untouched: p, q out of range, a block of the other dtype, blocks of one block row (column) with different
+ *   heights (widths) or against row_sizes (col_sizes), a block row / column whose size cannot be derived, total rows, columns or entries
+ *   beyond 2^31 - 1.
+ * block_refresh_*: the numeric phase alone into the kept pattern of `c` (made by block_create from a p x q table), for a matrix rebuilt
+ *   every time step or Newton step: every slot must again be NULL or not as at create and have the rows, cols and entry count recorded
+ *   there, else SMM_HIP_ERR_INVALID and nothing changed.  THAT EVERY BLOCK HAS THE PATTERN OF THE BLOCK AT CREATE BEYOND THAT IS THE CALLER'S
+ *   CONTRACT, as for smm_hip_csr_convert_refresh (smm_hip_csr_transpose_refresh_* checks more); a block with other row lengths gives
+ *   wrong values in c, never a write outside it.  `coef` may differ from create's.  Asynchronous on `stream` once every handle is ready.
+ *   Afterwards `c` is in the state smm_hip_csr_values_changed_* leaves it in: what was derived from the pattern stays, what was derived
+ *   from the values follows (constant diagonals re-verified, the slots / sweep / single-launch copies).  Nothing of size nnz is kept
+ *   for it: the place of a segment is recomputed from the blocks' row pointers.
+ *   How: a count launch (one lane per output row), the scan, ONE fill launch for the whole table: a slot gets L lanes per row, L the
+ *   power of two next to a quarter of its mean row length, up to 65536 -- a lone row of 100 000 entries is copied by 32768 lanes --, and
+ *   inside a slot with short rows what a long row holds beyond 8 L entries is copied by whole wavefronts.
+ *   Cost (s = sizeof(T)): create nnz (2 s + 8) bytes plus the row pointers ((q + 2) rows 4), refresh nnz 2 s plus the row pointers.
+ *
+ * submatrix_create / _create_dev: row i of *out is row rows_idx[i] of `a` (any in-range indices in any order, repeats allowed: a gather
+ *   of rows), restricted to the columns cols_idx[0] < cols_idx[1] < ... (strictly ascending, so the output's columns ascend), renumbered
+ *   0 .. nc - 1.  Either list may be NULL: all rows / all columns (its count is then ignored).  _create takes host arrays, _create_dev
+ *   int32 device arrays.  submatrix_range_create: rows [r0, r1) and columns [c0, c1), no lists.  Values are a's, bit for bit.
+ *   SMM_HIP_ERR_INVALID, *out untouched: an index outside the matrix, a column list that does not ascend strictly (found on the device;
+ *   smm_hip_last_error() names the first offending position as rows_idx[k] / cols_idx[k]), ranges outside the matrix, more than 2^31 - 1
+ *   entries.  Cost: a.cols 4 bytes for the column map (index form), two passes over the selected rows' columns, nnz_out (2 s + 8) written
+ *   and gathered.
+ * submatrix_refresh_*: a value edit of `a` carried over by one gather pass through the kept map of one source index per output entry
+ *   (4 bytes per entry of the submatrix): nnz_out (2 s + 4) bytes, asynchronous.  `a` must have the rows, cols and entry count of the
+ *   source; that it has its pattern is the caller's contract.  Then as every value edit (see block_refresh).
+ *
+ * diagonal_dev_*: d_out[i] = a_ii for i < min(rows, cols), 0 where no diagonal entry is stored; *d_missing (int32 on the device, may be
+ *   NULL) = the number of such i.  Asynchronous.  diagonal_*: the same into host memory, synchronous; *missing may be NULL.
+ * scale_rows_cols_dev_*: v_ij <- (r_i * v_ij) * c_j in place, two roundings in this order; d_r has rows elements, d_c cols.  A NULL
+ *   vector skips its factor (one rounding; both NULL: nothing is touched).  A value edit with the rules of smm_hip_csr_set_values_dev_*.
+ *   scale_rows_cols_*: the same with the vectors in host memory, synchronous.
+ * Distributed handles are not covered. */
+int smm_hip_csr_block_create_f32(int p, int q, const smm_hip_csr* const* blocks, const float* coef, const int* row_sizes, const int* col_sizes, smm_hip_stream stream,
+                                 smm_hip_csr** out);
+int smm_hip_csr_block_create_f64(int p, int q, const smm_hip_csr* const* blocks, const double* coef, const int* row_sizes, const int* col_sizes, smm_hip_stream stream,
+                                 smm_hip_csr** out);
+int smm_hip_csr_block_refresh_f32(smm_hip_csr* c, int p, int q, const smm_hip_csr* const* blocks, const float* coef, smm_hip_stream stream);
+int smm_hip_csr_block_refresh_f64(smm_hip_csr* c, int p, int q, const smm_hip_csr* const* blocks, const double* coef, smm_hip_stream stream);
+int smm_hip_csr_submatrix_create(const smm_hip_csr* a, const int* rows_idx, size_t nr, const int* cols_idx, size_t nc, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_submatrix_create_dev(const smm_hip_csr* a, const int* d_rows_idx, size_t nr, const int* d_cols_idx, size_t nc, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_submatrix_range_create(const smm_hip_csr* a, int r0, int r1, int c0, int c1, smm_hip_stream stream, smm_hip_csr** out);
+int smm_hip_csr_submatrix_refresh_f32(smm_hip_csr* sub, const smm_hip_csr* a, smm_hip_stream stream);
+int smm_hip_csr_submatrix_refresh_f64(smm_hip_csr* sub, const smm_hip_csr* a, smm_hip_stream stream);
+int smm_hip_csr_diagonal_f32(const smm_hip_csr* a, float* out, int* missing);
+int smm_hip_csr_diagonal_f64(const smm_hip_csr* a, double* out, int* missing);
+int smm_hip_csr_diagonal_dev_f32(const smm_hip_csr* a, float* d_out, int* d_missing, smm_hip_stream stream);
+int smm_hip_csr_diagonal_dev_f64(const smm_hip_csr* a, double* d_out, int* d_missing, smm_hip_stream stream);
+int smm_hip_csr_scale_rows_cols_dev_f32(smm_hip_csr* m, const float* d_r, const float* d_c, smm_hip_stream stream);
+int smm_hip_csr_scale_rows_cols_dev_f64(smm_hip_csr* m, const double* d_r, const double* d_c, smm_hip_stream stream);
+int smm_hip_csr_scale_rows_cols_f32(smm_hip_csr* m, const float* r, const float* c);
+int smm_hip_csr_scale_rows_cols_f64(smm_hip_csr* m, const double* r, const double* c);
+
 /* ---- a matrix in the OTHER PRECISION, converted on the device (csrc/smm_convert.hip); additions with no counterpart in the reference -------
  * convert_create: *out is `a`'s matrix with values of `dtype` (SMM_DTYPE_F32 or SMM_DTYPE_F64).  It owns its three device arrays -- start[]
  *   and positions[] are copies -- and does not depend on `a`'s lifetime: an smm_hip_csr like any other (AUTO kernel choice, PATTERN analysis

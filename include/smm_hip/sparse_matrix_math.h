@@ -7,6 +7,7 @@
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
 //     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::LSQR, SMM::eigsh, SMM::lobpcg, SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
+//      SMM::blockMatrix, SMM::blockRefresh, SMM::submatrix, SMM::submatrixRefresh, SMM::diagonal, CSRMatrix::scaleRowsCols;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
 //
 // compiles against this header unchanged and runs those calls on an MI355X: same names, same argument order and meaning,
@@ -36,6 +37,7 @@
 #include <cstring>
 #include <cstdio>
 #include <fstream>
+#include <initializer_list>
 #include <limits>
 #include <map>
 #include <memory>
@@ -104,6 +106,13 @@ struct Abi<float> {
 	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f32(c, a, b, nullptr); }
 	static int addCreate(const smm_hip_csr* a, float alpha, const smm_hip_csr* b, float beta, smm_hip_csr** o) { return smm_hip_csr_add_create_f32(a, alpha, b, beta, nullptr, o); }
 	static int addInto(smm_hip_csr* c, const smm_hip_csr* a, float alpha, const smm_hip_csr* b, float beta) { return smm_hip_csr_add_into_f32(c, a, alpha, b, beta, nullptr); }
+	static int blockCreate(int p, int q, const smm_hip_csr* const* blocks, const float* coef, const int* rs, const int* cs, smm_hip_csr** o) {
+		return smm_hip_csr_block_create_f32(p, q, blocks, coef, rs, cs, nullptr, o);
+	}
+	static int blockRefresh(smm_hip_csr* c, int p, int q, const smm_hip_csr* const* blocks, const float* coef) { return smm_hip_csr_block_refresh_f32(c, p, q, blocks, coef, nullptr); }
+	static int submatrixRefresh(smm_hip_csr* s, const smm_hip_csr* a) { return smm_hip_csr_submatrix_refresh_f32(s, a, nullptr); }
+	static int diagonal(const smm_hip_csr* a, float* out, int* missing) { return smm_hip_csr_diagonal_f32(a, out, missing); }
+	static int scaleRowsCols(smm_hip_csr* m, const float* r, const float* c) { return smm_hip_csr_scale_rows_cols_f32(m, r, c); }
 	static int spmm(const smm_hip_csr* m, int op, int k, const float* l, const float* x, float* o) { return smm_hip_spmm_f32(m, op, k, l, x, o); }
 	static int bicgstabBatch(const smm_hip_csr* a, int k, float* b, float* x, int it, float eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_bicgstab_batch_f32(a, k, b, x, it, eps, M, st, nullptr, nullptr);
@@ -158,6 +167,13 @@ struct Abi<double> {
 	static int multiplyInto(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b) { return smm_hip_csr_multiply_into_f64(c, a, b, nullptr); }
 	static int addCreate(const smm_hip_csr* a, double alpha, const smm_hip_csr* b, double beta, smm_hip_csr** o) { return smm_hip_csr_add_create_f64(a, alpha, b, beta, nullptr, o); }
 	static int addInto(smm_hip_csr* c, const smm_hip_csr* a, double alpha, const smm_hip_csr* b, double beta) { return smm_hip_csr_add_into_f64(c, a, alpha, b, beta, nullptr); }
+	static int blockCreate(int p, int q, const smm_hip_csr* const* blocks, const double* coef, const int* rs, const int* cs, smm_hip_csr** o) {
+		return smm_hip_csr_block_create_f64(p, q, blocks, coef, rs, cs, nullptr, o);
+	}
+	static int blockRefresh(smm_hip_csr* c, int p, int q, const smm_hip_csr* const* blocks, const double* coef) { return smm_hip_csr_block_refresh_f64(c, p, q, blocks, coef, nullptr); }
+	static int submatrixRefresh(smm_hip_csr* s, const smm_hip_csr* a) { return smm_hip_csr_submatrix_refresh_f64(s, a, nullptr); }
+	static int diagonal(const smm_hip_csr* a, double* out, int* missing) { return smm_hip_csr_diagonal_f64(a, out, missing); }
+	static int scaleRowsCols(smm_hip_csr* m, const double* r, const double* c) { return smm_hip_csr_scale_rows_cols_f64(m, r, c); }
 	static int spmm(const smm_hip_csr* m, int op, int k, const double* l, const double* x, double* o) { return smm_hip_spmm_f64(m, op, k, l, x, o); }
 	static int bicgstabBatch(const smm_hip_csr* a, int k, double* b, double* x, int it, double eps, const smm_hip_precond* M, int* st) {
 		return smm_hip_bicgstab_batch_f64(a, k, b, x, it, eps, M, st, nullptr, nullptr);
@@ -970,6 +986,80 @@ public:
 		deviceEdited(abi);
 		return abi;
 	}
+	// additions: composing and slicing on the GPU through the device mirrors (smm_hip.h "COMPOSING and SLICING matrices").  The created
+	// matrices fill their host arrays from the device result and keep the built handle as their mirror, as initSumOf does; each returns 0,
+	// or the SMM_HIP_* status (also in lastHipStatus()) with the matrix left empty (creates) or unchanged (refreshes, scaleRowsCols).
+	// An operand without a mirror (no GPU, or left empty by a call that failed) answers the status of that failure, SMM_HIP_ERR_INVALID if none.
+	// initBlockOf: this matrix becomes the block matrix of the row-major p x q table `blocks` (nullptr: a zero block; p q <= 64; one matrix
+	// may fill several slots, none may be this one); coef nullptr or p q scalars (coef * v, one rounding; 1 copies the bits); rowSizes /
+	// colSizes nullptr, or the heights / widths for block rows / columns of nullptr alone (< 0 elsewhere).  SMM::blockMatrix is this call.
+	int initBlockOf(int p, int q, const CSRMatrix* const* blocks, const T* coef = nullptr, const int* rowSizes = nullptr, const int* colSizes = nullptr) noexcept {
+		std::vector<const smm_hip_csr*> table;
+		const int st = blockTable(p, q, blocks, table);
+		if (st != SMM_HIP_OK) return detail::note(st);
+		clearAll();
+		smm_hip_csr* d = nullptr;
+		if (detail::note(detail::Abi<T>::blockCreate(p, q, table.data(), coef, rowSizes, colSizes, &d)) != SMM_HIP_OK) return lastHipStatus();
+		return adoptBuilt(d);
+	}
+	// the numeric phase alone into the pattern initBlockOf made, from the blocks' present values (the same table: that the patterns are
+	// those of then is the caller's contract); a bulk edit on the device like operator*=.  SMM::blockRefresh is this call.
+	int blockRefresh(int p, int q, const CSRMatrix* const* blocks, const T* coef = nullptr) {
+		std::vector<const smm_hip_csr*> table;
+		const int st = blockTable(p, q, blocks, table);
+		if (st != SMM_HIP_OK) return detail::note(st);
+		(void)device();
+		if (!flushedMirror()) return detail::note(lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const int abi = detail::Abi<T>::blockRefresh(dev, p, q, table.data(), coef);
+		deviceEdited(abi);
+		return abi;
+	}
+	// initSubmatrixOf: this matrix becomes the rows rows[0 .. nr) of `a` (any order, repeats allowed; nullptr: all) restricted to the columns
+	// cols[0 .. nc) (strictly ascending; nullptr: all), renumbered; values bit for bit.  SMM::submatrix is this call.
+	int initSubmatrixOf(const CSRMatrix& a, const int* rows, size_t nr, const int* cols, size_t nc) noexcept {
+		if (&a == this) return detail::note(SMM_HIP_ERR_INVALID);
+		clearAll();
+		const smm_hip_csr* src = a.device();
+		if (!src) return detail::note(lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(smm_hip_csr_submatrix_create(src, rows, nr, cols, nc, nullptr, &d)) != SMM_HIP_OK) return lastHipStatus();
+		return adoptBuilt(d);
+	}
+	// ... the rows [r0, r1) and the columns [c0, c1) of `a`
+	int initSubmatrixOf(const CSRMatrix& a, int r0, int r1, int c0, int c1) noexcept {
+		if (&a == this) return detail::note(SMM_HIP_ERR_INVALID);
+		clearAll();
+		const smm_hip_csr* src = a.device();
+		if (!src) return detail::note(lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		smm_hip_csr* d = nullptr;
+		if (detail::note(smm_hip_csr_submatrix_range_create(src, r0, r1, c0, c1, nullptr, &d)) != SMM_HIP_OK) return lastHipStatus();
+		return adoptBuilt(d);
+	}
+	// a matrix made by initSubmatrixOf takes over the present values of `a` (its source, or a matrix with that pattern) in one gather pass on
+	// the GPU; the host values follow.  SMM::submatrixRefresh is this call.
+	int submatrixRefresh(const CSRMatrix& a) {
+		const smm_hip_csr* src = a.device();
+		(void)device();
+		if (!src || !flushedMirror()) return detail::note(lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const int abi = detail::Abi<T>::submatrixRefresh(dev, src);
+		deviceEdited(abi);
+		return abi;
+	}
+	// out[i] = a_ii for i < min(rows, cols), 0 where no diagonal entry is stored; *missing (may be null) counts those.  SMM::diagonal is this call.
+	int diagonal(T* out, int* missing = nullptr) const noexcept {
+		const smm_hip_csr* d = device();
+		if (!d) return detail::note(lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		return detail::note(detail::Abi<T>::diagonal(d, out, missing));
+	}
+	// v_ij <- (r_i v_ij) c_j on the GPU, two roundings in this order; r has getDenseRowCount() elements, c getDenseColCount(); nullptr skips
+	// the factor.  A bulk edit on the device like operator*=.
+	int scaleRowsCols(const T* r, const T* c) {
+		(void)device();
+		if (!flushedMirror()) return detail::note(lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID);
+		const int abi = detail::Abi<T>::scaleRowsCols(dev, r, c);
+		deviceEdited(abi);
+		return abi;
+	}
 	// addition: new values for a matrix made by init(plan, ...) from the same plan -- those of init(plan, valuesIn), or added to the present
 	// ones (add) -- in one device pass; the pattern and what the library derived from it stay.  Non-zero (the SMM_HIP_* status): not this
 	// plan's matrix, no GPU; nothing changed then.
@@ -1178,6 +1268,47 @@ private:
 		if (!d || detail::note(detail::Abi<T>::spmm(d, op, k, lhs, mult, out)) != SMM_HIP_OK) {
 			detail::fillNaN(out, k >= 1 && k <= SMM_HIP_MAX_RHS ? denseRowCount * k : 0);  // (a k out of range says nothing about out's size)
 		}
+	}
+	void clearAll() noexcept {
+		release();
+		values.reset();
+		positions.reset();
+		start.reset();
+		denseRowCount = denseColCount = firstActiveStart = 0;
+	}
+	// the device mirrors of a p x q table of matrices (nullptr stays nullptr); non-zero: a bad table, this matrix inside it, or a failed mirror
+	int blockTable(int p, int q, const CSRMatrix* const* blocks, std::vector<const smm_hip_csr*>& table) const noexcept {
+		if (p < 1 || q < 1 || static_cast<long long>(p) * q > 64 || !blocks) return SMM_HIP_ERR_INVALID;
+		table.assign(static_cast<size_t>(p) * q, nullptr);
+		for (int k = 0; k < p * q; ++k) {
+			if (!blocks[k]) continue;
+			if (blocks[k] == this) return SMM_HIP_ERR_INVALID;
+			table[k] = blocks[k]->device();
+			if (!table[k]) return lastHipStatus() ? lastHipStatus() : SMM_HIP_ERR_INVALID;
+		}
+		return SMM_HIP_OK;
+	}
+	// this (empty) matrix takes the built handle `d` as its mirror and fills its host arrays from it; on a failure `d` is destroyed
+	int adoptBuilt(smm_hip_csr* d) noexcept {
+		int rows = 0, cols = 0, nnz = 0;
+		int abi = smm_hip_csr_info(d, &rows, &cols, &nnz, nullptr, nullptr);
+		std::unique_ptr<T[]> v(new T[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> p(new int[nnz > 0 ? nnz : 1]);
+		std::unique_ptr<int[]> s(new int[rows + 1]());
+		if (abi == SMM_HIP_OK) abi = smm_hip_csr_get_pattern(d, s.get(), p.get());
+		if (abi == SMM_HIP_OK) abi = detail::Abi<T>::getValues(d, v.get());
+		if (detail::note(abi) != SMM_HIP_OK) {
+			smm_hip_csr_destroy(d);
+			return abi;
+		}
+		values = std::move(v);
+		positions = std::move(p);
+		start = std::move(s);
+		denseRowCount = rows;
+		denseColCount = cols;
+		computeFirstActive();
+		dev = d;
+		return 0;
 	}
 	void computeFirstActive() noexcept {  // ref:1619-1628
 		firstActiveStart = denseRowCount;
@@ -1665,6 +1796,48 @@ template <typename T>
 inline int addInto(CSRMatrix<T>& c, const CSRMatrix<T>& a, typename std::enable_if<true, T>::type alpha, const CSRMatrix<T>& b,
                    typename std::enable_if<true, T>::type beta) {
 	return c.addInto(a, alpha, b, beta);
+}
+// ---- composing and slicing (smm_hip.h "COMPOSING and SLICING matrices"); each returns 0 or the SMM_HIP_* status ----
+// out becomes the block matrix of the row-major p x q table `blocks` (CSRMatrix::initBlockOf): SMM::blockMatrix(2, 2, {&H, &Bt, &B, nullptr}, K)
+template <typename T>
+inline int blockMatrix(int p, int q, const CSRMatrix<T>* const* blocks, CSRMatrix<T>& out, const T* coef = nullptr, const int* rowSizes = nullptr,
+                       const int* colSizes = nullptr) noexcept {
+	return out.initBlockOf(p, q, blocks, coef, rowSizes, colSizes);
+}
+template <typename T>
+inline int blockMatrix(int p, int q, std::initializer_list<const CSRMatrix<T>*> blocks, CSRMatrix<T>& out, const T* coef = nullptr, const int* rowSizes = nullptr,
+                       const int* colSizes = nullptr) noexcept {
+	if (static_cast<long long>(blocks.size()) != static_cast<long long>(p) * q) return detail::note(SMM_HIP_ERR_INVALID);
+	return out.initBlockOf(p, q, blocks.begin(), coef, rowSizes, colSizes);
+}
+// the values of c (made by blockMatrix from such a table) again from the blocks' present values (CSRMatrix::blockRefresh)
+template <typename T>
+inline int blockRefresh(CSRMatrix<T>& c, int p, int q, const CSRMatrix<T>* const* blocks, const T* coef = nullptr) {
+	return c.blockRefresh(p, q, blocks, coef);
+}
+template <typename T>
+inline int blockRefresh(CSRMatrix<T>& c, int p, int q, std::initializer_list<const CSRMatrix<T>*> blocks, const T* coef = nullptr) {
+	if (static_cast<long long>(blocks.size()) != static_cast<long long>(p) * q) return detail::note(SMM_HIP_ERR_INVALID);
+	return c.blockRefresh(p, q, blocks.begin(), coef);
+}
+// out becomes the rows rows[0 .. nr) of a restricted to the ascending columns cols[0 .. nc) (nullptr: all), or the ranges [r0, r1) x [c0, c1)
+template <typename T>
+inline int submatrix(const CSRMatrix<T>& a, const int* rows, size_t nr, const int* cols, size_t nc, CSRMatrix<T>& out) noexcept {
+	return out.initSubmatrixOf(a, rows, nr, cols, nc);
+}
+template <typename T>
+inline int submatrix(const CSRMatrix<T>& a, int r0, int r1, int c0, int c1, CSRMatrix<T>& out) noexcept {
+	return out.initSubmatrixOf(a, r0, r1, c0, c1);
+}
+// the values of s (made by submatrix from a) again from a's present values (CSRMatrix::submatrixRefresh)
+template <typename T>
+inline int submatrixRefresh(CSRMatrix<T>& s, const CSRMatrix<T>& a) {
+	return s.submatrixRefresh(a);
+}
+// out[i] = a_ii, 0 where none is stored; *missing (may be null) counts those (CSRMatrix::diagonal)
+template <typename T>
+inline int diagonal(const CSRMatrix<T>& a, T* out, int* missing = nullptr) noexcept {
+	return a.diagonal(out, missing);
 }
 // BiCGSymmetric's text (ref:2021-2102) with the shadow sequence on `at`, the transpose of `a` (SMM::transpose): for matrices that are not
 // symmetric.  That `at` is the transpose is the caller's contract; `a` itself as `at` asserts symmetry and gives BiCGSymmetric's bits.

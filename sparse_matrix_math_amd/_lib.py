@@ -123,6 +123,13 @@ _TYPED = {
     "smm_hip_csr_multiply_into": (c_int, [_P, _P, _P, _P]),
     "smm_hip_csr_add_create": (c_int, [_P, "T", _P, "T", _P, POINTER(_P)]),
     "smm_hip_csr_add_into": (c_int, [_P, _P, "T", _P, "T", _P]),
+    "smm_hip_csr_block_create": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, POINTER(_P)]),
+    "smm_hip_csr_block_refresh": (c_int, [_P, c_int, c_int, _P, _P, _P]),
+    "smm_hip_csr_submatrix_refresh": (c_int, [_P, _P, _P]),
+    "smm_hip_csr_diagonal": (c_int, [_P, _P, POINTER(c_int)]),
+    "smm_hip_csr_diagonal_dev": (c_int, [_P, _P, _P, _P]),
+    "smm_hip_csr_scale_rows_cols_dev": (c_int, [_P, _P, _P, _P]),
+    "smm_hip_csr_scale_rows_cols": (c_int, [_P, _P, _P]),
 }
 
 
@@ -168,6 +175,9 @@ _PLAIN = {
     "smm_hip_csr_rcm_dev": (c_int, [_P, _P, c_size_t, c_int, _P, POINTER(c_int), POINTER(c_int), POINTER(c_longlong), POINTER(c_longlong)]),
     "smm_hip_csr_bandwidth": (c_int, [_P, POINTER(c_longlong), POINTER(c_longlong)]),
     "smm_hip_csr_multiply_create": (c_int, [_P, _P, _P, POINTER(_P)]),
+    "smm_hip_csr_submatrix_create": (c_int, [_P, _P, c_size_t, _P, c_size_t, _P, POINTER(_P)]),
+    "smm_hip_csr_submatrix_create_dev": (c_int, [_P, _P, c_size_t, _P, c_size_t, _P, POINTER(_P)]),
+    "smm_hip_csr_submatrix_range_create": (c_int, [_P, c_int, c_int, c_int, c_int, _P, POINTER(_P)]),
     "smm_hip_csr_convert_create": (c_int, [_P, c_int, _P, POINTER(_P)]),
     "smm_hip_csr_convert_refresh": (c_int, [_P, _P, _P]),
     "smm_hip_refine_f64": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, c_float, c_int, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),

@@ -279,8 +279,9 @@ int enqueueBlockRows(const smm_hip_csr* m, DevBuf<int>& ranges, hipStream_t s) {
 
 // What the host can tell without the device, then the check of every operand not yet known to be good; the word is read before the caller
 // queues anything else.  ops[k] may repeat a handle (a == b, c == a): it is checked once, under its first name.
-int checkOperands(const char* what, const smm_hip_csr* const* ops, int count, int* d_words, hipStream_t s) {
-	static const char* const NAMES[3] = {"a", "b", "c"};
+int checkOperands(const char* what, const smm_hip_csr* const* ops, int count, int* d_words, hipStream_t s, const char* const* names = nullptr) {
+	static const char* const ABC[3] = {"a", "b", "c"};
+	const char* const* NAMES = names ? names : ABC;
 	bool queued = false;
 	for (int k = 0; k < count; ++k) {
 		const smm_hip_csr* m = ops[k];
@@ -462,6 +463,15 @@ int addCreate(const smm_hip_csr* a, T alpha, const smm_hip_csr* b, T beta, smm_h
 }
 
 }  // namespace
+
+int csrCheckSorted(const char* what, const char* name, const smm_hip_csr* m, hipStream_t s) {
+	if (m->sorted_ok.load(std::memory_order_acquire) == 1) return SMM_HIP_OK;
+	DevBuf<int> d_words;
+	SMM_TRY(d_words.alloc(N_WORDS));
+	wordsInitKernel<<<1, 64, 0, s>>>(d_words.p);
+	return checkOperands(what, &m, 1, d_words, s, &name);
+}
+
 }  // namespace smm
 
 using namespace smm;

@@ -239,6 +239,12 @@ struct smm_hip_csr {
 	// row permutation (rows entries, owned: new row i is the source's row d_pperm[i]) and permuteOf the uid of the source (0: not a permutation)
 	int* d_pperm = nullptr;
 	unsigned long long permuteOf = 0;
+	// made by smm_hip_csr_submatrix_* (smm_compose.hip): d_tperm is the entry map in the same sense (output entry k is the source's entry
+	// d_tperm[k]); the shape and the entry count of the source are what smm_hip_csr_submatrix_refresh_* checks (subSrcNnz < 0: not a submatrix)
+	int subSrcRows = 0, subSrcCols = 0, subSrcNnz = -1;
+	// made by smm_hip_csr_block_create_* (smm_compose.hip): {p, q} and {rows, cols, nnz} of every slot, row-major, rows = -1 for a NULL
+	// slot -- what smm_hip_csr_block_refresh_* checks; empty: not a block matrix.  Nothing of size nnz is kept.
+	std::vector<int> blockSlots;
 	// whether values[] holds finite numbers only: -1 not known, 1 yes, 0 an Inf or a NaN.  Found by one pass over values[] the first time a
 	// Krylov driver starts from x0 = 0 (zeroStart, smm_solver_host.h); back to -1 at every value edit (valuesEdited, smm_csr_update.hip)
 	mutable std::atomic<int> values_finite{-1};
@@ -370,6 +376,9 @@ int csrValuesEdited(smm_hip_csr* m, hipStream_t s);
 unsigned long long csrUid(const smm_hip_csr* m);
 int csrPatternVerdict(const smm_hip_csr* a, unsigned long long uid);
 void csrPatternRecord(const smm_hip_csr* a, unsigned long long uid, bool same);
+// the operand check of the sparse sum (smm_add.hip) for one matrix called `name` in the error text: start[] ascends from 0 to nnz, columns
+// lie in [0, cols) and ascend strictly inside a row.  Kept in the handle once passed; synchronises `s` the first time.  `m` is ready.
+int csrCheckSorted(const char* what, const char* name, const smm_hip_csr* m, hipStream_t s);
 // Aᵀ as a handle of its own (smm_transpose.hip); may synchronise `s`
 int csrTransposeCreate(const smm_hip_csr* a, hipStream_t s, smm_hip_csr** out);
 // `a` with values of `dtype` as a handle of its own (smm_convert.hip); synchronises `s`

@@ -796,6 +796,73 @@ class CSRMatrix:
         check(_fn("smm_hip_csr_add_into", self._suf)(self._h, A._h, float(alpha), B._h, float(beta), _dptr(stream)))
         self._edited(stream)
 
+    # ---- composing and slicing on the device (smm_hip.h "COMPOSING and SLICING matrices"); bmat / hstack / vstack are module functions ----
+    def block_refresh(self, blocks, coef=None, stream=None):
+        """called on a matrix made by bmat(): the numeric phase alone into the kept pattern, from the present values of `blocks` (the table
+        of bmat: same None slots, same shapes and entry counts; that the patterns are those of then is the caller's contract) -- a value
+        edit of this matrix.  SmmHipError (SMM_HIP_ERR_INVALID, nothing changed) otherwise."""
+        p, q, table, pcoef, _ = _block_table(blocks, coef, self.dtype)
+        check(_fn("smm_hip_csr_block_refresh", self._suf)(self._h, p, q, table, pcoef, _dptr(stream)))
+        self._edited(stream)
+
+    def submatrix(self, rows=None, cols=None, stream=None):
+        """the rows `rows` (any order, repeats allowed) restricted to the columns `cols` (strictly ascending) as a new CSRMatrix that owns
+        its arrays; values bit for bit.  Each of the two is None (all), a slice with step 1 (with two slices or a slice and None: the range
+        form, no index list) or an integer array.  SmmHipError (SMM_HIP_ERR_INVALID) naming the first offending position for an index
+        outside the matrix or columns that do not ascend strictly.  Synchronises `stream`."""
+        h = ctypes.c_void_p()
+        lib = _lib.load()
+        rows, cols = _index_arg(rows, self.rows, "rows"), _index_arg(cols, self.cols, "cols")
+        if isinstance(rows, tuple) and isinstance(cols, tuple):  # two ranges: no index list
+            check(lib.smm_hip_csr_submatrix_range_create(self._h, rows[0], rows[1], cols[0], cols[1], _dptr(stream), ctypes.byref(h)))
+            return CSRMatrix._adopt(h, self.dtype)
+        if isinstance(rows, tuple):  # a range beside an index list: all of them is NULL, anything else is written out
+            rows = None if rows == (0, self.rows) else np.arange(rows[0], rows[1], dtype=np.int32)
+        if isinstance(cols, tuple):
+            cols = None if cols == (0, self.cols) else np.arange(cols[0], cols[1], dtype=np.int32)
+        pr = _host(rows, np.int32, "rows") if rows is not None else ctypes.c_void_p(0)
+        pc = _host(cols, np.int32, "cols") if cols is not None else ctypes.c_void_p(0)
+        check(lib.smm_hip_csr_submatrix_create(self._h, pr, 0 if rows is None else rows.size, pc, 0 if cols is None else cols.size, _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, self.dtype)
+
+    def submatrix_dev(self, d_rows, nr, d_cols, nc, stream=None):
+        """submatrix() with the index lists in int32 device arrays of nr / nc entries (None: all rows / all columns)"""
+        h = ctypes.c_void_p()
+        check(_lib.load().smm_hip_csr_submatrix_create_dev(self._h, _dptr(d_rows), int(nr), _dptr(d_cols), int(nc), _dptr(stream), ctypes.byref(h)))
+        return CSRMatrix._adopt(h, self.dtype)
+
+    def submatrix_refresh(self, A, stream=None):
+        """called on a matrix made by submatrix(): take over the present values of A (the source, or a matrix with its pattern) in one
+        gather pass -- a value edit of this matrix.  SmmHipError (SMM_HIP_ERR_INVALID, nothing changed) for a matrix of another shape or
+        entry count."""
+        check(_fn("smm_hip_csr_submatrix_refresh", self._suf)(self._h, A._h, _dptr(stream)))
+        self._edited(stream)
+
+    def diagonal(self, return_missing=False):
+        """the diagonal as a vector of min(rows, cols) elements, 0 where no diagonal entry is stored; with return_missing also how many
+        are not stored"""
+        out = np.zeros(min(self.rows, self.cols), dtype=self.dtype)
+        missing = ctypes.c_int()
+        check(_fn("smm_hip_csr_diagonal", self._suf)(self._h, _host(out, self.dtype, "out"), ctypes.byref(missing)))
+        return (out, missing.value) if return_missing else out
+
+    def diagonal_dev(self, d_out, d_missing=None, stream=None):
+        """the same into a device array of min(rows, cols) elements; d_missing: an int32 on the device for the count, or None"""
+        check(_fn("smm_hip_csr_diagonal_dev", self._suf)(self._h, _dptr(d_out), _dptr(d_missing), _dptr(stream)))
+
+    def scale_rows_cols(self, r=None, c=None):
+        """v_ij <- (r_i v_ij) c_j in place, two roundings in this order; r has `rows` elements, c `cols`; None skips the factor"""
+        r = None if r is None else np.ascontiguousarray(r, dtype=self.dtype)
+        c = None if c is None else np.ascontiguousarray(c, dtype=self.dtype)
+        pr = _host(r, self.dtype, "r", self.rows) if r is not None else ctypes.c_void_p(0)
+        pc = _host(c, self.dtype, "c", self.cols) if c is not None else ctypes.c_void_p(0)
+        check(_fn("smm_hip_csr_scale_rows_cols", self._suf)(self._h, pr, pc))
+
+    def scale_rows_cols_dev(self, d_r=None, d_c=None, stream=None):
+        """the same with the vectors in device memory, enqueued on `stream`"""
+        check(_fn("smm_hip_csr_scale_rows_cols_dev", self._suf)(self._h, _dptr(d_r), _dptr(d_c), _dptr(stream)))
+        self._edited(stream)
+
     # ---- the other precision, converted on the device (smm_hip.h "a matrix in the OTHER PRECISION") ----
     def astype(self, dtype, stream=None):
         """this matrix with values of `dtype` (float32 / float64) as a new CSRMatrix that owns its arrays: float64 -> float32 rounds to
@@ -880,6 +947,78 @@ class CSRMatrix:
             self.close()
         except Exception:
             pass
+
+
+def _index_arg(v, n, name):
+    """None -> the range (0, n); a slice with step 1 -> the range (lo, hi); anything else -> a contiguous int32 array"""
+    if v is None:
+        return 0, n
+    if isinstance(v, slice):
+        lo, hi, step = v.indices(n)
+        if step != 1:
+            raise ValueError(f"{name}: a slice must have step 1 (pass an integer array for anything else)")
+        return lo, max(lo, hi)
+    a = np.ascontiguousarray(v, dtype=np.int32)
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be one-dimensional")
+    return a
+
+
+def _block_table(blocks, coef, dtype=None):
+    """(p, q, the row-major handle table, the coefficient array or NULL, dtype) of a rectangular nested list of CSRMatrix / None"""
+    rows = [list(r) for r in blocks]
+    p, q = len(rows), len(rows[0]) if rows else 0
+    if p < 1 or q < 1 or any(len(r) != q for r in rows):
+        raise ValueError("blocks must be a rectangular table of at least one row and one column")
+    flat = [b for r in rows for b in r]
+    for b in flat:
+        if b is not None and not isinstance(b, CSRMatrix):
+            raise TypeError("a block is a CSRMatrix or None")
+        if b is not None and dtype is None:
+            dtype = b.dtype
+    if dtype is None:
+        raise ValueError("a table of None blocks has no element type")
+    table = (ctypes.c_void_p * (p * q))(*[None if b is None else b._h for b in flat])
+    pcoef = ctypes.c_void_p(0)
+    if coef is not None:
+        coef = np.ascontiguousarray(coef, dtype=dtype).reshape(-1)
+        if coef.size != p * q:
+            raise ValueError(f"coef has {coef.size} elements, the table has {p * q} slots")
+        pcoef = _host(coef, dtype, "coef")
+    return p, q, table, pcoef, np.dtype(dtype)
+
+
+def _sizes(v, n, name):
+    if v is None:
+        return None, ctypes.c_void_p(0)
+    a = np.ascontiguousarray([-1 if x is None else x for x in v], dtype=np.int32)
+    if a.size != n:
+        raise ValueError(f"{name} has {a.size} entries, the table has {n}")
+    return a, _host(a, np.int32, name)
+
+
+def bmat(blocks, coef=None, row_sizes=None, col_sizes=None, dtype=None, stream=None):
+    """The block matrix of a rectangular nested list of CSRMatrix / None (a zero block), built on the device (smm_hip.h "COMPOSING and
+    SLICING matrices") as a new CSRMatrix that owns its arrays: bmat([[H, Bt], [B, None]]).  coef: None or one scalar per slot (the
+    entries of a slot become coef * v, one rounding; 1 copies the bits, 0 keeps stored zeros).  row_sizes / col_sizes: the heights /
+    widths, needed only for a block row / column of None alone (None entries elsewhere).  dtype: needed only for a table of None alone.
+    At most 64 slots.  Synchronises `stream`."""
+    p, q, table, pcoef, dtype = _block_table(blocks, coef, dtype)
+    keep_r, pr = _sizes(row_sizes, p, "row_sizes")
+    keep_c, pc = _sizes(col_sizes, q, "col_sizes")
+    h = ctypes.c_void_p()
+    check(_fn("smm_hip_csr_block_create", _suffix(dtype))(p, q, table, pcoef, pr, pc, _dptr(stream), ctypes.byref(h)))
+    return CSRMatrix._adopt(h, dtype)
+
+
+def hstack(blocks, coef=None, stream=None):
+    """[A, B, ...] side by side: bmat([blocks])"""
+    return bmat([list(blocks)], coef, stream=stream)
+
+
+def vstack(blocks, coef=None, stream=None):
+    """[A; B; ...] one above the other: bmat([[A], [B], ...])"""
+    return bmat([[b] for b in blocks], coef, stream=stream)
 
 
 class AssemblyPlan:
