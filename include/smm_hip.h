@@ -1188,6 +1188,80 @@ int smm_hip_eigsh_dev_f64(const smm_hip_csr* a, int k, int which, int ncv, int m
                           double* d_eigenvalues, double* d_eigenvectors, long long ldx, smm_hip_stream stream, double* residuals, int* nconv, int* restarts,
                           int* matvecs, int* solver_status);
 
+/* smm_hip_svds_*: the k LARGEST singular values of a matrix of ANY shape, with their left and right singular vectors, by thick-restart
+ * Golub-Kahan-Lanczos bidiagonalisation (Baglama and Reichel 2005, restarted with Ritz vectors) with full reorthogonalisation of both
+ * bases -- an addition, the reference has no SVD (csrc/smm_solvers_svds.hip; the definition, line by line, is
+ * tests/svds_restatement.py).  It works on A and A^T, never on A^T A: the condition number is not squared and no product is formed.
+ * `a` is rows x cols.  `at` is its transpose as a handle of its own, as in smm_hip_lsqr_*: the caller's (smm_hip_csr_transpose_create_*;
+ *   kept across calls), or NULL -- the library then builds one for the call and destroys it afterwards.  `a` itself as `at` asserts
+ *   symmetry and needs a square matrix.
+ * Parameters: k >= 1 wanted triplets; ncv with k + 2 <= ncv <= min(rows, cols, SMM_SVDS_MAX_NCV), ncv == 0 meaning
+ *   min(rows, cols, max(2k + 1, 20)); maxRestarts >= 0; tol, with tol <= 0 meaning the machine epsilon of T; a start vector v0 of cols
+ *   elements, or NULL for the hash vector of (seed, col = 0) -- smm_hip_eigsh_*'s generator; every later fresh vector takes the next col.
+ * The bases: V is cols x (ncv + 1), U is rows x ncv (leading dimensions rounded up to 64); the first l columns of each are kept Ritz
+ *   vectors, l = 0 at first.  v_0 = v0 / ||v0||.
+ *   a cycle, for j = l .. ncv-1:
+ *     w = A v_j
+ *     twice (classical Gram-Schmidt): h_i = u_i.w for all i < j from the same w; w = _smm_fma(-h_i, u_i, w), i ascending
+ *     alpha_j = sqrt(w.w);  scale = max(scale, alpha_j)
+ *     alpha_j <= eps(T) * scale: an ALPHA-BREAKDOWN at j -- u_j is not formed, nothing divides by alpha_j, the cycle ends
+ *     u_j = w / alpha_j
+ *     w = A^T u_j
+ *     twice: g_i = v_i.w for all i <= j; w = _smm_fma(-g_i, v_i, w), i ascending
+ *     beta_j = sqrt(w.w);  scale = max(scale, beta_j)
+ *     beta_j <= eps(T) * scale: a BETA-BREAKDOWN at j -- v_{j+1} is not formed, the cycle ends
+ *     v_{j+1} = w / beta_j
+ *   (scale: the largest alpha, beta or kept sigma seen so far in the solve.  All of this runs on the device without a host read.)
+ *   the projected matrix B, upper triangular: diag(sigma_kept) in the leading l x l block, the arrow s in column l (rows 0 .. l-1),
+ *     alpha_j on the rest of the diagonal, beta_j at (j, j+1).  Its entries are the recurrence's norms and the arrow; the Gram-Schmidt
+ *     products h and g serve orthogonality only.  A V_m = U_m B and A^T U_m = V_m B^T + beta_{m-1} v_m e_{m-1}^T.
+ *   the Ritz step, once per cycle, on the host in fp64 for both dtypes (one-sided Jacobi):
+ *     no breakdown: m = ncv, B = X diag(sigma) Y^T, sigma descending, rho_i = |beta_{m-1} X[m-1][i]|
+ *     beta-breakdown at j: m = j + 1, B is m x m, every rho_i = 0
+ *     alpha-breakdown at j: m = j, B^ = B[0..j-1][0..j] (j x (j + 1): column j is the coupling of v_j) = X diag(sigma) Y^^T gives j
+ *       exact triplets with right vectors in V_{j+1}; every rho_i = 0; j == 0 gives none
+ *   the k wanted triplets have converged when rho_i <= tol * sigma_0 for each (sigma_0: the largest Ritz value of the step, an estimate
+ *     of ||A||_2 from below)
+ *   the solve ends on convergence, on a breakdown that leaves at least k triplets, or when maxRestarts restarts were made:
+ *     U_k = U[:, 0..m-1] X[:, 0..k-1], V_k = V[:, 0..m-1 (m after an alpha-breakdown)] Y[:, 0..k-1] (smm_hip_multi_rotate_dev_*)
+ *   otherwise a restart: l = k + (ncv - k) / 2; both bases compressed in place; v_l = v_m; sigma_kept = those Ritz values;
+ *     s_i = beta_{m-1} X[m-1][i]
+ *   a breakdown that leaves fewer than k triplets: all of them are kept (l = their count), s = 0, and v_l = the next hash vector,
+ *     orthogonalised twice against the kept V columns and normalised; this counts as a restart.  Copies of a multiple singular value
+ *     are found this way.  A matrix of rank below k therefore ends by maxRestarts with nconv < k, or returns a singular value at
+ *     rounding level as converged; it never returns a number that is not finite.
+ * Outputs: singular_values[k], descending; U (rows x k, vector i at U + i * ldu, ldu >= rows) and V (cols x k, ldv >= cols), each may
+ *   be NULL: that factor is not formed, and with both NULL no basis is rotated at the end.  smm_hip_svds_* takes host arrays;
+ *   smm_hip_svds_dev_* takes d_v0, d_singular_values, d_U and d_V in device memory (element alignment suffices) and synchronises
+ *   `stream`.  The additive outputs are host words and may each be NULL: residuals[k] (rho_i), nconv, restarts, matvecs (SpMVs on `a`
+ *   and on `at` together: 2 (ncv + restarts * (ncv - l)) when nothing broke down), solver_status: SUCCESS if all k converged,
+ *   MAX_ITERATIONS_REACHED if not -- the triplets returned are then the best available, with their rho_i (only as many as a breakdown
+ *   left when those are fewer than k) --, DIVERGED if an alpha, a beta, a sigma or the start vector's norm is not finite (or that norm
+ *   is 0): the triplets are not written then.
+ * k == 0, rows == 0 or cols == 0: SUCCESS, nothing is touched.
+ * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one call give the same bits.
+ * Memory: (ncv + 1) * cols + ncv * rows elements for the bases, plus the transpose if the library built it.
+ * WHAT THIS IS NOT: not the SMALLEST singular values -- Ritz restarts converge poorly there, harmonic restarts are not implemented --,
+ *   no shift, no block method, no implicit A^T A.  From a start vector that lies in an invariant subspace of A^T A the triplets returned
+ *   are that subspace's, as with smm_hip_eigsh_*.
+ * SMM_HIP_ERR_INVALID (the message starts with "svds:"; checked before the device is touched, the outputs are not written): a null or
+ * dtype-mismatched `a`, an `at` of the other dtype, of another shape or entry count, `a` as `at` when `a` is not square, k < 0,
+ * maxRestarts < 0, an ncv (after the default) outside k + 2 .. min(rows, cols, SMM_SVDS_MAX_NCV) -- so k > min(rows, cols) - 2 always --,
+ * null singular_values, ldu < rows with U, ldv < cols with V. */
+#define SMM_SVDS_MAX_NCV 64
+int smm_hip_svds_f32(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int maxRestarts, float tol, const float* v0, unsigned long long seed,
+                     float* singular_values, float* U, long long ldu, float* V, long long ldv, float* residuals, int* nconv, int* restarts, int* matvecs,
+                     int* solver_status);
+int smm_hip_svds_f64(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int maxRestarts, double tol, const double* v0, unsigned long long seed,
+                     double* singular_values, double* U, long long ldu, double* V, long long ldv, double* residuals, int* nconv, int* restarts, int* matvecs,
+                     int* solver_status);
+int smm_hip_svds_dev_f32(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int maxRestarts, float tol, const float* d_v0, unsigned long long seed,
+                         float* d_singular_values, float* d_U, long long ldu, float* d_V, long long ldv, smm_hip_stream stream, float* residuals, int* nconv,
+                         int* restarts, int* matvecs, int* solver_status);
+int smm_hip_svds_dev_f64(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int maxRestarts, double tol, const double* d_v0, unsigned long long seed,
+                         double* d_singular_values, double* d_U, long long ldu, double* d_V, long long ldv, smm_hip_stream stream, double* residuals, int* nconv,
+                         int* restarts, int* matvecs, int* solver_status);
+
 /* smm_hip_lobpcg_*: the k algebraically LARGEST or SMALLEST eigenvalues of a symmetric matrix, with their eigenvectors, by LOBPCG
  * (Knyazev 2001), the locally optimal block preconditioned conjugate gradient method, with the SVQB orthonormalisation of the search
  * block (Stathopoulos and Wu 2002) -- an addition, the reference has no eigensolver (csrc/smm_solvers_lobpcg.hip; the definition,

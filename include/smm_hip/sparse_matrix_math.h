@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::LSQR, SMM::eigsh, SMM::lobpcg, SMM::IDRs, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::LSQR, SMM::eigsh, SMM::svds, SMM::lobpcg, SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
 //      SMM::blockMatrix, SMM::blockRefresh, SMM::submatrix, SMM::submatrixRefresh, SMM::diagonal, CSRMatrix::scaleRowsCols;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
@@ -83,6 +83,10 @@ struct Abi<float> {
 	                 float* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
 		return smm_hip_eigsh_f32(a, k, which, ncv, restarts, tol, v0, seed, w, x, ldx, rho, nconv, nrestarts, matvecs, st);
 	}
+	static int svds(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int restarts, float tol, const float* v0, unsigned long long seed, float* sv, float* u, long long ldu,
+	                float* v, long long ldv, float* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
+		return smm_hip_svds_f32(a, at, k, ncv, restarts, tol, v0, seed, sv, u, ldu, v, ldv, rho, nconv, nrestarts, matvecs, st);
+	}
 	static int lobpcg(const smm_hip_csr* a, int k, int which, int it, float tol, const smm_hip_precond* M, const float* x0, long long ldx0, unsigned long long seed, float* w,
 	                  float* x, long long ldx, float* rn, int* nconv, int* iterations, int* matvecs, int* applies, int* st) {
 		return smm_hip_lobpcg_f32(a, k, which, it, tol, M, x0, ldx0, seed, w, x, ldx, rn, nconv, iterations, matvecs, applies, st);
@@ -143,6 +147,10 @@ struct Abi<double> {
 	static int eigsh(const smm_hip_csr* a, int k, int which, int ncv, int restarts, double tol, const double* v0, unsigned long long seed, double* w, double* x, long long ldx,
 	                 double* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
 		return smm_hip_eigsh_f64(a, k, which, ncv, restarts, tol, v0, seed, w, x, ldx, rho, nconv, nrestarts, matvecs, st);
+	}
+	static int svds(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int restarts, double tol, const double* v0, unsigned long long seed, double* sv, double* u, long long ldu,
+	                double* v, long long ldv, double* rho, int* nconv, int* nrestarts, int* matvecs, int* st) {
+		return smm_hip_svds_f64(a, at, k, ncv, restarts, tol, v0, seed, sv, u, ldu, v, ldv, rho, nconv, nrestarts, matvecs, st);
 	}
 	static int lobpcg(const smm_hip_csr* a, int k, int which, int it, double tol, const smm_hip_precond* M, const double* x0, long long ldx0, unsigned long long seed, double* w,
 	                  double* x, long long ldx, double* rn, int* nconv, int* iterations, int* matvecs, int* applies, int* st) {
@@ -1200,6 +1208,17 @@ public:
 		return AMGPreconditioner(*this, theta, maxLevels, coarseRows, smoothDegree, eigRatio);
 	}
 
+	// addition: ||A||_2, the largest singular value -- SMM::svds with k = 1 and no vectors (needs min(rows, cols) >= 3).  tol as in SMM::svds.
+	// A NaN when the solve does not report SUCCESS or the call failed (lastHipStatus() says why).
+	T norm2(T tol = T(1e-6)) const noexcept {
+		const smm_hip_csr* d = device();
+		T sigma = T(0);
+		int st = 0;
+		const int rc = d ? detail::note(detail::Abi<T>::svds(d, nullptr, 1, 0, 300, tol, nullptr, 0ull, &sigma, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, &st))
+		                 : detail::note(SMM_HIP_ERR_NO_DEVICE);
+		return rc == SMM_HIP_OK && st == 0 ? sigma : std::numeric_limits<T>::quiet_NaN();
+	}
+
 	// device mirror of the three arrays, created on first use; nullptr when there is no GPU
 	// (entries queued by updateEntry / addEntry / setValue are sent first, as one batched update)
 	const smm_hip_csr* device() const noexcept {
@@ -1660,6 +1679,31 @@ inline SolverStatus eigsh(const CSRMatrix<T>& a, int k, int which, T* eigenvalue
 	const int rc = d ? detail::Abi<T>::eigsh(d, k, which, ncv, maxRestarts, tol, v0, seed, eigenvalues, eigenvectors, static_cast<long long>(a.getDenseRowCount()),
 	                                         residuals, &o->nconv, &o->restarts, &o->matvecs, &st)
 	                 : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+
+// ---- an addition with no counterpart in the reference: the k largest singular triplets of a matrix of any shape by thick-restart
+// Golub-Kahan-Lanczos bidiagonalisation on the device (smm_hip.h states the algorithm) ----
+// singularValues[k] come out descending; U (may be null) receives left vector i at U + i * rows, V (may be null) right vector i at
+// V + i * cols.  ncv == 0 means min(rows, cols, max(2k + 1, 20)); tol <= 0 the machine epsilon of T; v0 == nullptr the hash vector of `seed`,
+// otherwise a start vector of cols elements.  `at`: the transpose (SMM::transpose) kept by the caller, null to have one built for the duration
+// of the solve, or &a to assert symmetry of a square matrix.  SUCCESS: all k converged; MAX_ITERATIONS_REACHED: the triplets are the best
+// available; DIVERGED: a value that is not finite, or the call failed (lastHipStatus() says why).  Not the smallest singular values, no shift,
+// no block method.  CSRMatrix<T>::norm2() is the k = 1 case without vectors.
+struct SvdsInfo {
+	int nconv = 0, restarts = 0, matvecs = 0;
+};
+template <typename T>
+inline SolverStatus svds(const CSRMatrix<T>& a, int k, T* singularValues, T* U = nullptr, T* V = nullptr, int ncv = 0, T tol = T(0), int maxRestarts = 300,
+                         const CSRMatrix<T>* at = nullptr, const T* v0 = nullptr, unsigned long long seed = 0, T* residuals = nullptr, SvdsInfo* info = nullptr) {
+	int st = 0;
+	SvdsInfo local;
+	SvdsInfo* o = info ? info : &local;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_csr* dt = !at ? nullptr : (at == &a ? d : at->device());
+	const int rc = d && (!at || dt) ? detail::Abi<T>::svds(d, dt, k, ncv, maxRestarts, tol, v0, seed, singularValues, U, static_cast<long long>(a.getDenseRowCount()), V,
+	                                                       static_cast<long long>(a.getDenseColCount()), residuals, &o->nconv, &o->restarts, &o->matvecs, &st)
+	                                : SMM_HIP_ERR_NO_DEVICE;
 	return detail::toStatus(rc, st);
 }
 

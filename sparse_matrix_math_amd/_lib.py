@@ -75,6 +75,10 @@ _TYPED = {
                               POINTER(c_int)]),
     "smm_hip_eigsh_dev": (c_int, [_P, c_int, c_int, c_int, c_int, "T", _P, c_ulonglong, _P, _P, c_longlong, _P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                   POINTER(c_int)]),
+    "smm_hip_svds": (c_int, [_P, _P, c_int, c_int, c_int, "T", _P, c_ulonglong, _P, _P, c_longlong, _P, c_longlong, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                             POINTER(c_int)]),
+    "smm_hip_svds_dev": (c_int, [_P, _P, c_int, c_int, c_int, "T", _P, c_ulonglong, _P, _P, c_longlong, _P, c_longlong, _P, _P, POINTER(c_int), POINTER(c_int),
+                                 POINTER(c_int), POINTER(c_int)]),
     "smm_hip_lobpcg": (c_int, [_P, c_int, c_int, c_int, "T", _P, _P, c_longlong, c_ulonglong, _P, _P, c_longlong, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                POINTER(c_int), POINTER(c_int)]),
     "smm_hip_lobpcg_dev": (c_int, [_P, c_int, c_int, c_int, "T", _P, _P, c_longlong, c_ulonglong, _P, _P, c_longlong, _P, _P, POINTER(c_int), POINTER(c_int),

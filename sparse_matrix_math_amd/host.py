@@ -665,6 +665,14 @@ class CSRMatrix:
         check(_lib.load().smm_hip_csr_transpose_create(self._h, _dptr(stream), ctypes.byref(h)))
         return CSRMatrix._adopt(h, self.dtype)
 
+    def norm2(self, tol=1e-6, at=None):
+        """||A||_2, the largest singular value: svds(self, 1)[1][0] without the vectors (needs min(rows, cols) >= 3).  tol is svds's:
+        the residual estimate relative to the value itself.  RuntimeError when the solve does not report SUCCESS."""
+        _, s, _, info = svds(self, 1, tol=tol, at=at, vectors=False)
+        if info.status != SolverStatus.SUCCESS:
+            raise RuntimeError(f"norm2: svds ended with {info.status.name} after {info.restarts} restarts")
+        return float(s[0])
+
     def transpose_refresh(self, A, stream=None):
         """called on a matrix made by transpose(): take over the present values of A (the source, or a matrix with its pattern) in one
         gather pass -- a value edit of this matrix.  SmmHipError (SMM_HIP_ERR_INVALID, nothing changed) for any other pair."""
@@ -1432,6 +1440,49 @@ def eigsh_dev(a, k, which, d_w, d_X, ldx, ncv=None, tol=0.0, max_restarts=300, d
                                         _dptr(d_w), _dptr(d_X), int(ldx), _dptr(stream), res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
                                         ctypes.byref(restarts), ctypes.byref(matvecs), ctypes.byref(st)))
     return EigshInfo(res, nconv.value, restarts.value, matvecs.value, SolverStatus(st.value))
+
+
+SVDS_MAX_NCV = 64  # SMM_SVDS_MAX_NCV
+SvdsInfo = collections.namedtuple("SvdsInfo", "residuals nconv restarts matvecs status")
+
+
+def svds(a, k=6, ncv=0, tol=0.0, max_restarts=300, v0=None, seed=0, at=None, vectors=True):
+    """The k largest singular values of the CSRMatrix `a` (any shape), with their left and right singular vectors, by thick-restart
+    Golub-Kahan-Lanczos bidiagonalisation on the device -- an addition (include/smm_hip.h states the algorithm).  It works on `a` and
+    its transpose, never on their product.  ncv: basis columns, k + 2 <= ncv <= min(rows, cols, SVDS_MAX_NCV); 0 means
+    min(rows, cols, max(2k + 1, 20)).  tol <= 0 means the machine epsilon of the dtype; the test is rho_i <= tol * sigma_0.  v0: a start
+    vector of a.cols elements, or None for the hash vector of `seed`.  at=None builds a transpose for the duration of the solve,
+    at=a.transpose() keeps one, at=a asserts symmetry (square matrices only); that `at` is the transpose is trusted.  Returns
+    (U, s, V, info): s descending, U of shape (rows, k) and V of shape (cols, k) with the vectors in their columns -- both None with
+    vectors=False --, info an SvdsInfo(residuals, nconv, restarts, matvecs, status).  When status is not SUCCESS the triplets are the best
+    available.  Not the smallest singular values, no shift, no block method."""
+    suf = a._suf
+    k = int(k)
+    s = np.zeros(max(k, 0), dtype=a.dtype)
+    res = np.zeros(max(k, 0), dtype=a.dtype)
+    U = np.zeros((max(k, 0), a.rows), dtype=a.dtype) if vectors else None  # row i: left vector i (column-major (rows, k))
+    V = np.zeros((max(k, 0), a.cols), dtype=a.dtype) if vectors else None
+    nconv, restarts, matvecs, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_fn("smm_hip_svds", suf)(a._h, _mh(at), k, int(ncv or 0), int(max_restarts), a.dtype.type(tol), None if v0 is None else _host(v0, a.dtype, "v0", a.cols),
+                                   int(seed), s.ctypes.data_as(ctypes.c_void_p), None if U is None else U.ctypes.data_as(ctypes.c_void_p), a.rows,
+                                   None if V is None else V.ctypes.data_as(ctypes.c_void_p), a.cols, res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
+                                   ctypes.byref(restarts), ctypes.byref(matvecs), ctypes.byref(st)))
+    info = SvdsInfo(res, nconv.value, restarts.value, matvecs.value, SolverStatus(st.value))
+    return (U.T, s, V.T, info) if vectors else (None, s, None, info)
+
+
+def svds_dev(a, k, d_s, d_U, ldu, d_V, ldv, ncv=0, tol=0.0, max_restarts=300, d_v0=None, seed=0, at=None, stream=None):
+    """device-pointer svds: d_s receives the k singular values, d_U (may be None) left vector i at d_U + i * ldu, d_V (may be None) right
+    vector i at d_V + i * ldv; d_v0: None or a start vector of a.cols elements on the device.  Returns an SvdsInfo (residuals: a host
+    array).  Synchronises `stream`."""
+    suf = a._suf
+    k = int(k)
+    res = np.zeros(max(k, 0), dtype=a.dtype)
+    nconv, restarts, matvecs, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_fn("smm_hip_svds_dev", suf)(a._h, _mh(at), k, int(ncv or 0), int(max_restarts), a.dtype.type(tol), _dptr(d_v0), int(seed), _dptr(d_s), _dptr(d_U), int(ldu),
+                                       _dptr(d_V), int(ldv), _dptr(stream), res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv), ctypes.byref(restarts),
+                                       ctypes.byref(matvecs), ctypes.byref(st)))
+    return SvdsInfo(res, nconv.value, restarts.value, matvecs.value, SolverStatus(st.value))
 
 
 LOBPCG_MAX_K, LOBPCG_MAX_BASIS = 8, 24  # SMM_LOBPCG_MAX_K, SMM_LOBPCG_MAX_BASIS
