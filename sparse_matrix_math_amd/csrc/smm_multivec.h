@@ -1,8 +1,12 @@
-// smm_multivec.h -- the tall-skinny kernels shared by the drivers that keep a block of columns on the device (smm_solvers_gmres.hip: the
-// Krylov basis; smm_solvers_idrs.hip: G, U and the shadow space): all products of the columns with one vector from one pass, and one
-// vector plus a combination of the columns.  Each unit that includes this instantiates its own copies.
+// smm_multivec.h -- what the five drivers that keep a block of columns on the device share (smm_solvers_gmres.hip: the Krylov basis;
+// smm_solvers_idrs.hip: G, U and the shadow space; smm_solvers_eigsh.hip and smm_solvers_svds.hip: the Lanczos bases; smm_solvers_lobpcg.hip:
+// the start block).  The tall-skinny kernels: all products of the columns with one vector from one pass (multiDot), one vector plus a
+// combination of the columns (multiAxpy), the columns times a small matrix in place (multiRotate).  And what every such basis is built
+// with: the hash column, classical Gram-Schmidt applied twice, the division by the norm and by a device scalar, the staging of
+// multiRotate's operand.  Each unit that includes this instantiates its own copies.
 #pragma once
 #include <algorithm>
+#include <vector>
 
 #include "smm_device.h"
 #include "smm_internal.h"
@@ -178,6 +182,78 @@ inline int gridMV(long long n, size_t elemBytes) {
 	return static_cast<int>(std::max<long long>(1, std::min<long long>((n + tile - 1) / tile, NPART)));
 }
 
+// w (n elements, a column of Q or a vector of its own) against the first c columns of Q, classical Gram-Schmidt applied twice, with the
+// partial sums of w . w left in parts1 (gmv of them).  Six launches: multiDot + finish + multiAxpy, twice; the products of the two passes
+// go to h1 and h2 (which may be one array), their negatives to coef.  c == 0: the last launch alone, which copies nothing and leaves w . w.
+// parts: c * NPART elements.  `flag` (may be null) guards every launch.
+template <typename T>
+inline void orthogonaliseTwice(const T* Q, long long ld, int n, int gmv, int c, T* w, T* parts, T* parts1, T* h1, T* h2, T* coef, const int* flag, hipStream_t s) {
+	if (c > 0) {
+		multiDotKernel<T><<<gmv, MV_TPB, 0, s>>>(n, c, Q, ld, w, parts, flag);
+		multiDotFinish<T><<<c, MV_TPB, 0, s>>>(parts, gmv, h1, coef, flag);
+		multiAxpyKernel<T, false><<<gmv, MV_TPB, 0, s>>>(n, c, nullptr, Q, ld, coef, w, w, nullptr, flag);
+		multiDotKernel<T><<<gmv, MV_TPB, 0, s>>>(n, c, Q, ld, w, parts, flag);
+		multiDotFinish<T><<<c, MV_TPB, 0, s>>>(parts, gmv, h2, coef, flag);
+	}
+	multiAxpyKernel<T, true><<<gmv, MV_TPB, 0, s>>>(n, c, nullptr, Q, ld, coef, w, w, parts1, flag);
+}
+
+__host__ __device__ inline unsigned long long splitmix64(unsigned long long z) {
+	z += 0x9E3779B97F4A7C15ull;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	return z ^ (z >> 31);
+}
+
+// The hash columns (IDR(s)'s shadow space, the start vectors of eigsh, svds and lobpcg): column blockIdx.y of the launch, at
+// X + blockIdx.y * ld, is column col = firstCol + blockIdx.y of the hash.  Its element `row` is ((h >> 40) + 0.5) 2^-23 - 1 with
+// h = splitmix64(splitmix64(splitmix64(seed) ^ col) ^ row): an odd multiple of 2^-24 inside (-1, 1), formed from the integer so that it
+// is exact in fp32 too.
+template <typename T>
+__global__ __launch_bounds__(MV_TPB) void hashFillKernel(long long n, unsigned long long seed, unsigned long long firstCol, T* X, long long ld) {
+	const unsigned long long hc = splitmix64(splitmix64(seed) ^ (firstCol + blockIdx.y));
+	T* col = X + static_cast<long long>(blockIdx.y) * ld;
+	for (long long i = static_cast<long long>(blockIdx.x) * MV_TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * MV_TPB) {
+		const unsigned long long h = splitmix64(hc ^ static_cast<unsigned long long>(i));
+		const int m = 2 * static_cast<int>(h >> 40) + 1 - (1 << 24);
+		col[i] = static_cast<T>(m) * T(1.0 / 16777216.0);
+	}
+}
+
+// v = v / sqrt(v . v), the nb partial sums of v . v added by every workgroup in the project's fixed order.  `bad` and `done` (each may
+// be null): a norm that is zero or not finite raises those given and divides nothing -- every workgroup comes to the same verdict.  With
+// neither there is no verdict: the division happens whatever the norm is.
+template <typename T>
+__global__ __launch_bounds__(MV_TPB) void normaliseKernel(long long n, T* v, const T* __restrict__ wwParts, int nb, int* bad, int* done) {
+	__shared__ T red[5];
+	T acc = T(0);
+	for (int i = threadIdx.x; i < nb; i += MV_TPB) acc += wwParts[i];
+	const T ww = blockSum256(acc, red);
+	if (threadIdx.x == 0) red[4] = sqrt(ww);
+	__syncthreads();
+	const T d = red[4];
+	if ((bad || done) && (!(d > T(0)) || !isfinite(d))) {
+		if (blockIdx.x == 0 && threadIdx.x == 0) {
+			if (bad) *bad = 1;
+			if (done) *done = 1;
+		}
+		return;
+	}
+	const T* const in[1] = {v};
+	T* const out[1] = {v};
+	streamMap<T, false, 1, 1>(n, in, out, [&](const T(&e)[1], T(&o)[1]) { o[0] = e[0] / d; });
+}
+
+// out = in / *divisor unless *flag (v_0 = r / beta, v_{j+1} = w / beta_j): a division, as the definitions say
+template <typename T>
+__global__ __launch_bounds__(MV_TPB) void scaleKernel(int n, const T* __restrict__ divisor, const T* in, T* out, const int* __restrict__ flag) {
+	if (*flag) return;
+	const T d = *divisor;
+	const T* const i1[1] = {in};
+	T* const o1[1] = {out};
+	streamMap<T, false, 1, 1>(n, i1, o1, [&](const T(&v)[1], T(&o)[1]) { o[0] = v[0] / d; });
+}
+
 // multiRotate: V[:, 0..l-1] = V[:, 0..m-1] Y in place (smm_solvers_eigsh.hip: a Lanczos basis compressed onto its Ritz vectors).  Rows are
 // independent: a lane loads the m values of its R rows (R consecutive rows: one load of R elements per column), forms the l outputs one
 // after the other -- j ascending, smmFma nesting, from the plain product of column 0 -- and stores each as it is formed: the lane holds its
@@ -264,6 +340,19 @@ inline void multiRotateLaunchMP(long long n, int m, int l, T* V, long long ld, c
 }
 
 inline int multiRotatePad(int m) { return m <= 16 ? 16 : m <= 32 ? 32 : MR_MAX; }
+
+// `count` columns of the host's mat (m rows, row-major with `stride` columns; column pick[c] goes to position c, column c itself with no
+// pick) as multiRotate's operand at d: multiRotatePad(m) x count, column-major, zero rows below row m, in T.  `h` is the caller's staging
+// array: it lives until the stream is next synchronised.
+template <typename T>
+inline int stageRotation(int m, int stride, int count, const std::vector<double>& mat, const int* pick, std::vector<T>& h, T* d, hipStream_t s) {
+	const int MP = multiRotatePad(m);
+	h.assign(static_cast<size_t>(MP) * count, T(0));
+	for (int c = 0; c < count; ++c) {
+		for (int r = 0; r < m; ++r) h[static_cast<size_t>(c) * MP + r] = static_cast<T>(mat[r * stride + (pick ? pick[c] : c)]);
+	}
+	return hostToDev(d, h.data(), sizeof(T) * h.size(), s);
+}
 
 // dY: multiRotatePad(m) x l, column-major, zero rows below row m.  1 <= l <= m <= MR_MAX, n > 0 (the caller checks).
 template <typename T>

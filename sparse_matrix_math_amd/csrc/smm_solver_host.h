@@ -1,6 +1,6 @@
 // smm_solver_host.h -- the host frame of the device-resident Krylov drivers (smm_solvers*.hip): the argument check, the grid of an update
-// kernel, the host's look at the loop's `done` word, the read-back that ends a loop, and the host-pointer form of a driver.  What a driver
-// launches per iteration stays written out in its own file.
+// kernel, the host's look at the loop's `done` word, the read-back that ends a loop, the report of the thick-restart drivers, and the
+// host-pointer form of a driver.  What a driver launches per iteration stays written out in its own file.
 #pragma once
 #include <algorithm>
 
@@ -144,6 +144,19 @@ inline int loopFinish(const LoopWatch& watch, void* h, const void* d, size_t byt
 	SMM_HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));
 	return SMM_HIP_OK;
+}
+
+// What a thick-restart driver (eigsh, svds) reports besides its arrays, and the hand-over to the caller's pointers (each may be null).
+struct RitzOut {
+	int status = SMM_SOLVER_SUCCESS, nconv = 0, restarts = 0, matvecs = 0;
+	int wrote = 0;  // eigenpairs or singular triplets written to the outputs
+};
+
+inline void ritzReport(const RitzOut& o, int* nconv, int* restarts, int* matvecs, int* status) {
+	if (nconv) *nconv = o.nconv;
+	if (restarts) *restarts = o.restarts;
+	if (matvecs) *matvecs = o.matvecs;
+	if (status) *status = o.status;
 }
 
 // labels of a traced wrapper's SetupTrace lines (null: not traced)

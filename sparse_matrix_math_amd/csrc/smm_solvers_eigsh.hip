@@ -10,7 +10,7 @@
 //   multiDot + finish   h2 the same again
 //   multiAxpy           ... with the partial sums of w . w in its epilogue
 //   eigshStep           one workgroup: alpha_j = h1_j + h2_j, beta_j = sqrt(w . w), the running scale, the breakdown test
-//   eigshScale          v_{j+1} = w / beta_j
+//   scaleKernel         v_{j+1} = w / beta_j
 // Eight launches and the SpMV; nothing is read by the host inside a cycle.  `done` (raised by eigshStep on a breakdown or on a value that
 // is not finite) turns the launches still queued for the cycle into no-ops.  At the end of a cycle the host reads the state once, solves
 // the small eigenproblem (cyclic Jacobi, smm_jacobi.h; fp64 results) and either ends the solve or compresses the basis (multiRotate, smm_multivec.h).
@@ -39,27 +39,9 @@ struct EigshState {
 	T alpha[MAXC], beta[MAXC];                      // of the running cycle, at the step's index
 	T h1[MAXC + 1], h2[MAXC + 1], coef[MAXC + 1];  // the two Gram-Schmidt passes' products and the coefficients (-h) of the running pass
 	T scale;                                        // the largest |alpha|, beta or kept |theta| seen so far in the solve
-	T nrm;                                          // the divisor of the next eigshScale
+	T nrm;                                          // the divisor of the next scaleKernel
 	int done, brk, bad, steps;                      // brk: the step that broke down (-1: none) ; steps: SpMVs of the running cycle
 };
-
-__host__ __device__ inline unsigned long long eigshMix(unsigned long long z) {  // the splitmix64 step
-	z += 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
-// out[row] = ((h >> 40) + 0.5) 2^-23 - 1 with h = mix(mix(mix(seed) ^ col) ^ row): the element formula of IDR(s)'s shadow space
-template <typename T>
-__global__ __launch_bounds__(TPB) void eigshHash(long long n, unsigned long long seed, unsigned long long col, T* out) {
-	const unsigned long long hc = eigshMix(eigshMix(seed) ^ col);
-	for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * TPB) {
-		const unsigned long long h = eigshMix(hc ^ static_cast<unsigned long long>(i));
-		const int m = 2 * static_cast<int>(h >> 40) + 1 - (1 << 24);
-		out[i] = static_cast<T>(m) * T(1.0 / 16777216.0);
-	}
-}
 
 // the start of a cycle: the flags, and the kept Ritz values' share of the scale
 template <typename T>
@@ -68,28 +50,6 @@ __global__ void eigshBegin(EigshState<T>* st, T thetaMax) {
 	st->brk = -1;
 	st->steps = 0;
 	if (thetaMax > st->scale) st->scale = thetaMax;
-}
-
-// v = v / sqrt(v . v) (a start vector); a norm that is zero or not finite: bad, the cycle's launches return
-template <typename T>
-__global__ __launch_bounds__(TPB) void eigshNormalise(long long n, T* v, const T* __restrict__ wwParts, int nb, EigshState<T>* st) {
-	__shared__ T red[5];
-	T acc = T(0);
-	for (int i = threadIdx.x; i < nb; i += TPB) acc += wwParts[i];
-	const T ww = blockSum256(acc, red);
-	if (threadIdx.x == 0) red[4] = sqrt(ww);
-	__syncthreads();
-	const T d = red[4];
-	if (!(d > T(0)) || !isfinite(d)) {
-		if (blockIdx.x == 0 && threadIdx.x == 0) {
-			st->bad = 1;
-			st->done = 1;
-		}
-		return;
-	}
-	const T* const in[1] = {v};
-	T* const out[1] = {v};
-	streamMap<T, false, 1, 1>(n, in, out, [&](const T(&e)[1], T(&o)[1]) { o[0] = e[0] / d; });
 }
 
 // One workgroup per Lanczos step: alpha, beta, the scale and the breakdown test.
@@ -123,28 +83,6 @@ __global__ __launch_bounds__(TPB) void eigshStep(EigshState<T>* st, const T* __r
 	st->nrm = beta;
 }
 
-// v_{j+1} = w / beta_j: a division, as the definition says
-template <typename T>
-__global__ __launch_bounds__(TPB) void eigshScale(int n, const EigshState<T>* __restrict__ st, T* w) {
-	if (st->done) return;
-	const T d = st->nrm;
-	const T* const in[1] = {w};
-	T* const out[1] = {w};
-	streamMap<T, false, 1, 1>(n, in, out, [&](const T(&e)[1], T(&o)[1]) { o[0] = e[0] / d; });
-}
-
-// `cols` columns of y (m rows, row-major with m columns; column pick[c] goes to position c) as the compression kernel's operand: MP x cols,
-// column-major, zero rows below row m, in T.  `h` is the caller's staging array: it lives until the stream is next synchronised.
-template <typename T>
-static int stageY(int m, int cols, const std::vector<double>& y, const int* pick, std::vector<T>& h, DevBuf<T>& dY, hipStream_t s) {
-	const int MP = multiRotatePad(m);
-	h.assign(static_cast<size_t>(MP) * cols, T(0));
-	for (int c = 0; c < cols; ++c) {
-		for (int r = 0; r < m; ++r) h[static_cast<size_t>(c) * MP + r] = static_cast<T>(y[r * m + pick[c]]);
-	}
-	return hostToDev(dY, h.data(), sizeof(T) * h.size(), s);
-}
-
 static int eigshResolveNcv(int rows, int k, int ncv) { return ncv == 0 ? std::min(rows, std::max(2 * k + 1, 20)) : ncv; }
 
 template <typename T>
@@ -171,14 +109,9 @@ static int eigshCheck(const smm_hip_csr* a, int k, int which, int ncv, int maxRe
 	return SMM_HIP_OK;
 }
 
-struct EigshOut {
-	int status = SMM_SOLVER_SUCCESS, nconv = 0, restarts = 0, matvecs = 0;
-	int wrote = 0;  // eigenpairs written to the outputs
-};
-
 template <typename T>
 static int eigshDev(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, T tol, const T* v0, unsigned long long seed, T* d_vals, T* d_X, long long ldx,
-                    hipStream_t s, T* residuals, EigshOut* out) {
+                    hipStream_t s, T* residuals, RitzOut* out) {
 	SMM_TRY(eigshCheck<T>(a, k, which, ncv, maxRestarts, d_vals, d_X, ldx));
 	const int n = a->rows;
 	if (n == 0 || k == 0) return SMM_HIP_OK;
@@ -201,16 +134,8 @@ static int eigshDev(const smm_hip_csr* a, int k, int which, int ncv, int maxRest
 	const int gmv = gridMV(n, sizeof(T));
 	const int g = solverGrid(n);
 	auto col = [&](int j) { return V.p + static_cast<long long>(j) * ld; };
-	// column j against the j columns before it, classical Gram-Schmidt twice, with the partial sums of its square at the end
-	auto orthogonalise = [&](int j, const int* flag) {
-		T* w = col(j);
-		multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j, V.p, ld, w, parts, flag);
-		multiDotFinish<T><<<j, TPB, 0, s>>>(parts, gmv, sp->h1, sp->coef, flag);
-		multiAxpyKernel<T, false><<<gmv, TPB, 0, s>>>(n, j, nullptr, V.p, ld, sp->coef, w, w, nullptr, flag);
-		multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j, V.p, ld, w, parts, flag);
-		multiDotFinish<T><<<j, TPB, 0, s>>>(parts, gmv, sp->h2, sp->coef, flag);
-		multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, j, nullptr, V.p, ld, sp->coef, w, w, parts1, flag);
-	};
+	// column j against the j columns before it, with the partial sums of its square at the end
+	auto orthogonalise = [&](int j, const int* flag) { orthogonaliseTwice<T>(V.p, ld, n, gmv, j, col(j), parts, parts1, sp->h1, sp->h2, sp->coef, flag, s); };
 
 	int l = 0;                  // kept Ritz vectors
 	int fresh = 0;              // hash vectors used so far
@@ -229,19 +154,18 @@ static int eigshDev(const smm_hip_csr* a, int k, int which, int ncv, int maxRest
 			if (l == 0 && v0) {
 				multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, 0, nullptr, V.p, ld, sp->coef, v0, c, parts1, nullptr);  // (no column: a copy and v0 . v0)
 			} else {
-				eigshHash<T><<<g, TPB, 0, s>>>(n, seed, static_cast<unsigned long long>(fresh), c);
+				hashFillKernel<T><<<g, TPB, 0, s>>>(n, seed, fresh, c, ld);
 				++fresh;
-				if (l == 0) multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, 0, nullptr, V.p, ld, sp->coef, c, c, parts1, nullptr);
-				else orthogonalise(l, nullptr);
+				orthogonalise(l, nullptr);
 			}
-			eigshNormalise<T><<<g, TPB, 0, s>>>(n, c, parts1, gmv, sp);
+			normaliseKernel<T><<<g, TPB, 0, s>>>(n, c, parts1, gmv, &sp->bad, &sp->done);
 			needStart = false;
 		}
 		for (int j = l; j < ncv; ++j) {
 			SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, col(j), col(j + 1), 0, nullptr, nullptr, done, s));
 			orthogonalise(j + 1, done);
 			eigshStep<T><<<1, TPB, 0, s>>>(sp, parts1, gmv, j);
-			eigshScale<T><<<g, TPB, 0, s>>>(n, sp, col(j + 1));
+			scaleKernel<T><<<g, TPB, 0, s>>>(n, &sp->nrm, col(j + 1), col(j + 1), &sp->done);
 		}
 		LoopWatch none;
 		SMM_TRY(loopFinish(none, &h, sp, sizeof(h), s));  // the one host read of the cycle
@@ -283,7 +207,7 @@ static int eigshDev(const smm_hip_csr* a, int k, int which, int ncv, int maxRest
 				rho[i] = static_cast<T>(std::fabs(last * y[(m - 1) * m + order[i]]));
 			}
 			if (d_X) {  // X = V[:, 0..m-1] Y[:, wanted]
-				SMM_TRY(stageY<T>(m, have, y, order.data(), hY, dY, s));
+				SMM_TRY(stageRotation<T>(m, m, have, y, order.data(), hY, dY, s));
 				multiRotateLaunch<T>(n, m, have, V.p, ld, dY.p, s);
 				for (int i = 0; i < have; ++i) SMM_TRY(launchCopy2<T>(n, col(i), d_X + static_cast<long long>(i) * ldx, nullptr, s));
 			}
@@ -296,7 +220,7 @@ static int eigshDev(const smm_hip_csr* a, int k, int which, int ncv, int maxRest
 		}
 		// the restart: the best lNew Ritz vectors into the first columns; after a breakdown short of k all m of them, and a fresh vector
 		const int lNew = broke ? m : k + (ncv - k) / 2;
-		SMM_TRY(stageY<T>(m, lNew, y, order.data(), hY, dY, s));
+		SMM_TRY(stageRotation<T>(m, m, lNew, y, order.data(), hY, dY, s));
 		multiRotateLaunch<T>(n, m, lNew, V.p, ld, dY.p, s);
 		if (!broke) SMM_TRY(launchCopy2<T>(n, col(m), col(lNew), nullptr, s));
 		kept.resize(lNew);
@@ -316,19 +240,11 @@ static int eigshDev(const smm_hip_csr* a, int k, int which, int ncv, int maxRest
 }
 
 template <typename T>
-static void eigshReport(const EigshOut& o, int* nconv, int* restarts, int* matvecs, int* status) {
-	if (nconv) *nconv = o.nconv;
-	if (restarts) *restarts = o.restarts;
-	if (matvecs) *matvecs = o.matvecs;
-	if (status) *status = o.status;
-}
-
-template <typename T>
 static int eigshDevEntry(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, T tol, const T* d_v0, unsigned long long seed, T* d_vals, T* d_X,
                          long long ldx, hipStream_t s, T* residuals, int* nconv, int* restarts, int* matvecs, int* status) {
-	EigshOut o;
+	RitzOut o;
 	SMM_TRY(eigshDev<T>(a, k, which, ncv, maxRestarts, tol, d_v0, seed, d_vals, d_X, ldx, s, residuals, &o));
-	eigshReport<T>(o, nconv, restarts, matvecs, status);
+	ritzReport(o, nconv, restarts, matvecs, status);
 	return SMM_HIP_OK;
 }
 
@@ -337,9 +253,9 @@ template <typename T>
 static int eigshHost(const smm_hip_csr* a, int k, int which, int ncv, int maxRestarts, T tol, const T* v0, unsigned long long seed, T* eigenvalues, T* eigenvectors,
                      long long ldx, T* residuals, int* nconv, int* restarts, int* matvecs, int* status) {
 	SMM_TRY(eigshCheck<T>(a, k, which, ncv, maxRestarts, eigenvalues, eigenvectors, ldx));
-	EigshOut o;
+	RitzOut o;
 	if (a->rows == 0 || k == 0) {
-		eigshReport<T>(o, nconv, restarts, matvecs, status);
+		ritzReport(o, nconv, restarts, matvecs, status);
 		return SMM_HIP_OK;
 	}
 	SMM_TRY(ensureInit());
@@ -360,7 +276,7 @@ static int eigshHost(const smm_hip_csr* a, int k, int which, int ncv, int maxRes
 		for (int i = 0; eigenvectors && i < o.wrote; ++i) SMM_TRY(devToHost(eigenvectors + static_cast<long long>(i) * ldx, dX.p + i * n, sizeof(T) * n, s));
 	}
 	drain.armed = false;
-	eigshReport<T>(o, nconv, restarts, matvecs, status);
+	ritzReport(o, nconv, restarts, matvecs, status);
 	return SMM_HIP_OK;
 }
 

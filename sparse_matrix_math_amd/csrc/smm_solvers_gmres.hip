@@ -9,7 +9,7 @@
 //   multiDot + finish   h2 the same again
 //   multiAxpy           ... with the partial sums of w . w in its epilogue
 //   gmresStep           one workgroup: H[.][j] = h1 + h2, H[j+1][j] = sqrt(w . w), the rotations, the tests, the counters
-//   gmresScale          v_{j+1} = w / H[j+1][j]
+//   scaleKernel         v_{j+1} = w / H[j+1][j]
 // The host never sees H.  Two device flags: cycleOver (raised by gmresStep) stops the launches that are still queued for the cycle;
 // solveOver (raised by gmresOuter after the residual was recomputed) stops everything.  The cycle-end kernels read the k that was reached
 // from device memory.  No floating-point atomics, every sum in a fixed order: two runs of one solve give the same bits.
@@ -36,16 +36,6 @@ struct GmresState {
 	T rr, beta, hn;                                 // r.r ; its root ; H[j+1][j] of the step just taken
 	int cycleOver, solveOver, k, iters, status, pad[3];
 };
-
-// out = in / *divisor (v_0 = r / beta, v_{j+1} = w / H[j+1][j]): a division, as the definition says
-template <typename T>
-__global__ __launch_bounds__(TPB) void gmresScale(int n, const T* __restrict__ divisor, const T* in, T* out, const int* __restrict__ flag) {
-	if (*flag) return;
-	const T d = *divisor;
-	const T* const i1[1] = {in};
-	T* const o1[1] = {out};
-	streamMap<T, false, 1, 1>(n, i1, o1, [&](const T(&v)[1], T(&o)[1]) { o[0] = v[0] / d; });
-}
 
 // x = x + z at the end of a cycle that reached k > 0 columns
 template <typename T>
@@ -146,7 +136,6 @@ __global__ __launch_bounds__(TPB) void gmresOuter(GmresState<T>* st, const T* __
 	st->cycleOver = 0;
 }
 
-
 template <typename T>
 static int gmresCheck(const smm_hip_csr* a, const T* b, const T* x, int restart) {
 	SMM_TRY(solverCheck<T>("gmres", a, b, x));
@@ -192,7 +181,7 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
 		SMM_TRY(launchSpmv<T>(a, SMM_OP_SUB, b, x, col(0), 0, nullptr, nullptr, first ? nullptr : solveOver, s));
 		SMM_TRY(launchDotPartials<T>(n, col(0), col(0), parts1, first ? nullptr : solveOver, s));
 		gmresOuter<T><<<1, TPB, 0, s>>>(sp, parts1, first, maxIterations, eps);
-		if (n > 0) gmresScale<T><<<solverGrid(n), TPB, 0, s>>>(n, &sp->beta, col(0), col(0), cycleOver);
+		if (n > 0) scaleKernel<T><<<solverGrid(n), TPB, 0, s>>>(n, &sp->beta, col(0), col(0), cycleOver);
 		return SMM_HIP_OK;
 	};
 	SMM_TRY(residual(1));
@@ -210,14 +199,9 @@ static int gmresDev(const smm_hip_csr* a, const T* b, T* x, int maxIterations, T
 			}
 			T* w = col(j + 1);
 			SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, z, w, 0, nullptr, nullptr, cycleOver, s));
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j + 1, V.p, ld, w, parts, cycleOver);
-			multiDotFinish<T><<<j + 1, TPB, 0, s>>>(parts, gmv, sp->h1, sp->coef, cycleOver);
-			multiAxpyKernel<T, false><<<gmv, TPB, 0, s>>>(n, j + 1, nullptr, V.p, ld, sp->coef, w, w, nullptr, cycleOver);
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j + 1, V.p, ld, w, parts, cycleOver);
-			multiDotFinish<T><<<j + 1, TPB, 0, s>>>(parts, gmv, sp->h2, sp->coef, cycleOver);
-			multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, j + 1, nullptr, V.p, ld, sp->coef, w, w, parts1, cycleOver);
+			orthogonaliseTwice<T>(V.p, ld, n, gmv, j + 1, w, parts, parts1, sp->h1, sp->h2, sp->coef, cycleOver, s);
 			gmresStep<T><<<1, TPB, 0, s>>>(sp, parts1, gmv, j, restart, maxIterations, eps);
-			if (n > 0) gmresScale<T><<<solverGrid(n), TPB, 0, s>>>(n, &sp->hn, w, w, cycleOver);
+			if (n > 0) scaleKernel<T><<<solverGrid(n), TPB, 0, s>>>(n, &sp->hn, w, w, cycleOver);
 		}
 		// the end of the cycle: y, t = sum y_i v_i, x = x + M^-1 t, the residual again
 		gmresBackSub<T><<<1, TPB, 0, s>>>(sp);

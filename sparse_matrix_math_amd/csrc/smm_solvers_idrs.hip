@@ -41,41 +41,6 @@ struct IdrsState {
 	int done, iters, status, bad;
 };
 
-__host__ __device__ inline unsigned long long splitmix64(unsigned long long z) {
-	z += 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
-// P[row + col * ld] = ((h >> 40) + 0.5) 2^-23 - 1 with h = splitmix64(splitmix64(splitmix64(seed) ^ col) ^ row): an odd multiple of 2^-24
-// inside (-1, 1), formed from the integer so that it is exact in fp32 too
-template <typename T>
-__global__ __launch_bounds__(TPB) void idrsShadowFill(long long n, unsigned long long seed, T* P, long long ld) {
-	const unsigned long long hc = splitmix64(splitmix64(seed) ^ static_cast<unsigned long long>(blockIdx.y));
-	T* col = P + static_cast<long long>(blockIdx.y) * ld;
-	for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * TPB) {
-		const unsigned long long h = splitmix64(hc ^ static_cast<unsigned long long>(i));
-		const int m = 2 * static_cast<int>(h >> 40) + 1 - (1 << 24);
-		col[i] = static_cast<T>(m) * T(1.0 / 16777216.0);
-	}
-}
-
-// v = v / sqrt(v . v), the nb partial sums of v . v added by every workgroup in the project's fixed order
-template <typename T>
-__global__ __launch_bounds__(TPB) void idrsNormalise(long long n, T* v, const T* __restrict__ wwParts, int nb) {
-	__shared__ T red[5];
-	T acc = T(0);
-	for (int i = threadIdx.x; i < nb; i += TPB) acc += wwParts[i];
-	const T ww = blockSum256(acc, red);
-	if (threadIdx.x == 0) red[4] = sqrt(ww);
-	__syncthreads();
-	const T d = red[4];
-	const T* const in[1] = {v};
-	T* const out[1] = {v};
-	streamMap<T, false, 1, 1>(n, in, out, [&](const T(&e)[1], T(&o)[1]) { o[0] = e[0] / d; });
-}
-
 // the set-up: iterations = 0, M = I, om = 1, r.r and the loop's first test
 template <typename T>
 __global__ __launch_bounds__(TPB) void idrsInit(IdrsState<T>* st, const T* __restrict__ rrParts, int maxIterations, T eps) {
@@ -343,26 +308,17 @@ __global__ __launch_bounds__(TPB) void idrsStep(IdrsState<T>* st, const T* __res
 	}
 }
 
-// P = the hash, then classical Gram-Schmidt applied twice and a scale, column by column.  parts: MAXS * NPART elements, parts1: NPART,
-// prod / neg: MAXS device scalars each.
+// P = the hash, then classical Gram-Schmidt applied twice and a division by the norm, column by column (all of it smm_multivec.h's).
+// parts: MAXS * NPART elements, parts1: NPART, prod / neg: MAXS device scalars each.
 template <typename T>
 static int shadowFill(int n, int S, unsigned long long seed, T* P, long long ld, T* parts, T* parts1, T* prod, T* neg, hipStream_t s) {
 	if (n <= 0) return SMM_HIP_OK;
 	const int gmv = gridMV(n, sizeof(T));
-	idrsShadowFill<T><<<dim3(solverGrid(n), S), TPB, 0, s>>>(n, seed, P, ld);
+	hashFillKernel<T><<<dim3(solverGrid(n), S), TPB, 0, s>>>(n, seed, 0, P, ld);
 	for (int j = 0; j < S; ++j) {
 		T* pj = P + static_cast<long long>(j) * ld;
-		if (j == 0) {
-			multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, 0, nullptr, P, ld, neg, pj, pj, parts1, nullptr);  // (no column: p.p alone)
-		} else {
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j, P, ld, pj, parts, nullptr);
-			multiDotFinish<T><<<j, TPB, 0, s>>>(parts, gmv, prod, neg, nullptr);
-			multiAxpyKernel<T, false><<<gmv, TPB, 0, s>>>(n, j, nullptr, P, ld, neg, pj, pj, nullptr, nullptr);
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j, P, ld, pj, parts, nullptr);
-			multiDotFinish<T><<<j, TPB, 0, s>>>(parts, gmv, prod, neg, nullptr);
-			multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, j, nullptr, P, ld, neg, pj, pj, parts1, nullptr);
-		}
-		idrsNormalise<T><<<solverGrid(n), TPB, 0, s>>>(n, pj, parts1, gmv);
+		orthogonaliseTwice<T>(P, ld, n, gmv, j, pj, parts, parts1, prod, prod, neg, nullptr, s);
+		normaliseKernel<T><<<solverGrid(n), TPB, 0, s>>>(n, pj, parts1, gmv, nullptr, nullptr);
 	}
 	SMM_HIP_TRY(hipGetLastError());
 	return SMM_HIP_OK;

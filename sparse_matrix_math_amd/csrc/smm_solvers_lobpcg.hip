@@ -55,25 +55,6 @@ struct LobpcgThetas {
 	T v[MAXK];
 };
 
-__host__ __device__ inline unsigned long long lobpcgMix(unsigned long long z) {  // the splitmix64 step
-	z += 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
-// X[row + col * ld] = ((h >> 40) + 0.5) 2^-23 - 1 with h = mix(mix(mix(seed) ^ col) ^ row): the element formula of IDR(s)'s shadow space
-template <typename T>
-__global__ __launch_bounds__(TPB) void lobpcgHash(long long n, unsigned long long seed, T* X, long long ld) {
-	const unsigned long long hc = lobpcgMix(lobpcgMix(seed) ^ static_cast<unsigned long long>(blockIdx.y));
-	T* col = X + static_cast<long long>(blockIdx.y) * ld;
-	for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * TPB) {
-		const unsigned long long h = lobpcgMix(hc ^ static_cast<unsigned long long>(i));
-		const int m = 2 * static_cast<int>(h >> 40) + 1 - (1 << 24);
-		col[i] = static_cast<T>(m) * T(1.0 / 16777216.0);
-	}
-}
-
 // v = v / d with d = sqrt(v . v) after the two Gram-Schmidt passes and d0 the same before them.  A d or d0 that is not finite, or
 // d <= sqrt(eps) d0 (the column lies in the span of those before it to working precision): bad, and every later launch of the start returns.
 template <typename T>
@@ -249,18 +230,11 @@ static int lobpcgDev(const smm_hip_csr* a, int k, int which, int maxIterations, 
 	LoopWatch none;
 
 	// the start block: the caller's, or the hash columns; classical Gram-Schmidt twice and a division by the norm, column by column
-	if (!X0) lobpcgHash<T><<<dim3(g, k), TPB, 0, s>>>(n, seed, S.p, ld);
+	if (!X0) hashFillKernel<T><<<dim3(g, k), TPB, 0, s>>>(n, seed, 0, S.p, ld);
 	for (int j = 0; j < k; ++j) {
 		T* xj = scol(j);
 		multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, 0, nullptr, S.p, ld, sp->coef, X0 ? X0 + j * ldx0 : xj, xj, parts0, &sp->bad);  // (no column: a copy and x . x)
-		if (j > 0) {
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j, S.p, ld, xj, parts, &sp->bad);
-			multiDotFinish<T><<<j, TPB, 0, s>>>(parts, gmv, sp->h, sp->coef, &sp->bad);
-			multiAxpyKernel<T, false><<<gmv, TPB, 0, s>>>(n, j, nullptr, S.p, ld, sp->coef, xj, xj, nullptr, &sp->bad);
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, j, S.p, ld, xj, parts, &sp->bad);
-			multiDotFinish<T><<<j, TPB, 0, s>>>(parts, gmv, sp->h, sp->coef, &sp->bad);
-			multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, j, nullptr, S.p, ld, sp->coef, xj, xj, parts1, &sp->bad);
-		}
+		if (j > 0) orthogonaliseTwice<T>(S.p, ld, n, gmv, j, xj, parts, parts1, sp->h, sp->h, sp->coef, &sp->bad, s);
 		lobpcgNormalise<T><<<g, TPB, 0, s>>>(n, xj, parts0, j > 0 ? parts1.p : parts0.p, gmv, sp);
 	}
 	LobpcgState<T> h;

@@ -11,23 +11,22 @@
 //   multiDot + finish   the same again
 //   multiAxpy           ... with the partial sums of w . w in its epilogue
 //   svdsStep            one workgroup: alpha_j (or beta_j) = sqrt(w . w), the running scale, the breakdown test
-//   svdsScale           u_j = w / alpha_j (or v_{j+1} = w / beta_j)
+//   scaleKernel         u_j = w / alpha_j (or v_{j+1} = w / beta_j)
 // Eight launches per SpMV, as in eigsh (three for u_0, which has no column before it); nothing is read by the host inside a cycle.
 // `done` (raised by svdsStep on a breakdown or on a value that is not finite) turns the launches still queued for the cycle into no-ops.
 // The entries of the projected matrix B are these norms and the restart's arrow; the Gram-Schmidt products serve orthogonality only.
-// At the end of a cycle the host reads the state once, takes the small SVD (one-sided Jacobi, below; fp64 results) and either ends the
-// solve or compresses both bases (multiRotate, smm_multivec.h).  No floating-point atomics, every sum in a fixed order: two runs of one
-// call give the same bits.
+// At the end of a cycle the host reads the state once, takes the small SVD (one-sided Jacobi, smm_jacobi.h; fp64 results) and either
+// ends the solve or compresses both bases (multiRotate, smm_multivec.h).  No floating-point atomics, every sum in a fixed order: two
+// runs of one call give the same bits.
 // NOT here: the smallest singular values (harmonic restarts), a shift, a block method, an implicit A^T A.
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <limits>
-#include <numeric>
 #include <vector>
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_jacobi.h"
 #include "smm_multivec.h"
 #include "smm_solver_host.h"
 #include "smm_solver_scal.h"
@@ -43,27 +42,9 @@ struct SvdsState {
 	T alpha[MAXC], beta[MAXC];        // of the running cycle, at the step's index
 	T h[MAXC + 1], coef[MAXC + 1];   // the running Gram-Schmidt pass: its products and the coefficients (-h)
 	T scale;                          // the largest alpha, beta or kept sigma seen so far in the solve
-	T nrm;                            // the divisor of the next svdsScale
+	T nrm;                            // the divisor of the next scaleKernel
 	int done, brk, brkBeta, bad, steps;  // brk: the step that broke down (-1: none), brkBeta: at its beta ; steps: SpMVs of the running cycle
 };
-
-__host__ __device__ inline unsigned long long svdsMix(unsigned long long z) {  // the splitmix64 step
-	z += 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
-
-// eigsh's hash vector: out[row] = ((h >> 40) + 0.5) 2^-23 - 1 with h = mix(mix(mix(seed) ^ col) ^ row)
-template <typename T>
-__global__ __launch_bounds__(TPB) void svdsHash(long long n, unsigned long long seed, unsigned long long col, T* out) {
-	const unsigned long long hc = svdsMix(svdsMix(seed) ^ col);
-	for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * TPB) {
-		const unsigned long long h = svdsMix(hc ^ static_cast<unsigned long long>(i));
-		const int m = 2 * static_cast<int>(h >> 40) + 1 - (1 << 24);
-		out[i] = static_cast<T>(m) * T(1.0 / 16777216.0);
-	}
-}
 
 // the start of a cycle: the flags, and the kept Ritz values' share of the scale
 template <typename T>
@@ -73,28 +54,6 @@ __global__ void svdsBegin(SvdsState<T>* st, T sigmaMax) {
 	st->brkBeta = 0;
 	st->steps = 0;
 	if (sigmaMax > st->scale) st->scale = sigmaMax;
-}
-
-// v = v / sqrt(v . v) (a start vector); a norm that is zero or not finite: bad, the cycle's launches return
-template <typename T>
-__global__ __launch_bounds__(TPB) void svdsNormalise(int n, T* v, const T* __restrict__ wwParts, int nb, SvdsState<T>* st) {
-	__shared__ T red[5];
-	T acc = T(0);
-	for (int i = threadIdx.x; i < nb; i += TPB) acc += wwParts[i];
-	const T ww = blockSum256(acc, red);
-	if (threadIdx.x == 0) red[4] = sqrt(ww);
-	__syncthreads();
-	const T d = red[4];
-	if (!(d > T(0)) || !isfinite(d)) {
-		if (blockIdx.x == 0 && threadIdx.x == 0) {
-			st->bad = 1;
-			st->done = 1;
-		}
-		return;
-	}
-	const T* const in[1] = {v};
-	T* const out[1] = {v};
-	streamMap<T, false, 1, 1>(n, in, out, [&](const T(&e)[1], T(&o)[1]) { o[0] = e[0] / d; });
 }
 
 // One workgroup per half step: the norm (alpha_j, or beta_j with BETA), the scale and the breakdown test.
@@ -125,123 +84,6 @@ __global__ __launch_bounds__(TPB) void svdsStep(SvdsState<T>* st, const T* __res
 		return;
 	}
 	st->nrm = nrm;
-}
-
-// w = w / nrm: a division, as the definition says
-template <typename T>
-__global__ __launch_bounds__(TPB) void svdsScale(int n, const SvdsState<T>* __restrict__ st, T* w) {
-	if (st->done) return;
-	const T d = st->nrm;
-	const T* const in[1] = {w};
-	T* const out[1] = {w};
-	streamMap<T, false, 1, 1>(n, in, out, [&](const T(&e)[1], T(&o)[1]) { o[0] = e[0] / d; });
-}
-
-// The SVD of the small matrix whose TRANSPOSE is `bt` (p x q, row-major, p >= q -- B is q x p): B = X diag(sigma) Y^T with sigma (q of
-// them) descending, X (q x q, x[r * q + i]) orthogonal and Y (p x q, y[r * q + i]) with orthonormal columns, by one-sided Jacobi
-// (Hestenes) on the columns of B^T: B^T X = Y diag(sigma).  X is the accumulated rotations: it is what rho and the arrow are read from,
-// and a restart multiplies the kept basis by it, so -- as in jacobiEigen (smm_jacobi.h) -- the rotations run in the host's long double
-// and are rounded to fp64 once.  A column of Y whose sigma is at rounding level beside sigma_0 has no direction of its own: it is
-// completed to a unit vector orthogonal to the others (any such vector is a singular vector of that sigma to rounding), so that a
-// rank-deficient B never divides by zero.  false: a value that is not finite.
-inline bool jacobiSvd(int p, int q, const std::vector<double>& bt, std::vector<double>& sigma, std::vector<double>& x, std::vector<double>& y) {
-	typedef long double R;
-	for (double e : bt) {
-		if (!std::isfinite(e)) return false;
-	}
-	std::vector<R> g(bt.begin(), bt.end()), w(static_cast<size_t>(q) * q, R(0));
-	for (int i = 0; i < q; ++i) w[i * q + i] = R(1);
-	const R tiny = R(4) * LDBL_EPSILON;
-	for (int sweep = 0; sweep < 100; ++sweep) {
-		bool rotated = false;
-		for (int a = 0; a < q; ++a) {
-			for (int b = a + 1; b < q; ++b) {
-				R aa = 0, bb = 0, ab = 0;
-				for (int r = 0; r < p; ++r) {
-					aa += g[r * q + a] * g[r * q + a];
-					bb += g[r * q + b] * g[r * q + b];
-					ab += g[r * q + a] * g[r * q + b];
-				}
-				if (ab == R(0) || std::fabs(ab) <= tiny * std::sqrt(aa * bb)) continue;
-				rotated = true;
-				const R zeta = (bb - aa) / (R(2) * ab);
-				const R tn = (zeta >= 0 ? R(1) : R(-1)) / (std::fabs(zeta) + std::sqrt(R(1) + zeta * zeta));
-				const R c = R(1) / std::sqrt(R(1) + tn * tn), s = tn * c;
-				for (int r = 0; r < p; ++r) {
-					const R ga = g[r * q + a], gb = g[r * q + b];
-					g[r * q + a] = c * ga - s * gb;
-					g[r * q + b] = s * ga + c * gb;
-				}
-				for (int r = 0; r < q; ++r) {
-					const R wa = w[r * q + a], wb = w[r * q + b];
-					w[r * q + a] = c * wa - s * wb;
-					w[r * q + b] = s * wa + c * wb;
-				}
-			}
-		}
-		if (!rotated) break;
-	}
-	std::vector<R> nrm(q);
-	for (int i = 0; i < q; ++i) {
-		R s = 0;
-		for (int r = 0; r < p; ++r) s += g[r * q + i] * g[r * q + i];
-		nrm[i] = std::sqrt(s);
-	}
-	std::vector<int> order(q);
-	std::iota(order.begin(), order.end(), 0);
-	std::stable_sort(order.begin(), order.end(), [&](int i, int j) { return nrm[i] > nrm[j]; });
-	sigma.resize(q);
-	x.assign(static_cast<size_t>(q) * q, 0.0);
-	y.assign(static_cast<size_t>(p) * q, 0.0);
-	std::vector<R> z(static_cast<size_t>(p) * q, R(0));  // Y in the wide format, column i at z[r * q + i]
-	const R cut = q > 0 ? R(DBL_EPSILON) * nrm[order[0]] : R(0);
-	for (int i = 0; i < q; ++i) {
-		const int o = order[i];
-		sigma[i] = static_cast<double>(nrm[o]);
-		if (!std::isfinite(sigma[i])) return false;
-		for (int r = 0; r < q; ++r) x[r * q + i] = static_cast<double>(w[r * q + o]);
-		if (nrm[o] > cut) {
-			for (int r = 0; r < p; ++r) z[r * q + i] = g[r * q + o] / nrm[o];
-		}
-	}
-	for (int i = 0; i < q; ++i) {  // (descending: the columns at rounding level are the last ones)
-		if (nrm[order[i]] > cut) continue;
-		std::vector<R> best(p, R(0)), t(p);
-		R bestNorm = R(-1);
-		for (int e = 0; e < p; ++e) {  // the unit vector that keeps most of itself
-			std::fill(t.begin(), t.end(), R(0));
-			t[e] = R(1);
-			for (int pass = 0; pass < 2; ++pass) {
-				for (int c = 0; c < i; ++c) {
-					R d = 0;
-					for (int r = 0; r < p; ++r) d += z[r * q + c] * t[r];
-					for (int r = 0; r < p; ++r) t[r] -= d * z[r * q + c];
-				}
-			}
-			R s = 0;
-			for (int r = 0; r < p; ++r) s += t[r] * t[r];
-			if (s > bestNorm) {
-				bestNorm = s;
-				best = t;
-			}
-		}
-		const R d = std::sqrt(bestNorm);
-		for (int r = 0; r < p; ++r) z[r * q + i] = best[r] / d;
-	}
-	for (size_t i = 0; i < z.size(); ++i) y[i] = static_cast<double>(z[i]);
-	return true;
-}
-
-// `count` leading columns of mat (m rows, row-major with `stride` columns) as the compression kernel's operand: MP x count, column-major,
-// zero rows below row m, in T.  `h` is the caller's staging array: it lives until the stream is next synchronised.
-template <typename T>
-static int svdsStage(int m, int stride, int count, const std::vector<double>& mat, std::vector<T>& h, DevBuf<T>& d, hipStream_t s) {
-	const int MP = multiRotatePad(m);
-	h.assign(static_cast<size_t>(MP) * count, T(0));
-	for (int c = 0; c < count; ++c) {
-		for (int r = 0; r < m; ++r) h[static_cast<size_t>(c) * MP + r] = static_cast<T>(mat[r * stride + c]);
-	}
-	return hostToDev(d, h.data(), sizeof(T) * h.size(), s);
 }
 
 static int svdsResolveNcv(int rows, int cols, int k, int ncv) { return ncv == 0 ? std::min(std::min(rows, cols), std::max(2 * k + 1, 20)) : ncv; }
@@ -291,11 +133,6 @@ static int svdsCheck(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv
 	return SMM_HIP_OK;
 }
 
-struct SvdsOut {
-	int status = SMM_SOLVER_SUCCESS, nconv = 0, restarts = 0, matvecs = 0;
-	int wrote = 0;  // triplets written to the outputs
-};
-
 struct SvdsCsrOwner {  // the transpose a solve built for itself
 	smm_hip_csr* m = nullptr;
 	~SvdsCsrOwner() { smm_hip_csr_destroy(m); }
@@ -303,7 +140,7 @@ struct SvdsCsrOwner {  // the transpose a solve built for itself
 
 template <typename T>
 static int svdsDev(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int maxRestarts, T tol, const T* v0, unsigned long long seed, T* d_vals, T* d_U,
-                   long long ldu, T* d_V, long long ldv, hipStream_t s, T* residuals, SvdsOut* out) {
+                   long long ldu, T* d_V, long long ldv, hipStream_t s, T* residuals, RitzOut* out) {
 	SMM_TRY(svdsCheck<T>(a, at, k, ncv, maxRestarts, d_vals, d_U, ldu, d_V, ldv));
 	const int rows = a->rows, cols = a->cols;
 	if (rows == 0 || cols == 0 || k == 0) return SMM_HIP_OK;
@@ -341,17 +178,8 @@ static int svdsDev(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, 
 	const int gV = solverGrid(cols), gU = solverGrid(rows);
 	auto vcol = [&](int j) { return V.p + static_cast<long long>(j) * ldV; };
 	auto ucol = [&](int j) { return U.p + static_cast<long long>(j) * ldU; };
-	// w (n elements, a column of Q or a vector of its own) against the first c columns of Q, classical Gram-Schmidt twice, with the partial
-	// sums of its square at the end; no column: those sums alone
 	auto orthogonalise = [&](const T* Q, long long ld, int n, int gmv, int c, T* w, const int* flag) {
-		if (c > 0) {
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, c, Q, ld, w, parts.p, flag);
-			multiDotFinish<T><<<c, TPB, 0, s>>>(parts.p, gmv, sp->h, sp->coef, flag);
-			multiAxpyKernel<T, false><<<gmv, TPB, 0, s>>>(n, c, nullptr, Q, ld, sp->coef, w, w, nullptr, flag);
-			multiDotKernel<T><<<gmv, TPB, 0, s>>>(n, c, Q, ld, w, parts.p, flag);
-			multiDotFinish<T><<<c, TPB, 0, s>>>(parts.p, gmv, sp->h, sp->coef, flag);
-		}
-		multiAxpyKernel<T, true><<<gmv, TPB, 0, s>>>(n, c, nullptr, Q, ld, sp->coef, w, w, parts1.p, flag);
+		orthogonaliseTwice<T>(Q, ld, n, gmv, c, w, parts, parts1, sp->h, sp->h, sp->coef, flag, s);
 	};
 
 	int l = 0;              // kept Ritz vectors
@@ -370,11 +198,11 @@ static int svdsDev(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, 
 			if (l == 0 && v0) {
 				multiAxpyKernel<T, true><<<gmvV, TPB, 0, s>>>(cols, 0, nullptr, V.p, ldV, sp->coef, v0, c, parts1.p, nullptr);  // (no column: a copy and v0 . v0)
 			} else {
-				svdsHash<T><<<gV, TPB, 0, s>>>(cols, seed, static_cast<unsigned long long>(fresh), c);
+				hashFillKernel<T><<<gV, TPB, 0, s>>>(cols, seed, fresh, c, ldV);
 				++fresh;
 				orthogonalise(V.p, ldV, cols, gmvV, l, c, nullptr);
 			}
-			svdsNormalise<T><<<gV, TPB, 0, s>>>(cols, c, parts1.p, gmvV, sp);
+			normaliseKernel<T><<<gV, TPB, 0, s>>>(cols, c, parts1, gmvV, &sp->bad, &sp->done);
 			needStart = false;
 		}
 		for (int j = l; j < ncv; ++j) {
@@ -382,12 +210,12 @@ static int svdsDev(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, 
 			else SMM_TRY(launchSpmv<T>(a, SMM_OP_ASSIGN, nullptr, vcol(j), ucol(j), 0, nullptr, nullptr, done, s));
 			orthogonalise(U.p, ldU, rows, gmvU, j, ucol(j), done);
 			svdsStep<T, false><<<1, TPB, 0, s>>>(sp, parts1.p, gmvU, j);
-			svdsScale<T><<<gU, TPB, 0, s>>>(rows, sp, ucol(j));
+			scaleKernel<T><<<gU, TPB, 0, s>>>(rows, &sp->nrm, ucol(j), ucol(j), &sp->done);
 			if (empty) SMM_HIP_TRY(hipMemsetAsync(vcol(j + 1), 0, sizeof(T) * cols, s));
 			else SMM_TRY(launchSpmv<T>(at, SMM_OP_ASSIGN, nullptr, ucol(j), vcol(j + 1), 0, nullptr, nullptr, done, s));
 			orthogonalise(V.p, ldV, cols, gmvV, j + 1, vcol(j + 1), done);
 			svdsStep<T, true><<<1, TPB, 0, s>>>(sp, parts1.p, gmvV, j);
-			svdsScale<T><<<gV, TPB, 0, s>>>(cols, sp, vcol(j + 1));
+			scaleKernel<T><<<gV, TPB, 0, s>>>(cols, &sp->nrm, vcol(j + 1), vcol(j + 1), &sp->done);
 		}
 		LoopWatch none;
 		SMM_TRY(loopFinish(none, &h, sp, sizeof(h), s));  // the one host read of the cycle
@@ -429,12 +257,12 @@ static int svdsDev(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, 
 				rho[i] = static_cast<T>(std::fabs(last * x[(m - 1) * m + i]));
 			}
 			if (d_U && have > 0) {  // U_k = U[:, 0..m-1] X[:, 0..k-1]
-				SMM_TRY(svdsStage<T>(m, m, have, x, hX, dX, s));
+				SMM_TRY(stageRotation<T>(m, m, have, x, nullptr, hX, dX, s));
 				multiRotateLaunch<T>(rows, m, have, U.p, ldU, dX.p, s);
 				for (int i = 0; i < have; ++i) SMM_TRY(launchCopy2<T>(rows, ucol(i), d_U + static_cast<long long>(i) * ldu, nullptr, s));
 			}
 			if (d_V && have > 0) {  // V_k = V[:, 0..mv-1] Y[:, 0..k-1]
-				SMM_TRY(svdsStage<T>(mv, m, have, y, hY, dY, s));
+				SMM_TRY(stageRotation<T>(mv, m, have, y, nullptr, hY, dY, s));
 				multiRotateLaunch<T>(cols, mv, have, V.p, ldV, dY.p, s);
 				for (int i = 0; i < have; ++i) SMM_TRY(launchCopy2<T>(cols, vcol(i), d_V + static_cast<long long>(i) * ldv, nullptr, s));
 			}
@@ -449,9 +277,9 @@ static int svdsDev(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, 
 		// fresh vector
 		const int lNew = broke ? m : k + (ncv - k) / 2;
 		if (lNew > 0) {
-			SMM_TRY(svdsStage<T>(m, m, lNew, x, hX, dX, s));
+			SMM_TRY(stageRotation<T>(m, m, lNew, x, nullptr, hX, dX, s));
 			multiRotateLaunch<T>(rows, m, lNew, U.p, ldU, dX.p, s);
-			SMM_TRY(svdsStage<T>(mv, m, lNew, y, hY, dY, s));
+			SMM_TRY(stageRotation<T>(mv, m, lNew, y, nullptr, hY, dY, s));
 			multiRotateLaunch<T>(cols, mv, lNew, V.p, ldV, dY.p, s);
 		}
 		if (!broke) SMM_TRY(launchCopy2<T>(cols, vcol(m), vcol(lNew), nullptr, s));
@@ -471,23 +299,16 @@ static int svdsDev(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, 
 	return SMM_HIP_OK;
 }
 
-static void svdsReport(const SvdsOut& o, int* nconv, int* restarts, int* matvecs, int* status) {
-	if (nconv) *nconv = o.nconv;
-	if (restarts) *restarts = o.restarts;
-	if (matvecs) *matvecs = o.matvecs;
-	if (status) *status = o.status;
-}
-
 template <typename T>
 static int svdsDevEntry(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int maxRestarts, T tol, const T* d_v0, unsigned long long seed, T* d_vals, T* d_U,
                         long long ldu, T* d_V, long long ldv, smm_hip_stream stream, T* residuals, int* nconv, int* restarts, int* matvecs, int* status) {
 	SMM_TRY(svdsCheck<T>(a, at, k, ncv, maxRestarts, d_vals, d_U, ldu, d_V, ldv));
-	SvdsOut o;
+	RitzOut o;
 	if (a->rows > 0 && a->cols > 0 && k > 0) {
 		SMM_TRY(ensureInit());
 		SMM_TRY(svdsDev<T>(a, at, k, ncv, maxRestarts, tol, d_v0, seed, d_vals, d_U, ldu, d_V, ldv, pickStream(stream), residuals, &o));
 	}
-	svdsReport(o, nconv, restarts, matvecs, status);
+	ritzReport(o, nconv, restarts, matvecs, status);
 	return SMM_HIP_OK;
 }
 
@@ -496,9 +317,9 @@ template <typename T>
 static int svdsHost(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv, int maxRestarts, T tol, const T* v0, unsigned long long seed, T* values, T* hU,
                     long long ldu, T* hV, long long ldv, T* residuals, int* nconv, int* restarts, int* matvecs, int* status) {
 	SMM_TRY(svdsCheck<T>(a, at, k, ncv, maxRestarts, values, hU, ldu, hV, ldv));
-	SvdsOut o;
+	RitzOut o;
 	if (a->rows == 0 || a->cols == 0 || k == 0) {
-		svdsReport(o, nconv, restarts, matvecs, status);
+		ritzReport(o, nconv, restarts, matvecs, status);
 		return SMM_HIP_OK;
 	}
 	SMM_TRY(ensureInit());
@@ -521,7 +342,7 @@ static int svdsHost(const smm_hip_csr* a, const smm_hip_csr* at, int k, int ncv,
 		for (int i = 0; hV && i < o.wrote; ++i) SMM_TRY(devToHost(hV + static_cast<long long>(i) * ldv, dV.p + i * cols, sizeof(T) * cols, s));
 	}
 	drain.armed = false;
-	svdsReport(o, nconv, restarts, matvecs, status);
+	ritzReport(o, nconv, restarts, matvecs, status);
 	return SMM_HIP_OK;
 }
 
