@@ -1575,6 +1575,60 @@ int smm_hip_precond_amg_level(const smm_hip_precond* M, int level, smm_hip_csr**
 int smm_hip_precond_amg_aggregates(const smm_hip_precond* M, int level, int* agg, size_t count);
 int smm_hip_precond_amg_coarse_inverse_f32(const smm_hip_precond* M, float* out, size_t count);
 int smm_hip_precond_amg_coarse_inverse_f64(const smm_hip_precond* M, double* out, size_t count);
+/* The multigrid preconditioner created with NEAR-NULL-SPACE CANDIDATES: smoothed aggregation after Vanek, Mandel and Brezina (1996), for
+ * vector-valued problems.  For linear elasticity the candidates are the rigid body modes (3 in the plane, 6 in space); with one dof per
+ * node and the constant vector it is the hierarchy above up to the scaling of T.  smm_hip_precond_create_amg is untouched by all this.
+ * The definition, line by line: tests/amg_candidates_restatement.py.
+ * B: n x k, COLUMN-MAJOR with leading dimension n, 1 <= k <= 6, in the matrix dtype (the suffix names it); read during the call only.
+ *   The _dev_ forms take it in device memory, in use on `stream` (which they synchronise).
+ * dofs_per_node: b, 1 .. 4, a divisor of n: rows b I .. b I + b - 1 are node I.  Deeper levels have k dofs per node.
+ * Per level l (block size b_l = b on level 0, k below), where it differs from SMM_PRECOND_AMG above:
+ *   node graph  b_l > 1: N = Tb^T ((A_l o A_l) Tb) by smm_hip_csr_multiply_create and smm_hip_csr_transpose_create, Tb the n x n / b_l
+ *               matrix with one 1 per row at column i / b_l, A o A the values squared (one rounding), then the square root of every
+ *               value of N: N_IJ is the Frobenius norm of block (I, J).  Strength, roots and aggregates are those above, on N with N's
+ *               diagonal; a dof takes its node's aggregate.  b_l = 1: A_l itself, as above.
+ *   T           n x n_agg k.  The member dofs of aggregate a in ascending order are the rows 0 .. m - 1 of its block V of B_l (m x k).
+ *               Thin QR by modified Gram-Schmidt.  EVERY inner product x . y: lane t of 64 sums the rows t, t + 64, ... in ascending
+ *               order from +0.0 with _smm_fma, then the xor butterfly (32, 16, ... 1) of the dot kernels: a function of m alone, the
+ *               same bits in every run.  Column by column, c ascending: norm0 = sqrt(v_c . v_c) as given; for j < c ascending
+ *               r_jc = q_j . v_c and, where column j was kept, v_c = _smm_fma(-r_jc, q_j, v_c); nrm = sqrt(v_c . v_c); the column is
+ *               KEPT iff nrm > SMM_AMG_DROP_TOL * norm0 (one product in T): r_cc = nrm, q_c = v_c / nrm.  Otherwise it is DROPPED:
+ *               q_c = 0, r_cc = 0 and row c of R is zero.  An aggregate of fewer than k rows, candidates that are dependent on it and
+ *               a column that is zero there all end this way: rank deficiency is an ordinary input.  Row i of T holds q_c of its
+ *               aggregate at column a k + c for the kept c only; B_{l+1} (n_agg k x k) holds R at rows a k .. a k + k - 1, so that
+ *               T B_{l+1} = B_l up to rounding and what was dropped.
+ *   A_{l+1}     R_l (A_l P_l) + E, E the matrix with a stored 1 on the diagonal of every coarse dof whose column of T is empty (its row
+ *               and column of R_l (A_l P_l) are empty): a decoupled identity row, by smm_hip_csr_add_create_*; a level with no dropped
+ *               column takes R_l (A_l P_l) itself.  No level has a zero diagonal.
+ *   the level is the coarsest when it would not shrink: 10 n_agg k >= 9 n.
+ * SMM_AMG_DROP_TOL = 2^-13: far above the rounding left by an exact dependency in either dtype (a few k eps of norm0), far below the
+ * part of a rigid rotation that is independent of the translations on an aggregate unless the body lies some thousand aggregate
+ * diameters from the point the rotations turn about -- so fp32, fp64 and the restatement decide alike.
+ * SMM_HIP_ERR_INVALID: what smm_hip_precond_create_amg refuses so; k outside 1 .. 6; dofs_per_node outside 1 .. 4 or not a divisor of
+ * the rows; rows * k >= 2^31; the other dtype; a value of B that is not finite.  A column of B that is zero everywhere is dropped on
+ * every aggregate, not refused.  SMM_HIP_ERR_PRECOND: as smm_hip_precond_create_amg.
+ * Set-up cost beyond the above, per level: two products and a transpose for N, one stable radix sort of n keys, the QR kernel (one
+ * wavefront per aggregate, 16 or 32 lanes where no aggregate of the level is larger; the block sits in LDS up to
+ * SMM_AMG_QR_LDS_ROWS rows and in global memory beyond: reads and writes n k values once each), three 4 n_agg-byte read-backs.
+ * amg_refresh keeps the aggregates, T and every B_l (the QR does not depend on the values of `a`) and redoes S, the products and the sum
+ * with E.  amg_info, amg_level, amg_aggregates (the aggregate of every DOF) and amg_coarse_inverse_* serve such a handle as any other.
+ * amg_candidates_*: the first `count` values of B_l of level `level` (n_l x k column-major; b_l may be NULL with count 0), *k, the
+ *   number of columns dropped on that level (0 on the coarsest) and T_l, BORROWED like amg_level's handles (NULL on the coarsest level);
+ *   any of the three pointers may be NULL.  SMM_HIP_ERR_INVALID for a handle created without candidates. */
+#define SMM_AMG_MAX_CANDIDATES 6
+#define SMM_AMG_MAX_DOFS_PER_NODE 4
+#define SMM_AMG_DROP_TOL 0.0001220703125 /* 2^-13 */
+#define SMM_AMG_QR_LDS_ROWS 256
+int smm_hip_precond_create_amg_candidates_f32(const smm_hip_csr* a, const float* B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows,
+                                              int smooth_degree, double eig_ratio, smm_hip_precond** out);
+int smm_hip_precond_create_amg_candidates_f64(const smm_hip_csr* a, const double* B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows,
+                                              int smooth_degree, double eig_ratio, smm_hip_precond** out);
+int smm_hip_precond_create_amg_candidates_dev_f32(const smm_hip_csr* a, const float* d_B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows,
+                                                  int smooth_degree, double eig_ratio, smm_hip_stream stream, smm_hip_precond** out);
+int smm_hip_precond_create_amg_candidates_dev_f64(const smm_hip_csr* a, const double* d_B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows,
+                                                  int smooth_degree, double eig_ratio, smm_hip_stream stream, smm_hip_precond** out);
+int smm_hip_precond_amg_candidates_f32(const smm_hip_precond* M, int level, float* b_l, size_t count, int* k, int* dropped, smm_hip_csr** t_l);
+int smm_hip_precond_amg_candidates_f64(const smm_hip_precond* M, int level, double* b_l, size_t count, int* k, int* dropped, smm_hip_csr** t_l);
 /* The multicolour kinds (SMM_PRECOND_MULTICOLOR_*, defined above) with a colouring of the caller's.  base_kind: SMM_PRECOND_SGS, _ILU0 or
  * _IC0.  colors: NULL (count ignored) for smm_hip_csr_color's, or `count` == rows colours on the HOST, each in [0, rows); it is checked
  * on the device -- a stored entry (i, j), i != j, with colors[i] == colors[j] gives SMM_HIP_ERR_INVALID.  Colours nobody holds are

@@ -99,6 +99,12 @@ struct Abi<float> {
 		return smm_hip_lsqr_f32(a, at, b, x, it, eps, damp, st, steps, reason, nullptr, nullptr);
 	}
 	static int apply(const smm_hip_precond* M, const float* r, float* x) { return smm_hip_precond_apply_f32(M, r, x); }
+	static int createAmgCandidates(const smm_hip_csr* a, const float* B, int k, int b, double theta, int levels, int coarse, int degree, double ratio, smm_hip_precond** o) {
+		return smm_hip_precond_create_amg_candidates_f32(a, B, k, b, theta, levels, coarse, degree, ratio, o);
+	}
+	static int amgCandidates(const smm_hip_precond* M, int level, float* out, size_t count, int* k, int* dropped) {
+		return smm_hip_precond_amg_candidates_f32(M, level, out, count, k, dropped, nullptr);
+	}
 	static int scale(smm_hip_csr* m, float a) { return smm_hip_csr_scale_f32(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, float a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f32(m, a, o, nullptr); }
 	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f32(m, nullptr); }
@@ -164,6 +170,12 @@ struct Abi<double> {
 		return smm_hip_lsqr_f64(a, at, b, x, it, eps, damp, st, steps, reason, nullptr, nullptr);
 	}
 	static int apply(const smm_hip_precond* M, const double* r, double* x) { return smm_hip_precond_apply_f64(M, r, x); }
+	static int createAmgCandidates(const smm_hip_csr* a, const double* B, int k, int b, double theta, int levels, int coarse, int degree, double ratio, smm_hip_precond** o) {
+		return smm_hip_precond_create_amg_candidates_f64(a, B, k, b, theta, levels, coarse, degree, ratio, o);
+	}
+	static int amgCandidates(const smm_hip_precond* M, int level, double* out, size_t count, int* k, int* dropped) {
+		return smm_hip_precond_amg_candidates_f64(M, level, out, count, k, dropped, nullptr);
+	}
 	static int scale(smm_hip_csr* m, double a) { return smm_hip_csr_scale_f64(m, a, nullptr); }
 	static int axpy(smm_hip_csr* m, double a, const smm_hip_csr* o) { return smm_hip_csr_axpy_f64(m, a, o, nullptr); }
 	static int zero(smm_hip_csr* m) { return smm_hip_csr_zero_f64(m, nullptr); }
@@ -465,6 +477,10 @@ public:
 			if (kind == SMM_PRECOND_CHEBYSHEV) {
 				return detail::note(smm_hip_precond_create_chebyshev(dev, cheb.degree, cheb.boundMode, cheb.eigRatio, cheb.powerSteps, cheb.lambdaMin, cheb.lambdaMax, &h)) == SMM_HIP_OK ? 0 : 1;
 			}
+			if (kind == SMM_PRECOND_AMG && amg.k > 0) {
+				return detail::note(detail::Abi<T>::createAmgCandidates(dev, amg.candidates.data(), amg.k, amg.dofsPerNode, amg.theta, amg.maxLevels, amg.coarseRows,
+				                                                        amg.smoothDegree, amg.eigRatio, &h)) == SMM_HIP_OK ? 0 : 1;
+			}
 			if (kind == SMM_PRECOND_AMG) {
 				return detail::note(smm_hip_precond_create_amg(dev, amg.theta, amg.maxLevels, amg.coarseRows, amg.smoothDegree, amg.eigRatio, &h)) == SMM_HIP_OK ? 0 : 1;
 			}
@@ -497,6 +513,8 @@ public:
 			double theta = 0.08;
 			int maxLevels = 10, coarseRows = 256, smoothDegree = 2;
 			double eigRatio = 30.0;
+			std::vector<T> candidates;  // k > 0: smm_hip_precond_create_amg_candidates_* with this n x k column-major block
+			int k = 0, dofsPerNode = 1;
 		} amg;
 		int ainvPower = 1;  // what smm_hip_precond_create_ainv takes (kinds FSAI / SPAI only)
 		struct JacobiSweepParameters {  // what smm_hip_precond_create_jsweep takes (kinds JSWEEP_* only); 0 steps: the default, 3
@@ -584,7 +602,21 @@ public:
 			this->amg.smoothDegree = smoothDegree;
 			this->amg.eigRatio = eigRatio;
 		}
+		// with near-null-space candidates (smm_hip.h, smm_hip_precond_create_amg_candidates_*): B is rows x k, COLUMN-MAJOR, 1 <= k <= 6, copied
+		// here; dofsPerNode (1 .. 4) consecutive rows form a node.  For elasticity: the rigid body modes, 2 or 3 dofs per node.
+		AMGPreconditioner(const CSRMatrix& m, const T* B, int k, int dofsPerNode, double theta = 0.08, int maxLevels = 10, int coarseRows = 256, int smoothDegree = 2,
+		                  double eigRatio = 30.0)
+		    : AMGPreconditioner(m, theta, maxLevels, coarseRows, smoothDegree, eigRatio) {
+			this->amg.k = k;
+			this->amg.dofsPerNode = dofsPerNode;
+			if (B && k > 0) this->amg.candidates.assign(B, B + static_cast<size_t>(m.getDenseRowCount()) * static_cast<size_t>(k));
+		}
 		AMGPreconditioner(AMGPreconditioner&&) noexcept = default;
+		// B_l of a level (rows_l x k column-major, the first `count` values; out may be null with count 0), k and the columns dropped there
+		int candidates(int level, T* out, size_t count, int* k, int* dropped) const noexcept {
+			if (this->init()) return 1;
+			return detail::note(detail::Abi<T>::amgCandidates(this->h, level, out, count, k, dropped)) == SMM_HIP_OK ? 0 : 1;
+		}
 		int validate() noexcept { return this->init(); }
 		// levels, rows / nnz of the first `count` levels (either may be null) and the operator complexity; non-zero when it could not be made
 		int info(int* levels, int* rows, int* nnz, size_t count, double* operatorComplexity) const noexcept {
@@ -1206,6 +1238,11 @@ public:
 	// the multigrid preconditioner with chosen parameters (the arguments of smm_hip_precond_create_amg)
 	AMGPreconditioner getAMGPreconditioner(double theta = 0.08, int maxLevels = 10, int coarseRows = 256, int smoothDegree = 2, double eigRatio = 30.0) const noexcept {
 		return AMGPreconditioner(*this, theta, maxLevels, coarseRows, smoothDegree, eigRatio);
+	}
+	// ... with near-null-space candidates: B is getDenseRowCount() x k column-major, dofsPerNode consecutive rows form a node
+	AMGPreconditioner getAMGPreconditioner(const T* B, int k, int dofsPerNode, double theta = 0.08, int maxLevels = 10, int coarseRows = 256, int smoothDegree = 2,
+	                                       double eigRatio = 30.0) const {
+		return AMGPreconditioner(*this, B, k, dofsPerNode, theta, maxLevels, coarseRows, smoothDegree, eigRatio);
 	}
 
 	// addition: ||A||_2, the largest singular value -- SMM::svds with k = 1 and no vectors (needs min(rows, cols) >= 3).  tol as in SMM::svds.

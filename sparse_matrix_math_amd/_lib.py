@@ -95,6 +95,9 @@ _TYPED = {
     "smm_hip_precond_apply_spmv_dev": (c_int, [_P, _P, _P, _P]),
     "smm_hip_precond_values": (c_int, [_P, _P, c_size_t]),
     "smm_hip_precond_amg_coarse_inverse": (c_int, [_P, _P, c_size_t]),
+    "smm_hip_precond_create_amg_candidates": (c_int, [_P, _P, c_int, c_int, c_double, c_int, c_int, c_int, c_double, POINTER(_P)]),
+    "smm_hip_precond_create_amg_candidates_dev": (c_int, [_P, _P, c_int, c_int, c_double, c_int, c_int, c_int, c_double, _P, POINTER(_P)]),
+    "smm_hip_precond_amg_candidates": (c_int, [_P, c_int, _P, c_size_t, POINTER(c_int), POINTER(c_int), POINTER(_P)]),
     "smm_hip_gen_poisson2d_dev": (c_int, [c_int, c_int, _P, _P, _P, _P]),
     "smm_hip_gen_stencil3d_dev": (c_int, [c_int, c_int, c_int, "T", "T", "T", _P, _P, _P, _P]),
     "smm_hip_gen_banded_dev": (c_int, [c_int, c_int, c_ulonglong, c_int, "T", _P, _P, _P, _P]),

@@ -17,6 +17,16 @@
 //   coarsest level    copied to the host, inverted in double by Gauss-Jordan with partial pivoting, rounded to T once, kept dense
 // No result depends on how rows are dealt to lanes: integer maxima / minima and counts only, every pass out of place.
 //
+// Created with near-null-space candidates B (smm_hip_precond_create_amg_candidates_*; tests/amg_candidates_restatement.py), a level differs in:
+//   node graph        block size b > 1: N = Tb^T ((A o A) Tb) by the library's product and transpose, the root of every value; the kernels
+//                     above run on N unchanged and a dof inherits its node's aggregate
+//   T                 the member dofs of every aggregate in ascending order (one stable radix sort), the thin QR of its block of B_l by
+//                     modified Gram-Schmidt (amgQrKernel: one wavefront or 16 / 32 lanes per aggregate, the block in LDS up to 256 rows,
+//                     inner products in an order fixed by the aggregate's size alone); Q is T's values, R the rows of B_{l+1}
+//   dropped columns   a column dependent on the earlier ones on an aggregate has no entries in T; its coarse dof gets a stored 1:
+//                     A_{l+1} = R (A P) + E by the library's sum
+// The cycle does not know about candidates.  Byte model and summation order: DESIGN.md section 3.31.
+//
 // The cycle (amgCycle) is launches only: per level two smoother applies, two residual SpMVs with A_l, one SpMV with R_l, one with P_l and
 // one x += d pass; the coarsest level is one launch, one wavefront per row.  Every launch takes the solver's done flag.  All level vectors
 // belong to the handle: one handle serves one stream at a time.  Traffic per cycle: DESIGN.md section 3.14.
@@ -25,6 +35,7 @@
 #include <string>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "smm_device.h"
@@ -38,11 +49,16 @@ struct smm_amg_level {
 	bool coarsest = true;
 	smm_hip_precond* cheb = nullptr;  // the smoother; its d_values is the diagonal copy
 	double lam = 0.0;
-	int* d_agg = nullptr;      // [n] aggregate numbers = T's positions
-	int* d_tstart = nullptr;   // [n + 1] 0 .. n
-	void* d_tval = nullptr;    // [n] ones
+	int* d_agg = nullptr;      // [n] aggregate numbers (without candidates: T's positions as well)
+	int* d_tstart = nullptr;   // [n + 1] 0 .. n; with candidates: the kept columns of every row's aggregate, scanned
+	void* d_tval = nullptr;    // [n] ones; with candidates: [nnz(T)] the columns of Q
 	void* d_sval = nullptr;    // [nnz] S on A's pattern
 	smm_hip_csr *S = nullptr, *Tm = nullptr, *P = nullptr, *R = nullptr, *AP = nullptr, *Anext = nullptr;
+	// created with candidates (k > 0 in the handle): T holds up to k entries per row at d_tpos, B_l is kept for every level
+	int nAgg = 0, dropped = 0;  // aggregates (nc = nAgg k coarse dofs); coarse dofs whose column of T is empty
+	int* d_tpos = nullptr;      // [nnz(T)]
+	void* d_B = nullptr;        // [n x k] column-major, leading dimension n
+	smm_hip_csr *E = nullptr, *RAP = nullptr;  // dropped > 0: Anext = RAP + E, E the stored ones of the dropped coarse dofs
 	void *x = nullptr, *b = nullptr, *r = nullptr, *d = nullptr;  // level vectors (level 0: r and d only)
 };
 
@@ -52,6 +68,8 @@ struct smm_precond_amg {
 	std::vector<smm_amg_level> lv;
 	void* d_inv = nullptr;  // [nL x nL] row-major, T
 	int nL = 0;
+	int k = 0, dofsPerNode = 1;  // k > 0: created with k candidates (smm_hip_precond_create_amg_candidates_*)
+	void* nextB = nullptr;       // during such a create: B_l of the level about to be made (the level takes it over)
 };
 
 namespace smm {
@@ -205,6 +223,168 @@ __global__ __launch_bounds__(TPB) void amgTentativeKernel(int n, int* __restrict
 	}
 }
 
+// ---- created with candidates: the node graph, the grouping by aggregate and the QR of every aggregate's block of B_l ----------------------
+constexpr int AMG_MAX_K = SMM_AMG_MAX_CANDIDATES;
+constexpr int AMG_QR_LDS_ROWS = SMM_AMG_QR_LDS_ROWS;
+
+__device__ __forceinline__ float amgSqrt(float x) { return __builtin_sqrtf(x); }
+__device__ __forceinline__ double amgSqrt(double x) { return __builtin_sqrt(x); }
+
+#define AMG_ITEMS(i, count) for (long long i = static_cast<long long>(blockIdx.x) * TPB + threadIdx.x; i < (count); i += static_cast<long long>(gridDim.x) * TPB)
+
+template <typename T>
+__global__ __launch_bounds__(TPB) void amgSquareKernel(long long count, const T* __restrict__ in, T* __restrict__ out) {
+	AMG_ITEMS(i, count) out[i] = in[i] * in[i];
+}
+
+template <typename T>
+__global__ __launch_bounds__(TPB) void amgRootKernel(long long count, T* __restrict__ v) {
+	AMG_ITEMS(i, count) v[i] = amgSqrt(v[i]);
+}
+
+// Tb, the dof -> node map: n x n / b, one 1 per row at column i / b
+template <typename T>
+__global__ __launch_bounds__(TPB) void amgNodeMapKernel(int n, int b, int* __restrict__ start, int* __restrict__ positions, T* __restrict__ vals) {
+	AMG_ROWS(row, n + 1LL) {
+		start[row] = static_cast<int>(row);
+		if (row < n) {
+			positions[row] = static_cast<int>(row / b);
+			vals[row] = T(1);
+		}
+	}
+}
+
+// the stored diagonal entry of every row (0 where a row has none)
+template <typename T>
+__global__ __launch_bounds__(TPB) void amgDiagKernel(int n, const int* __restrict__ start, const int* __restrict__ positions, const T* __restrict__ vals, T* __restrict__ diag) {
+	AMG_ROWS(row, n) {
+		T d = T(0);
+		for (int k = start[row]; k < start[row + 1]; ++k) {
+			if (positions[k] == row) d = vals[k];
+		}
+		diag[row] = d;
+	}
+}
+
+// a dof inherits its node's aggregate; also the identity the stable grouping sorts along
+__global__ __launch_bounds__(TPB) void amgInheritKernel(int n, int b, const int* __restrict__ nodeAgg, int* __restrict__ agg) {
+	AMG_ROWS(row, n) { agg[row] = nodeAgg[row / b]; }
+}
+__global__ __launch_bounds__(TPB) void amgIotaKernel(int n, int* __restrict__ out) {
+	AMG_ROWS(row, n) { out[row] = static_cast<int>(row); }
+}
+
+// bounds[a] = the first position of the sorted aggregate numbers that holds a number >= a (a = 0 .. nAgg)
+__global__ __launch_bounds__(TPB) void amgBoundsKernel(int nAgg, int n, const int* __restrict__ sorted, int* __restrict__ bounds) {
+	AMG_ROWS(a, nAgg + 1LL) {
+		int lo = 0, hi = n;
+		while (lo < hi) {
+			const int mid = lo + (hi - lo) / 2;
+			if (sorted[mid] < a) lo = mid + 1;
+			else hi = mid;
+		}
+		bounds[a] = lo;
+	}
+}
+
+template <typename T>
+__global__ __launch_bounds__(TPB) void amgFiniteKernel(long long count, const T* __restrict__ v, int* bad) {
+	AMG_ITEMS(i, count) {
+		if (!isfinite(v[i])) atomicOr(bad, 1);
+	}
+}
+
+// The thin QR of every aggregate's block of B_l by modified Gram-Schmidt: G lanes per aggregate (G = 16 / 32 where no aggregate of the
+// level has more rows than that, else one wavefront).  Rank r of the aggregate -- its member dofs ascend -- belongs to lane r mod G, which
+// alone reads and writes that row of the block: the lanes meet in the inner products only.  An inner product: every lane sums its ranks in
+// ascending order from +0.0 with smmFma, then the xor butterfly G / 2 .. 1; with m <= G a lane holds one term and the missing lanes +0.0, so
+// the sum is what the 64-lane form gives: a function of m alone.  The block (column c at w + c m) sits in LDS while m <= LROWS and in its
+// place in qd otherwise.  Column c: norm0 = |v_c| as gathered; v_c = smmFma(-r_jc, q_j, v_c) for the kept j < c ascending, r_jc =
+// q_j . v_c; nrm = |v_c|; kept iff nrm > tol norm0: q_c = v_c / nrm, r_cc = nrm; otherwise q_c = 0 and row c of R stays zero.  R goes to
+// rows a k .. of Bnext (zeroed by the caller), Q to qd (aggregate a at qd + start_a k, column-major, leading dimension m).
+// Every shuffle is reached by all lanes: the loops over aggregates, c and j are uniform, a group without an aggregate runs them with m = 0.
+template <typename T, int G>
+__global__ __launch_bounds__(TPB) void amgQrKernel(int nAgg, int k, int n, const int* __restrict__ aggStart, const int* __restrict__ members, const T* __restrict__ B,
+                                                   T* __restrict__ qd, T* __restrict__ Bnext, int* __restrict__ keptMask, T tol) {
+	constexpr int GROUPS = TPB / G;
+	constexpr int LROWS = G == WAVE ? AMG_QR_LDS_ROWS : G;
+	__shared__ T lds[GROUPS * LROWS * AMG_MAX_K];
+	const int t = threadIdx.x % G;
+	const int grp = threadIdx.x / G;
+	const size_t ldn = static_cast<size_t>(nAgg) * k;
+	for (int first = blockIdx.x * GROUPS; first < nAgg; first += gridDim.x * GROUPS) {
+		const int a = first + grp;
+		const bool live = a < nAgg;
+		const int o = live ? aggStart[a] : 0;
+		const int m = live ? aggStart[a + 1] - o : 0;
+		const bool inLds = m <= LROWS;
+		T* const home = qd + static_cast<size_t>(o) * k;
+		T* const w = inLds ? lds + grp * (LROWS * AMG_MAX_K) : home;
+		for (int c = 0; c < k; ++c) {
+			for (int r = t; r < m; r += G) w[c * m + r] = B[static_cast<size_t>(c) * n + members[o + r]];
+		}
+		unsigned kept = 0;
+		for (int c = 0; c < k; ++c) {
+			T* const v = w + c * m;
+			T acc = T(0);
+			for (int r = t; r < m; r += G) acc = smmFma(v[r], v[r], acc);
+			const T norm0 = amgSqrt(groupSum<G>(acc));
+			for (int j = 0; j < c; ++j) {
+				const T* const q = w + j * m;
+				acc = T(0);
+				for (int r = t; r < m; r += G) acc = smmFma(q[r], v[r], acc);
+				const T rjc = groupSum<G>(acc);
+				if ((kept >> j) & 1u) {
+					for (int r = t; r < m; r += G) v[r] = smmFma(-rjc, q[r], v[r]);
+					if (t == 0) Bnext[static_cast<size_t>(c) * ldn + static_cast<size_t>(a) * k + j] = rjc;
+				}
+			}
+			acc = T(0);
+			for (int r = t; r < m; r += G) acc = smmFma(v[r], v[r], acc);
+			const T nrm = amgSqrt(groupSum<G>(acc));
+			if (nrm > tol * norm0) {
+				kept |= 1u << c;
+				for (int r = t; r < m; r += G) v[r] = v[r] / nrm;
+				if (t == 0) Bnext[static_cast<size_t>(c) * ldn + static_cast<size_t>(a) * k + c] = nrm;
+			} else {
+				for (int r = t; r < m; r += G) v[r] = T(0);
+			}
+		}
+		if (inLds) {
+			for (int c = 0; c < k; ++c) {
+				for (int r = t; r < m; r += G) home[c * m + r] = w[c * m + r];
+			}
+		}
+		if (live && t == 0) keptMask[a] = static_cast<int>(kept);
+	}
+}
+
+// count[i] = the kept columns of row i's aggregate (count[n] = 0): scanned, T's row starts
+__global__ __launch_bounds__(TPB) void amgRowCountKernel(int n, const int* __restrict__ agg, const int* __restrict__ keptMask, int* __restrict__ count) {
+	AMG_ROWS(row, n + 1LL) { count[row] = row < n ? __popc(static_cast<unsigned>(keptMask[agg[row]])) : 0; }
+}
+
+// T's positions and values, one lane per place p of the grouping: row members[p] takes q_c of its aggregate at column a k + c, kept c only
+template <typename T>
+__global__ __launch_bounds__(TPB) void amgTentativeFillKernel(int n, int k, const int* __restrict__ members, const int* __restrict__ sortedAgg, const int* __restrict__ aggStart,
+                                                              const int* __restrict__ keptMask, const int* __restrict__ tstart, const T* __restrict__ qd,
+                                                              int* __restrict__ tpos, T* __restrict__ tval) {
+	AMG_ROWS(p, n) {
+		const int a = sortedAgg[p];
+		const int o = aggStart[a];
+		const int m = aggStart[a + 1] - o;
+		const unsigned kept = static_cast<unsigned>(keptMask[a]);
+		int e = tstart[members[p]];
+		for (int c = 0; c < k; ++c) {
+			if ((kept >> c) & 1u) {
+				tpos[e] = a * k + c;
+				tval[e] = qd[static_cast<size_t>(o) * k + static_cast<size_t>(c) * m + (p - o)];
+				++e;
+			}
+		}
+	}
+}
+
 // S = I - omega D^-1 A on A's pattern: s = omega / d_i; off the diagonal -(s a_ij), on it 1 - s a_ii; every operation rounds once
 template <typename T>
 __global__ __launch_bounds__(TPB) void amgSmootherKernel(int n, const int* __restrict__ start, const int* __restrict__ positions, const T* __restrict__ vals,
@@ -280,11 +460,10 @@ int makeSmoother(const smm_precond_amg* G, smm_amg_level& L) {
 	return smm_hip_precond_chebyshev_info(L.cheb, nullptr, nullptr, nullptr, &L.lam);
 }
 
-// the aggregates of level L: L.d_agg and L.nc
+// the aggregates of the graph A (n rows, its diagonal in diag): *outAgg (n + 1 ints, the caller's from then on) and *outCount
 template <typename T>
-int aggregate(smm_amg_level& L, double thetaL, hipStream_t s) {
-	const smm_hip_csr* A = L.A;
-	const int n = L.n, g = rowGrid(n);
+int aggregateGraph(const smm_hip_csr* A, const T* diag, double thetaL, int** outAgg, int* outCount, hipStream_t s) {
+	const int n = A->rows, g = rowGrid(n);
 	const size_t len = static_cast<size_t>(n) + 1;
 	DevBuf<unsigned char> strong;
 	DevBuf<int> stateA, stateB, flag, number, aggB, word;
@@ -300,8 +479,9 @@ int aggregate(smm_amg_level& L, double thetaL, hipStream_t s) {
 	SMM_TRY(keyA.alloc(len));
 	SMM_TRY(keyB.alloc(len));
 	SMM_TRY(keyC.alloc(len));
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_agg), len * sizeof(int)));
-	amgStrongKernel<T><<<g, TPB, 0, s>>>(n, A->d_start, A->d_positions, static_cast<const T*>(A->d_values), diagOf<T>(L), thetaL * thetaL, strong);
+	SMM_TRY(devAlloc(reinterpret_cast<void**>(outAgg), len * sizeof(int)));
+	int* const agg = *outAgg;
+	amgStrongKernel<T><<<g, TPB, 0, s>>>(n, A->d_start, A->d_positions, static_cast<const T*>(A->d_values), diag, thetaL * thetaL, strong);
 	amgInitKernel<<<g, TPB, 0, s>>>(n, stateA, keyA);
 	int* stIn = stateA;
 	int* stOut = stateB;
@@ -327,8 +507,8 @@ int aggregate(smm_amg_level& L, double thetaL, hipStream_t s) {
 	SMM_TRY(scanExclusive(flag, number, len, s));
 	int nRoots = 0;
 	SMM_TRY(readInt(number.p + n, &nRoots, s));
-	amgPhase1Kernel<<<g, TPB, 0, s>>>(n, A->d_start, A->d_positions, strong, state, number, L.d_agg);
-	int* aIn = L.d_agg;
+	amgPhase1Kernel<<<g, TPB, 0, s>>>(n, A->d_start, A->d_positions, strong, state, number, agg);
+	int* aIn = agg;
 	int* aOut = aggB;
 	for (long long pass = 0; pass <= n; ++pass) {
 		SMM_HIP_TRY(hipMemsetAsync(word, 0, sizeof(int), s));
@@ -339,16 +519,156 @@ int aggregate(smm_amg_level& L, double thetaL, hipStream_t s) {
 		if (got == 0) break;  // (aOut equals aIn)
 		std::swap(aIn, aOut);
 	}
-	if (aIn != L.d_agg) SMM_HIP_TRY(hipMemcpyAsync(L.d_agg, aIn, static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToDevice, s));
-	amgFlagKernel<<<rowGrid(len), TPB, 0, s>>>(n, L.d_agg, 0, true, flag);
+	if (aIn != agg) SMM_HIP_TRY(hipMemcpyAsync(agg, aIn, static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToDevice, s));
+	amgFlagKernel<<<rowGrid(len), TPB, 0, s>>>(n, agg, 0, true, flag);
 	SMM_TRY(scanExclusive(flag, number, len, s));
 	int left = 0;
 	SMM_TRY(readInt(number.p + n, &left, s));
-	if (left) amgLeftKernel<<<g, TPB, 0, s>>>(n, nRoots, number, L.d_agg);
+	if (left) amgLeftKernel<<<g, TPB, 0, s>>>(n, nRoots, number, agg);
 	SMM_HIP_TRY(hipGetLastError());
 	SMM_HIP_TRY(hipStreamSynchronize(s));  // the scratch arrays go back to the allocator when this scope ends
 	drain.armed = false;
-	L.nc = nRoots + left;
+	*outCount = nRoots + left;
+	return SMM_HIP_OK;
+}
+
+// the aggregates of level L: L.d_agg and L.nc
+template <typename T>
+int aggregate(smm_amg_level& L, double thetaL, hipStream_t s) {
+	return aggregateGraph<T>(L.A, diagOf<T>(L), thetaL, &L.d_agg, &L.nc, s);
+}
+
+template <typename T>
+int createDev(int rows, int cols, const int* start, const int* positions, const T* vals, smm_hip_csr** out) {
+	if (std::is_same<T, float>::value) return smm_hip_csr_create_dev_f32(rows, cols, start, positions, reinterpret_cast<const float*>(vals), out);
+	return smm_hip_csr_create_dev_f64(rows, cols, start, positions, reinterpret_cast<const double*>(vals), out);
+}
+
+// handles of a set-up stage that wrap its scratch arrays: destroyed before those arrays are released
+struct ScratchHandles {
+	std::vector<smm_hip_csr*> h;
+	~ScratchHandles() {
+		for (smm_hip_csr* m : h) smm_hip_csr_destroy(m);
+	}
+	smm_hip_csr** add() {
+		h.push_back(nullptr);
+		return &h.back();
+	}
+};
+
+// created with candidates: the dof aggregates of level L (block size b) -- L.d_agg, L.nAgg.  b > 1: the aggregates of the node graph
+// N = Tb^T ((A o A) Tb) with the root of every value, N_IJ = the Frobenius norm of block (I, J); a dof inherits its node's aggregate
+template <typename T>
+int nodeAggregates(smm_amg_level& L, int b, double thetaL, hipStream_t s) {
+	if (b == 1) return aggregateGraph<T>(L.A, diagOf<T>(L), thetaL, &L.d_agg, &L.nAgg, s);
+	const smm_hip_csr* A = L.A;
+	const int n = L.n, nodes = n / b;
+	DevBuf<int> mapStart, mapPos, nodeAgg;
+	DevBuf<T> ones, squared, diag;
+	ScratchHandles tmp;
+	tmp.h.reserve(5);
+	DrainOnExit drain(s);
+	SMM_TRY(mapStart.alloc(static_cast<size_t>(n) + 1));
+	SMM_TRY(mapPos.alloc(static_cast<size_t>(n)));
+	SMM_TRY(ones.alloc(static_cast<size_t>(n)));
+	SMM_TRY(squared.alloc(static_cast<size_t>(std::max(1, A->nnz))));
+	SMM_TRY(diag.alloc(static_cast<size_t>(nodes)));
+	amgNodeMapKernel<T><<<rowGrid(n + 1LL), TPB, 0, s>>>(n, b, mapStart, mapPos, ones);
+	amgSquareKernel<T><<<rowGrid(A->nnz), TPB, 0, s>>>(A->nnz, static_cast<const T*>(A->d_values), squared);
+	SMM_HIP_TRY(hipGetLastError());
+	smm_hip_csr **A2 = tmp.add(), **Tb = tmp.add(), **TbT = tmp.add(), **A2Tb = tmp.add(), **N = tmp.add();
+	SMM_TRY(createDev<T>(n, n, A->d_start, A->d_positions, squared.p, A2));
+	SMM_TRY(createDev<T>(n, nodes, mapStart, mapPos, ones.p, Tb));
+	SMM_TRY(smm_hip_csr_multiply_create(*A2, *Tb, asHandle(s), A2Tb));
+	SMM_TRY(smm_hip_csr_transpose_create(*Tb, asHandle(s), TbT));
+	SMM_TRY(smm_hip_csr_multiply_create(*TbT, *A2Tb, asHandle(s), N));
+	const smm_hip_csr* g = *N;
+	amgRootKernel<T><<<rowGrid(g->nnz), TPB, 0, s>>>(g->nnz, static_cast<T*>(g->d_values));
+	amgDiagKernel<T><<<rowGrid(nodes), TPB, 0, s>>>(nodes, g->d_start, g->d_positions, static_cast<const T*>(g->d_values), diag);
+	SMM_HIP_TRY(hipGetLastError());
+	int* perNode = nullptr;
+	const int st = aggregateGraph<T>(g, diag.p, thetaL, &perNode, &L.nAgg, s);
+	nodeAgg.p = perNode;  // (released with the other scratch arrays)
+	SMM_TRY(st);
+	SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_agg), (static_cast<size_t>(n) + 1) * sizeof(int)));
+	amgInheritKernel<<<rowGrid(n), TPB, 0, s>>>(n, b, nodeAgg, L.d_agg);
+	SMM_HIP_TRY(hipGetLastError());
+	SMM_HIP_TRY(hipStreamSynchronize(s));
+	drain.armed = false;
+	return SMM_HIP_OK;
+}
+
+template <typename T, int G>
+void launchQr(int nAgg, int k, int n, const int* aggStart, const int* members, const T* B, T* qd, T* Bnext, int* keptMask, hipStream_t s) {
+	constexpr int GROUPS = TPB / G;
+	const int grid = static_cast<int>(std::max<long long>(1, std::min<long long>((nAgg + GROUPS - 1LL) / GROUPS, numCUs() * 8LL)));
+	amgQrKernel<T, G><<<grid, TPB, 0, s>>>(nAgg, k, n, aggStart, members, B, qd, Bnext, keptMask, static_cast<T>(SMM_AMG_DROP_TOL));
+}
+
+// created with candidates: T of level L (d_tstart, d_tpos, d_tval), *Bnext = B_{l+1} (nc x k, the caller's from then on), L.dropped and E
+template <typename T>
+int buildTentative(const smm_precond_amg* G, smm_amg_level& L, void** Bnext, hipStream_t s) {
+	const int n = L.n, k = G->k, nAgg = L.nAgg;
+	const size_t nk = static_cast<size_t>(n) * k, nck = static_cast<size_t>(L.nc) * k;
+	DevBuf<int> iota, sortedAgg, members, aggStart, keptMask, count;
+	DevBuf<T> qd, next;
+	DevBuf<unsigned char> temp;
+	DrainOnExit drain(s);
+	SMM_TRY(iota.alloc(static_cast<size_t>(n)));
+	SMM_TRY(sortedAgg.alloc(static_cast<size_t>(n)));
+	SMM_TRY(members.alloc(static_cast<size_t>(n)));
+	SMM_TRY(aggStart.alloc(static_cast<size_t>(nAgg) + 1));
+	SMM_TRY(keptMask.alloc(static_cast<size_t>(nAgg)));
+	SMM_TRY(count.alloc(static_cast<size_t>(n) + 1));
+	SMM_TRY(qd.alloc(nk));
+	SMM_TRY(next.alloc(nck));
+	// the member dofs of every aggregate in ascending order: a stable sort of the dof numbers by aggregate number
+	amgIotaKernel<<<rowGrid(n), TPB, 0, s>>>(n, iota);
+	size_t bytes = 0;
+	SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, L.d_agg, sortedAgg.p, iota.p, members.p, static_cast<size_t>(n), 0u, 32u, s));
+	SMM_TRY(temp.alloc(std::max<size_t>(bytes, 1)));
+	SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, bytes, L.d_agg, sortedAgg.p, iota.p, members.p, static_cast<size_t>(n), 0u, 32u, s));
+	amgBoundsKernel<<<rowGrid(nAgg + 1LL), TPB, 0, s>>>(nAgg, n, sortedAgg, aggStart);
+	SMM_HIP_TRY(hipGetLastError());
+	std::vector<int> bounds(static_cast<size_t>(nAgg) + 1);
+	SMM_HIP_TRY(hipMemcpyAsync(bounds.data(), aggStart.p, bounds.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+	SMM_HIP_TRY(hipStreamSynchronize(s));
+	int longest = 0;
+	for (int a = 0; a < nAgg; ++a) longest = std::max(longest, bounds[static_cast<size_t>(a) + 1] - bounds[static_cast<size_t>(a)]);
+	SMM_HIP_TRY(hipMemsetAsync(next.p, 0, std::max<size_t>(nck, 1) * sizeof(T), s));
+	const T* B = static_cast<const T*>(L.d_B);
+	if (longest <= 16) launchQr<T, 16>(nAgg, k, n, aggStart, members, B, qd, next, keptMask, s);
+	else if (longest <= 32) launchQr<T, 32>(nAgg, k, n, aggStart, members, B, qd, next, keptMask, s);
+	else launchQr<T, WAVE>(nAgg, k, n, aggStart, members, B, qd, next, keptMask, s);
+	amgRowCountKernel<<<rowGrid(n + 1LL), TPB, 0, s>>>(n, L.d_agg, keptMask, count);
+	SMM_HIP_TRY(hipGetLastError());
+	SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_tstart), (static_cast<size_t>(n) + 1) * sizeof(int)));
+	SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_tpos), std::max<size_t>(nk, 1) * sizeof(int)));
+	SMM_TRY(devAlloc(&L.d_tval, std::max<size_t>(nk, 1) * sizeof(T)));
+	SMM_TRY(scanExclusive(count, L.d_tstart, static_cast<size_t>(n) + 1, s));
+	amgTentativeFillKernel<T><<<rowGrid(n), TPB, 0, s>>>(n, k, members, sortedAgg, aggStart, keptMask, L.d_tstart, qd, L.d_tpos, static_cast<T*>(L.d_tval));
+	SMM_HIP_TRY(hipGetLastError());
+	std::vector<int> kept(static_cast<size_t>(nAgg));
+	SMM_HIP_TRY(hipMemcpyAsync(kept.data(), keptMask.p, kept.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+	SMM_HIP_TRY(hipStreamSynchronize(s));
+	drain.armed = false;
+	// E: a stored 1 on the diagonal of every coarse dof whose column of T is empty
+	std::vector<int> start(static_cast<size_t>(L.nc) + 1, 0), pos;
+	for (int a = 0; a < nAgg; ++a) {
+		for (int c = 0; c < k; ++c) {
+			const size_t row = static_cast<size_t>(a) * k + c;
+			const bool gone = ((kept[static_cast<size_t>(a)] >> c) & 1) == 0;
+			if (gone) pos.push_back(static_cast<int>(row));
+			start[row + 1] = static_cast<int>(pos.size());
+		}
+	}
+	L.dropped = static_cast<int>(pos.size());
+	if (L.dropped) {
+		const std::vector<T> ones(pos.size(), T(1));
+		if (std::is_same<T, float>::value) SMM_TRY(smm_hip_csr_create_f32(L.nc, L.nc, start.data(), pos.data(), reinterpret_cast<const float*>(ones.data()), &L.E));
+		else SMM_TRY(smm_hip_csr_create_f64(L.nc, L.nc, start.data(), pos.data(), reinterpret_cast<const double*>(ones.data()), &L.E));
+	}
+	*Bnext = next.detach();
 	return SMM_HIP_OK;
 }
 
@@ -368,23 +688,23 @@ template <typename T>
 int buildOperators(smm_amg_level& L, hipStream_t s) {
 	const smm_hip_csr* A = L.A;
 	const int n = L.n;
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_tstart), (static_cast<size_t>(n) + 1) * sizeof(int)));
-	SMM_TRY(devAlloc(&L.d_tval, static_cast<size_t>(std::max(1, n)) * sizeof(T)));
-	SMM_TRY(devAlloc(&L.d_sval, static_cast<size_t>(std::max(1, A->nnz)) * sizeof(T)));
-	amgTentativeKernel<T><<<rowGrid(n + 1LL), TPB, 0, s>>>(n, L.d_tstart, static_cast<T*>(L.d_tval));
-	SMM_TRY(fillSmoother<T>(L, s));
-	if (std::is_same<T, float>::value) {
-		SMM_TRY(smm_hip_csr_create_dev_f32(n, L.nc, L.d_tstart, L.d_agg, static_cast<const float*>(L.d_tval), &L.Tm));
-		SMM_TRY(smm_hip_csr_create_dev_f32(n, n, A->d_start, A->d_positions, static_cast<const float*>(L.d_sval), &L.S));
-	} else {
-		SMM_TRY(smm_hip_csr_create_dev_f64(n, L.nc, L.d_tstart, L.d_agg, static_cast<const double*>(L.d_tval), &L.Tm));
-		SMM_TRY(smm_hip_csr_create_dev_f64(n, n, A->d_start, A->d_positions, static_cast<const double*>(L.d_sval), &L.S));
+	if (!L.d_tpos) {  // one 1 per row at the aggregate's column; with candidates buildTentative has written T already
+		SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_tstart), (static_cast<size_t>(n) + 1) * sizeof(int)));
+		SMM_TRY(devAlloc(&L.d_tval, static_cast<size_t>(std::max(1, n)) * sizeof(T)));
 	}
+	SMM_TRY(devAlloc(&L.d_sval, static_cast<size_t>(std::max(1, A->nnz)) * sizeof(T)));
+	if (!L.d_tpos) amgTentativeKernel<T><<<rowGrid(n + 1LL), TPB, 0, s>>>(n, L.d_tstart, static_cast<T*>(L.d_tval));
+	SMM_TRY(fillSmoother<T>(L, s));
+	SMM_TRY(createDev<T>(n, L.nc, L.d_tstart, L.d_tpos ? L.d_tpos : L.d_agg, static_cast<const T*>(L.d_tval), &L.Tm));
+	SMM_TRY(createDev<T>(n, n, A->d_start, A->d_positions, static_cast<const T*>(L.d_sval), &L.S));
 	SMM_TRY(smm_hip_csr_multiply_create(L.S, L.Tm, asHandle(s), &L.P));
 	SMM_TRY(smm_hip_csr_transpose_create(L.P, asHandle(s), &L.R));
 	SMM_TRY(smm_hip_csr_multiply_create(A, L.P, asHandle(s), &L.AP));
-	SMM_TRY(smm_hip_csr_multiply_create(L.R, L.AP, asHandle(s), &L.Anext));
-	return SMM_HIP_OK;
+	if (!L.E) return smm_hip_csr_multiply_create(L.R, L.AP, asHandle(s), &L.Anext);
+	// a coarse dof whose column of T is empty has an empty row and column in R (A P): it becomes a decoupled identity row
+	SMM_TRY(smm_hip_csr_multiply_create(L.R, L.AP, asHandle(s), &L.RAP));
+	if (std::is_same<T, float>::value) return smm_hip_csr_add_create_f32(L.RAP, 1.0f, L.E, 1.0f, asHandle(s), &L.Anext);
+	return smm_hip_csr_add_create_f64(L.RAP, 1.0, L.E, 1.0, asHandle(s), &L.Anext);
 }
 
 template <typename T>
@@ -395,13 +715,15 @@ int refreshOperators(smm_amg_level& L, hipStream_t s) {
 		SMM_TRY(smm_hip_csr_multiply_into_f32(L.P, L.S, L.Tm, asHandle(s)));
 		SMM_TRY(smm_hip_csr_multiply_into_f32(L.AP, L.A, L.P, asHandle(s)));
 		SMM_TRY(smm_hip_csr_transpose_refresh_f32(L.R, L.P, asHandle(s)));
-		SMM_TRY(smm_hip_csr_multiply_into_f32(L.Anext, L.R, L.AP, asHandle(s)));
+		SMM_TRY(smm_hip_csr_multiply_into_f32(L.E ? L.RAP : L.Anext, L.R, L.AP, asHandle(s)));
+		if (L.E) SMM_TRY(smm_hip_csr_add_into_f32(L.Anext, L.RAP, 1.0f, L.E, 1.0f, asHandle(s)));
 	} else {
 		SMM_TRY(smm_hip_csr_values_changed_f64(L.S, asHandle(s)));
 		SMM_TRY(smm_hip_csr_multiply_into_f64(L.P, L.S, L.Tm, asHandle(s)));
 		SMM_TRY(smm_hip_csr_multiply_into_f64(L.AP, L.A, L.P, asHandle(s)));
 		SMM_TRY(smm_hip_csr_transpose_refresh_f64(L.R, L.P, asHandle(s)));
-		SMM_TRY(smm_hip_csr_multiply_into_f64(L.Anext, L.R, L.AP, asHandle(s)));
+		SMM_TRY(smm_hip_csr_multiply_into_f64(L.E ? L.RAP : L.Anext, L.R, L.AP, asHandle(s)));
+		if (L.E) SMM_TRY(smm_hip_csr_add_into_f64(L.Anext, L.RAP, 1.0, L.E, 1.0, asHandle(s)));
 	}
 	SMM_HIP_TRY(hipStreamSynchronize(s));
 	return SMM_HIP_OK;
@@ -532,6 +854,10 @@ void amgDestroy(smm_precond_amg* G) {
 		smm_hip_csr_destroy(L.R);
 		smm_hip_csr_destroy(L.AP);
 		smm_hip_csr_destroy(L.Anext);
+		smm_hip_csr_destroy(L.RAP);
+		smm_hip_csr_destroy(L.E);
+		devFree(L.d_tpos);
+		devFree(L.d_B);
 		devFree(L.d_agg);
 		devFree(L.d_tstart);
 		devFree(L.d_tval);
@@ -542,6 +868,7 @@ void amgDestroy(smm_precond_amg* G) {
 		devFree(L.d);
 	}
 	devFree(G->d_inv);
+	devFree(G->nextB);
 	delete G;
 }
 
@@ -558,16 +885,24 @@ static int amgCreateTyped(const smm_hip_csr* a, smm_hip_precond* M) {
 		L.A = A;
 		L.n = A->rows;
 		SMM_TRY(ensureCsrReady(A, nullptr, false));
+		L.d_B = G->nextB;
+		G->nextB = nullptr;
 		SMM_TRY(makeSmoother(G, L));
 		if (L.n <= G->coarseRows || l + 1 == G->maxLevels) break;
-		SMM_TRY(aggregate<T>(L, std::ldexp(G->theta, -l), s));
+		if (G->k) {  // node aggregates, k coarse dofs for each
+			SMM_TRY(nodeAggregates<T>(L, l == 0 ? G->dofsPerNode : G->k, std::ldexp(G->theta, -l), s));
+			L.nc = L.nAgg * G->k;  // (at most n k, which the create call has checked)
+		} else {
+			SMM_TRY(aggregate<T>(L, std::ldexp(G->theta, -l), s));
+		}
 		if (10LL * L.nc >= 9LL * L.n) {  // the level would not shrink: it is the coarsest
 			devFree(L.d_agg);
 			L.d_agg = nullptr;
-			L.nc = 0;
+			L.nc = L.nAgg = 0;
 			break;
 		}
 		L.coarsest = false;
+		if (G->k) SMM_TRY(buildTentative<T>(G, L, &G->nextB, s));
 		SMM_TRY(buildOperators<T>(L, s));
 		A = L.Anext;
 	}
@@ -625,14 +960,8 @@ static const smm_precond_amg* amgOf(const smm_hip_precond* M, const char* who) {
 	return M->amg;
 }
 
-extern "C" {
-
-int smm_hip_precond_create_amg(const smm_hip_csr* a, double theta, int max_levels, int coarse_rows, int smooth_degree, double eig_ratio, smm_hip_precond** out) {
-	if (!a || !out) {
-		setError("precond_create_amg: null argument");
-		return SMM_HIP_ERR_INVALID;
-	}
-	*out = nullptr;
+// what both ways of creating the kind check, in the order smm_hip_precond_create_amg always had
+static int amgCheckParameters(const smm_hip_csr* a, double theta, int max_levels, int coarse_rows, int smooth_degree, double eig_ratio) {
 	if (!(theta >= 0.0 && theta < 1.0)) {  // (a NaN fails both)
 		setError("precond_create_amg: theta must be in [0, 1)");
 		return SMM_HIP_ERR_INVALID;
@@ -657,8 +986,10 @@ int smm_hip_precond_create_amg(const smm_hip_csr* a, double theta, int max_level
 		setError("precond_create_amg: eig_ratio must be finite and > 1");
 		return SMM_HIP_ERR_PRECOND;
 	}
-	SMM_TRY(ensureInit());
-	SMM_TRY(ensureCsrReady(a, nullptr, false));
+	return SMM_HIP_OK;
+}
+
+static smm_hip_precond* amgNewHandle(const smm_hip_csr* a, double theta, int max_levels, int coarse_rows, int smooth_degree, double eig_ratio) {
 	auto* M = new smm_hip_precond();
 	M->kind = SMM_PRECOND_AMG;
 	M->dtype = a->dtype;
@@ -669,6 +1000,109 @@ int smm_hip_precond_create_amg(const smm_hip_csr* a, double theta, int max_level
 	M->amg->coarseRows = coarse_rows;
 	M->amg->smoothDegree = smooth_degree;
 	M->amg->eigRatio = eig_ratio;
+	return M;
+}
+
+// B: n x k column-major, on the host or (onDevice) in device memory in use on `stream`
+template <typename T>
+static int amgCreateWithCandidates(const smm_hip_csr* a, const T* B, bool onDevice, hipStream_t stream, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows,
+                                   int smooth_degree, double eig_ratio, smm_hip_precond** out) {
+	if (!a || !out) {
+		setError("precond_create_amg_candidates: null argument");
+		return SMM_HIP_ERR_INVALID;
+	}
+	*out = nullptr;
+	if (a->dtype != dtypeOf<T>()) {
+		setError("precond_create_amg_candidates: the matrix has the other dtype");
+		return SMM_HIP_ERR_INVALID;
+	}
+	if (k < 1 || k > SMM_AMG_MAX_CANDIDATES || dofs_per_node < 1 || dofs_per_node > SMM_AMG_MAX_DOFS_PER_NODE) {
+		setError("precond_create_amg_candidates: k must be 1 .. %d and dofs_per_node 1 .. %d", SMM_AMG_MAX_CANDIDATES, SMM_AMG_MAX_DOFS_PER_NODE);
+		return SMM_HIP_ERR_INVALID;
+	}
+	SMM_TRY(amgCheckParameters(a, theta, max_levels, coarse_rows, smooth_degree, eig_ratio));
+	const size_t count = static_cast<size_t>(a->rows) * static_cast<size_t>(k);
+	if (a->rows % dofs_per_node != 0 || count > 0x7fffffffULL || (count && !B)) {
+		setError("precond_create_amg_candidates: %d rows with %d dofs per node and %d candidates (the rows must be whole nodes, rows * k below 2^31, B not null)", a->rows,
+		         dofs_per_node, k);
+		return SMM_HIP_ERR_INVALID;
+	}
+	SMM_TRY(ensureInit());
+	SMM_TRY(ensureCsrReady(a, nullptr, false));
+	hipStream_t s = libStream();
+	DevBuf<T> own;
+	DevBuf<int> bad;
+	SMM_TRY(own.alloc(count));
+	SMM_TRY(bad.alloc(1));
+	if (count) {
+		if (onDevice) {
+			SMM_HIP_TRY(hipMemcpyAsync(own.p, B, count * sizeof(T), hipMemcpyDeviceToDevice, stream));
+			SMM_HIP_TRY(hipStreamSynchronize(stream));
+		} else {
+			SMM_TRY(hostToDev(own.p, B, count * sizeof(T), s));
+		}
+	}
+	SMM_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), s));
+	amgFiniteKernel<T><<<rowGrid(static_cast<long long>(count)), TPB, 0, s>>>(static_cast<long long>(count), own.p, bad.p);
+	SMM_HIP_TRY(hipGetLastError());
+	int notFinite = 0;
+	SMM_TRY(readInt(bad.p, &notFinite, s));
+	if (notFinite) {
+		setError("precond_create_amg_candidates: B holds a value that is not finite");
+		return SMM_HIP_ERR_INVALID;
+	}
+	smm_hip_precond* M = amgNewHandle(a, theta, max_levels, coarse_rows, smooth_degree, eig_ratio);
+	M->amg->k = k;
+	M->amg->dofsPerNode = dofs_per_node;
+	M->amg->nextB = own.detach();
+	const int st = amgCreateTyped<T>(a, M);
+	if (st != SMM_HIP_OK) {
+		smm_hip_precond_destroy(M);
+		return st;
+	}
+	*out = M;
+	return SMM_HIP_OK;
+}
+
+template <typename T>
+static int amgCandidatesOf(const smm_hip_precond* M, int level, T* b_l, size_t count, int* k, int* dropped, smm_hip_csr** t_l) {
+	const smm_precond_amg* G = amgOf(M, "precond_amg_candidates");
+	if (!G) return SMM_HIP_ERR_INVALID;
+	if (G->k == 0 || M->dtype != dtypeOf<T>()) {
+		setError("precond_amg_candidates: not created with candidates, or the other dtype");
+		return SMM_HIP_ERR_INVALID;
+	}
+	if (level < 0 || static_cast<size_t>(level) >= G->lv.size()) {
+		setError("precond_amg_candidates: level %d of %zu", level, G->lv.size());
+		return SMM_HIP_ERR_INVALID;
+	}
+	const smm_amg_level& L = G->lv[static_cast<size_t>(level)];
+	if (count > static_cast<size_t>(L.n) * static_cast<size_t>(G->k) || (count && !b_l)) {
+		setError("precond_amg_candidates: level %d has %d x %d values", level, L.n, G->k);
+		return SMM_HIP_ERR_INVALID;
+	}
+	if (k) *k = G->k;
+	if (dropped) *dropped = L.dropped;
+	if (t_l) *t_l = L.Tm;
+	SMM_TRY(ensureInit());
+	hipStream_t s = libStream();
+	if (count) SMM_HIP_TRY(hipMemcpyAsync(b_l, L.d_B, count * sizeof(T), hipMemcpyDeviceToHost, s));
+	SMM_HIP_TRY(hipStreamSynchronize(s));
+	return SMM_HIP_OK;
+}
+
+extern "C" {
+
+int smm_hip_precond_create_amg(const smm_hip_csr* a, double theta, int max_levels, int coarse_rows, int smooth_degree, double eig_ratio, smm_hip_precond** out) {
+	if (!a || !out) {
+		setError("precond_create_amg: null argument");
+		return SMM_HIP_ERR_INVALID;
+	}
+	*out = nullptr;
+	SMM_TRY(amgCheckParameters(a, theta, max_levels, coarse_rows, smooth_degree, eig_ratio));
+	SMM_TRY(ensureInit());
+	SMM_TRY(ensureCsrReady(a, nullptr, false));
+	smm_hip_precond* M = amgNewHandle(a, theta, max_levels, coarse_rows, smooth_degree, eig_ratio);
 	const int st = a->dtype == SMM_DTYPE_F32 ? amgCreateTyped<float>(a, M) : amgCreateTyped<double>(a, M);
 	if (st != SMM_HIP_OK) {
 		smm_hip_precond_destroy(M);
@@ -676,6 +1110,29 @@ int smm_hip_precond_create_amg(const smm_hip_csr* a, double theta, int max_level
 	}
 	*out = M;
 	return SMM_HIP_OK;
+}
+
+int smm_hip_precond_create_amg_candidates_f32(const smm_hip_csr* a, const float* B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows, int smooth_degree,
+                                              double eig_ratio, smm_hip_precond** out) {
+	return amgCreateWithCandidates<float>(a, B, false, nullptr, k, dofs_per_node, theta, max_levels, coarse_rows, smooth_degree, eig_ratio, out);
+}
+int smm_hip_precond_create_amg_candidates_f64(const smm_hip_csr* a, const double* B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows, int smooth_degree,
+                                              double eig_ratio, smm_hip_precond** out) {
+	return amgCreateWithCandidates<double>(a, B, false, nullptr, k, dofs_per_node, theta, max_levels, coarse_rows, smooth_degree, eig_ratio, out);
+}
+int smm_hip_precond_create_amg_candidates_dev_f32(const smm_hip_csr* a, const float* d_B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows,
+                                                  int smooth_degree, double eig_ratio, smm_hip_stream stream, smm_hip_precond** out) {
+	return amgCreateWithCandidates<float>(a, d_B, true, reinterpret_cast<hipStream_t>(stream), k, dofs_per_node, theta, max_levels, coarse_rows, smooth_degree, eig_ratio, out);
+}
+int smm_hip_precond_create_amg_candidates_dev_f64(const smm_hip_csr* a, const double* d_B, int k, int dofs_per_node, double theta, int max_levels, int coarse_rows,
+                                                  int smooth_degree, double eig_ratio, smm_hip_stream stream, smm_hip_precond** out) {
+	return amgCreateWithCandidates<double>(a, d_B, true, reinterpret_cast<hipStream_t>(stream), k, dofs_per_node, theta, max_levels, coarse_rows, smooth_degree, eig_ratio, out);
+}
+int smm_hip_precond_amg_candidates_f32(const smm_hip_precond* M, int level, float* b_l, size_t count, int* k, int* dropped, smm_hip_csr** t_l) {
+	return amgCandidatesOf<float>(M, level, b_l, count, k, dropped, t_l);
+}
+int smm_hip_precond_amg_candidates_f64(const smm_hip_precond* M, int level, double* b_l, size_t count, int* k, int* dropped, smm_hip_csr** t_l) {
+	return amgCandidatesOf<double>(M, level, b_l, count, k, dropped, t_l);
 }
 
 int smm_hip_precond_amg_refresh(smm_hip_precond* M) {

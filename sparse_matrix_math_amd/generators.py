@@ -308,6 +308,110 @@ def with_long_rows(start, positions, cols, long_rows, long_lens, seed=1, dtype=n
     return out_start.astype(np.int32), out_pos, values
 
 
+def _q1_stiffness(dim, nu):
+    """the element stiffness of the unit Q1 square (plane stress) or cube (isotropic), E = 1, 2 Gauss points per axis; the dofs are
+    ordered corner by corner (x fastest), component inside the corner"""
+    if dim == 2:
+        D = np.array([[1.0, nu, 0.0], [nu, 1.0, 0.0], [0.0, 0.0, (1.0 - nu) / 2.0]]) / (1.0 - nu * nu)
+        strain = [(0, 0), (1, 1), (0, 1)]  # eps_xx, eps_yy, gamma_xy as (component, derivative) pairs; the shear rows take both
+    else:
+        lam, mu = nu / ((1.0 + nu) * (1.0 - 2.0 * nu)), 1.0 / (2.0 * (1.0 + nu))
+        D = np.zeros((6, 6))
+        D[:3, :3] = lam
+        D[np.arange(3), np.arange(3)] = lam + 2.0 * mu
+        D[np.arange(3, 6), np.arange(3, 6)] = mu
+        strain = [(0, 0), (1, 1), (2, 2), (0, 1), (1, 2), (0, 2)]
+    corners = np.array([[(c >> a) & 1 for a in range(dim)] for c in range(1 << dim)], dtype=np.float64)
+    g = 0.5 + np.array([-0.5, 0.5]) / np.sqrt(3.0)
+    K = np.zeros((dim << dim, dim << dim))
+    for q in range(1 << dim):
+        x = np.array([g[(q >> a) & 1] for a in range(dim)])
+        shape = np.where(corners == 1.0, x, 1.0 - x)  # [corner][axis]: the 1-D factors of the corner's shape function
+        grad = np.empty((1 << dim, dim))
+        for a in range(dim):
+            f = np.where(corners[:, a] == 1.0, 1.0, -1.0)
+            for o in range(dim):
+                if o != a:
+                    f = f * shape[:, o]
+            grad[:, a] = f
+        Bm = np.zeros((len(strain), dim << dim))
+        for r, (u, v) in enumerate(strain):
+            if u == v:
+                Bm[r, u::dim] = grad[:, u]
+            else:
+                Bm[r, u::dim] = grad[:, v]
+                Bm[r, v::dim] = grad[:, u]
+        K += Bm.T @ D @ Bm / (1 << dim)
+    return (K + K.T) / 2.0  # symmetric to the bit, and so is the assembled matrix: both triangles sum the same terms in the same order
+
+
+_CLAMP = {"left": (0, 0), "right": (0, -1), "bottom": (1, 0), "top": (1, -1), "front": (2, 0), "back": (2, -1)}
+
+
+def _elasticity(cells, nu, clamp, dtype):
+    dim = len(cells)
+    dtype = np.dtype(dtype).type
+    if any(c < 1 for c in cells) or clamp not in _CLAMP or _CLAMP[clamp][0] >= dim:
+        raise ValueError(f"elasticity: {cells} cells clamped at {clamp!r}")
+    nodes = [c + 1 for c in cells]
+    grid = np.stack(np.meshgrid(*[np.arange(m) for m in nodes[::-1]], indexing="ij")[::-1], axis=-1).reshape(-1, dim)  # x fastest
+    axis, side = _CLAMP[clamp]
+    kept = grid[:, axis] != (0 if side == 0 else cells[axis])
+    number = np.cumsum(kept) - 1
+    stride = np.cumprod([1] + nodes[:-1])
+    cell = np.stack(np.meshgrid(*[np.arange(c) for c in cells[::-1]], indexing="ij")[::-1], axis=-1).reshape(-1, dim)
+    corners = np.array([[(c >> a) & 1 for a in range(dim)] for c in range(1 << dim)])
+    node = ((cell[:, None, :] + corners[None, :, :]) * stride).sum(axis=2)  # [cell][corner]
+    free = kept[node]
+    dof = (number[node][:, :, None] * dim + np.arange(dim)).reshape(len(cell), -1)
+    free = np.repeat(free, dim, axis=1)
+    K = _q1_stiffness(dim, nu)
+    n = int(kept.sum()) * dim
+    pair = free[:, :, None] & free[:, None, :]
+    keys = (dof[:, :, None] * n + dof[:, None, :])[pair]
+    vals = np.broadcast_to(K, pair.shape)[pair]
+    uniq, slot = np.unique(keys, return_inverse=True)
+    values = np.bincount(slot.reshape(-1), weights=vals, minlength=len(uniq))
+    start = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(uniq // n, minlength=n), out=start[1:])
+    return start.astype(np.int32), (uniq % n).astype(np.int32), values.astype(dtype), grid[kept].astype(np.float64)
+
+
+def elasticity2d(nx, ny, nu=0.3, clamp="left", dtype=np.float64):
+    """Plane-stress linear elasticity (E = 1, Poisson ratio nu) on nx x ny unit Q1 squares, the nodes of one edge ("left", "right",
+    "bottom", "top") clamped and removed.  Two dofs per kept node, node by node (x fastest), u_x then u_y.  Returns (start, positions,
+    values, coords): CSR with ascending columns, symmetric positive definite, and the (nodes, 2) coordinates of the kept nodes."""
+    return _elasticity([int(nx), int(ny)], float(nu), clamp, dtype)
+
+
+def elasticity3d(nx, ny, nz, nu=0.3, clamp="left", dtype=np.float64):
+    """Isotropic linear elasticity (E = 1, Poisson ratio nu) on nx x ny x nz unit Q1 bricks with 2 x 2 x 2 Gauss points, the nodes of one
+    face ("left", "right", "bottom", "top", "front", "back") clamped and removed.  Three dofs per kept node.  Returns (start, positions,
+    values, coords) as elasticity2d does, coords (nodes, 3)."""
+    return _elasticity([int(nx), int(ny), int(nz)], float(nu), clamp, dtype)
+
+
+def rigid_body_modes(coords, dtype=np.float64):
+    """The rigid body modes of the nodes `coords` ((nodes, 2) or (nodes, 3)), dofs node by node: (2 nodes, 3) -- two translations and the
+    rotation -- or (3 nodes, 6) -- three translations and the rotations about x, y and z.  The rotations turn about the centroid, so that
+    they stay well apart from the translations wherever the body lies.  The near-null space of the elasticity generators' matrices."""
+    coords = np.asarray(coords, dtype=np.float64)
+    nodes, dim = coords.shape
+    if dim not in (2, 3):
+        raise ValueError("rigid_body_modes: coords must be (nodes, 2) or (nodes, 3)")
+    c = coords - coords.mean(axis=0) if nodes else coords
+    out = np.zeros((nodes, dim, 3 if dim == 2 else 6))
+    for a in range(dim):
+        out[:, a, a] = 1.0
+    if dim == 2:
+        out[:, 0, 2], out[:, 1, 2] = -c[:, 1], c[:, 0]
+    else:
+        out[:, 1, 3], out[:, 2, 3] = -c[:, 2], c[:, 1]
+        out[:, 0, 4], out[:, 2, 4] = c[:, 2], -c[:, 0]
+        out[:, 0, 5], out[:, 1, 5] = -c[:, 1], c[:, 0]
+    return out.reshape(nodes * dim, -1).astype(dtype)
+
+
 def row_sums(start, values):
     """RHS convention of the reference's solver tests: b = row sums of A, so the exact solution is all ones
     (sumColumsPerRow, test/include/test_common.h:13-21) -- accumulated left to right in the matrix dtype."""

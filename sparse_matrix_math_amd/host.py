@@ -178,7 +178,8 @@ def profile_read_waits(reset=True):
 class Preconditioner:
     """`int apply(const T* rhs, T* x) const` (ref:1173-1235).  Created by CSRMatrix.getPreconditioner."""
 
-    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None, colors=None, power=None, sweeps=None):
+    def __init__(self, matrix, kind, block_rows=None, level_cap=None, partition=None, chebyshev=None, amg=None, colors=None, power=None, sweeps=None,
+                 candidates=None):
         self.matrix = matrix  # keeps the matrix alive (the reference holds a const CSRMatrix&)
         self.kind = SolverPreconditioner(kind)
         self._h = ctypes.c_void_p()
@@ -186,6 +187,25 @@ class Preconditioner:
             degree, bound, ratio, steps, lmin, lmax = chebyshev
             check(_lib.load().smm_hip_precond_create_chebyshev(matrix._h, int(degree), int(bound), float(ratio), int(steps), float(lmin), float(lmax),
                                                                ctypes.byref(self._h)))
+        elif candidates is not None:  # (B, dofs_per_node, stream) + amg: AMG with near-null-space candidates
+            B, dofs_per_node, stream = candidates
+            theta, max_levels, coarse_rows, smooth_degree, ratio = amg
+            rest = (int(dofs_per_node), float(theta), int(max_levels), int(coarse_rows), int(smooth_degree), float(ratio))
+            if hasattr(B, "data_ptr"):  # a device tensor (n, k) with strides (1, n) -- e.g. the transpose of a contiguous (k, n) one --, or (n,)
+                shape, stride = tuple(B.shape), tuple(B.stride())
+                if not (len(shape) == 1 or (len(shape) == 2 and (shape[1] == 1 or stride[1] == shape[0]) and (shape[0] <= 1 or stride[0] == 1))):
+                    raise TypeError("candidates on the device must be column-major: shape (n, k) with strides (1, n)")
+                if shape[0] != matrix.rows or _SUFFIX.get(np.dtype(str(B.dtype).replace("torch.", ""))) != matrix._suf:
+                    raise ValueError(f"candidates must have {matrix.rows} rows and the matrix dtype")
+                k = 1 if len(shape) == 1 else shape[1]
+                check(_fn("smm_hip_precond_create_amg_candidates_dev", matrix._suf)(matrix._h, _dptr(B), k, *rest, _dptr(stream), ctypes.byref(self._h)))
+            else:
+                B = np.asarray(B)
+                B = B.reshape(-1, 1) if B.ndim == 1 else B
+                if B.ndim != 2 or B.shape[0] != matrix.rows:
+                    raise ValueError(f"candidates must have {matrix.rows} rows, got {B.shape[0]}")
+                B = np.asfortranarray(B, dtype=matrix.dtype)
+                check(_fn("smm_hip_precond_create_amg_candidates", matrix._suf)(matrix._h, B.ctypes.data_as(ctypes.c_void_p), B.shape[1], *rest, ctypes.byref(self._h)))
         elif amg is not None:  # (theta, max_levels, coarse_rows, smooth_degree, eig_ratio): AMG with chosen parameters
             theta, max_levels, coarse_rows, smooth_degree, ratio = amg
             check(_lib.load().smm_hip_precond_create_amg(matrix._h, float(theta), int(max_levels), int(coarse_rows), int(smooth_degree), float(ratio), ctypes.byref(self._h)))
@@ -301,6 +321,24 @@ class Preconditioner:
         out = np.empty((n, n), dtype=self.matrix.dtype)
         check(_fn("smm_hip_precond_amg_coarse_inverse", self.matrix._suf)(self._h, _host(out, self.matrix.dtype, "out"), n * n))
         return out
+
+    def amg_candidates(self, level):
+        """AMG created with candidates: {B: B_l of level `level` (n_l, k), dropped: the columns of T_l with no entries (the coarse dofs
+        that became identity rows), T: T_l as a CSRMatrix this preconditioner owns (None on the coarsest level)}"""
+        info = self.amg_info()
+        if not 0 <= int(level) < info["levels"]:
+            raise ValueError(f"level {level} of {info['levels']}")
+        fn = _fn("smm_hip_precond_amg_candidates", self.matrix._suf)
+        k, dropped, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_void_p()
+        check(fn(self._h, int(level), ctypes.c_void_p(0), 0, ctypes.byref(k), ctypes.byref(dropped), ctypes.byref(t)))
+        B = np.empty((info["rows"][int(level)], k.value), dtype=self.matrix.dtype, order="F")
+        check(fn(self._h, int(level), B.ctypes.data_as(ctypes.c_void_p), B.size, None, None, None))
+        T = None
+        if t:
+            T = CSRMatrix._adopt(t, self.matrix.dtype)
+            T._borrowed = True
+            T._keep = self
+        return {"B": B, "dropped": dropped.value, "T": T}
 
     def amg_refresh(self):
         """AMG: keep every aggregate and pattern, redo the values from the matrix's present values (after a value edit).  Synchronous."""
@@ -897,14 +935,26 @@ class CSRMatrix:
         check(_fn(name, self._suf)(self._h, int(op), _dptr(d_lhs), _dptr(d_x), _dptr(d_out), int(dot_mode), _dptr(d_w1), _dptr(d_partials), _dptr(stream)))
 
     def getPreconditioner(self, kind, block_rows=None, level_cap=None, partition=None, degree=None, bound=None, eig_ratio=None, power_steps=None,
-                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None, colors=None, power=None, sweeps=None):
+                          lambda_min=None, lambda_max=None, theta=None, max_levels=None, coarse_rows=None, smooth_degree=None, colors=None, power=None, sweeps=None,
+                          candidates=None, dofs_per_node=None, stream=None):
         """ref:1643-1651.  kind: a SolverPreconditioner or its name ("CHEBYSHEV").  block_rows / level_cap / partition: BLOCK_ kinds only;
         degree (3) / bound ("GERSHGORIN", "POWER", "USER" or a CHEB_BOUND_* code) / eig_ratio (30) / power_steps (10) / lambda_min /
         lambda_max (USER): CHEBYSHEV only; theta (0.08) / max_levels (10) / coarse_rows (256) / smooth_degree (2) and eig_ratio (30): AMG only.
         colors (one per row; None = CSRMatrix.color's): MULTICOLOR_ kinds only; power (1 .. 4; 1): FSAI / SPAI only;
-        sweeps (an int, or a (lower, upper) pair; 1 .. 1024; 3): JSWEEP_ kinds only.  None = the default."""
+        sweeps (an int, or a (lower, upper) pair; 1 .. 1024; 3): JSWEEP_ kinds only.  None = the default.
+        candidates (AMG only): the near-null space B, (n, k) with 1 <= k <= 6 -- a numpy array, or a column-major device tensor in use on
+        `stream` --, with dofs_per_node (1 .. 4; 1) rows per node: smoothed aggregation for vector-valued problems, e.g.
+        generators.rigid_body_modes(coords) for elasticity.  None: the scalar hierarchy, as always."""
         if isinstance(kind, str):
             kind = SolverPreconditioner[kind]
+        if candidates is not None or dofs_per_node is not None:
+            if SolverPreconditioner(kind) != SolverPreconditioner.AMG or candidates is None:
+                raise ValueError("candidates / dofs_per_node belong to the AMG preconditioner, and dofs_per_node needs candidates")
+            if any(v is not None for v in (block_rows, level_cap, partition, degree, bound, power_steps, lambda_min, lambda_max, colors, power, sweeps)):
+                raise ValueError("the AMG preconditioner takes theta / max_levels / coarse_rows / smooth_degree / eig_ratio only")
+            return Preconditioner(self, kind, candidates=(candidates, 1 if dofs_per_node is None else dofs_per_node, stream),
+                                  amg=(0.08 if theta is None else theta, 10 if max_levels is None else max_levels, 256 if coarse_rows is None else coarse_rows,
+                                       2 if smooth_degree is None else smooth_degree, 30.0 if eig_ratio is None else eig_ratio))
         if sweeps is not None:
             if SolverPreconditioner(kind) not in _JSWEEP_BASE:
                 raise ValueError("sweeps belongs to the JSWEEP_ preconditioners")
