@@ -31,17 +31,14 @@
 //     fill / numeric (nnz_a + nnz_b)(s + 4) read plus the probes of the searches (LDS or cache), nnz_c (s + 4) written (create) or
 //     nnz_c s (into, plus nnz_c 4 of c's columns read).
 #include <climits>
-#include <memory>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 
 namespace smm {
 namespace {
 
-constexpr int ATPB = 256;
+constexpr int ATPB = BUILD_TPB;
 constexpr int ADD_SEG = 1024;  // columns of a searched row segment a workgroup stages in LDS; longer segments are searched in global memory
 
 // the words of a call
@@ -52,8 +49,6 @@ constexpr int W_MISS_ROW = 7;   // + operand (0, 1): the smallest row of the ope
 constexpr int N_WORDS = 9;
 constexpr int NO_ROW = INT_MAX;
 constexpr int BAD_START = 1, BAD_COL = 2, BAD_ORDER = 4;
-
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + ATPB - 1) / ATPB)); }
 
 __global__ void wordsInitKernel(int* words) {
 	if (blockIdx.x == 0 && threadIdx.x < N_WORDS) words[threadIdx.x] = threadIdx.x == W_BITS ? 0 : NO_ROW;
@@ -263,13 +258,6 @@ __global__ __launch_bounds__(ATPB) void coveredKernel(const int* __restrict__ ra
 	if (!hit) atomicMin(&words[W_MISS_ROW + operand], row);
 }
 
-struct CsrDeleter {
-	void operator()(smm_hip_csr* m) const { smm_hip_csr_destroy(m); }
-};
-
-template <typename T>
-int allocArray(T** p, size_t count) { return devAlloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)); }
-
 int enqueueBlockRows(const smm_hip_csr* m, DevBuf<int>& ranges, hipStream_t s) {
 	const int blocks = gridOf(m->nnz);
 	SMM_TRY(ranges.alloc(2 * static_cast<size_t>(blocks)));
@@ -327,12 +315,8 @@ int addCreateTyped(const smm_hip_csr* a, T alpha, const smm_hip_csr* b, T beta, 
 	wordsInitKernel<<<1, 64, 0, s>>>(d_words.p);
 	const smm_hip_csr* ops[2] = {a, b};
 	SMM_TRY(checkOperands(what, ops, 2, d_words, s));
-	std::unique_ptr<smm_hip_csr, CsrDeleter> c(new smm_hip_csr());
-	c->rows = m;
-	c->cols = a->cols;
-	c->dtype = a->dtype;
-	c->owns = true;
-	SMM_TRY(allocArray(&c->d_start, static_cast<size_t>(m) + 1));
+	OwnedCsr c;
+	SMM_TRY(newOwnedCsr(m, a->cols, a->dtype, &c));
 	const int nnzA = a->nnz, nnzB = b->nnz;
 	DevBuf<int> rangesA, rangesB, N, where;  // N[nnzB + 1]: isNew[] before the scan (the last word 0), the new entries before q after it
 	int newTotal = 0;
@@ -343,11 +327,7 @@ int addCreateTyped(const smm_hip_csr* a, T alpha, const smm_hip_csr* b, T beta, 
 		SMM_TRY(enqueueBlockRows(b, rangesB, s));
 		symbolicKernel<<<gridOf(nnzB), ATPB, 0, s>>>(rangesB.p, nnzB, a->d_start, a->d_positions, b->d_start, b->d_positions, N.p, where.p);
 		SMM_HIP_TRY(hipGetLastError());
-		size_t tempBytes = 0;
-		SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, N.p, N.p, 0, static_cast<size_t>(nnzB) + 1, rocprim::plus<int>(), s));
-		DevBuf<unsigned char> temp;
-		SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-		SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, N.p, N.p, 0, static_cast<size_t>(nnzB) + 1, rocprim::plus<int>(), s));
+		SMM_TRY(scanExclusive(N.p, N.p, static_cast<size_t>(nnzB) + 1, s));
 		SMM_HIP_TRY(hipMemcpyAsync(&newTotal, N.p + nnzB, sizeof(int), hipMemcpyDeviceToHost, s));
 		SMM_HIP_TRY(hipStreamSynchronize(s));
 	}
@@ -357,8 +337,7 @@ int addCreateTyped(const smm_hip_csr* a, T alpha, const smm_hip_csr* b, T beta, 
 		return SMM_HIP_ERR_INVALID;
 	}
 	startKernel<<<gridOf(m + 1LL), ATPB, 0, s>>>(m, a->d_start, b->d_start, nnzB > 0 ? N.p : nullptr, c->d_start);
-	SMM_TRY(allocArray(&c->d_positions, static_cast<size_t>(nnzC)));
-	SMM_TRY(devAlloc(&c->d_values, static_cast<size_t>(nnzC ? nnzC : 1) * sizeof(T)));
+	SMM_TRY(allocCsrEntries(c.get(), nnzC, false));
 	T* cVal = static_cast<T*>(c->d_values);
 	if (nnzA > 0) {
 		SMM_TRY(enqueueBlockRows(a, rangesA, s));
@@ -423,15 +402,7 @@ int addIntoTyped(smm_hip_csr* c, const smm_hip_csr* a, T alpha, const smm_hip_cs
 		setError("%s: row %d of %s holds an entry that c does not store", what, miss[op], op == 0 ? "a" : "b");
 		return SMM_HIP_ERR_INVALID;
 	}
-	if (c->nnz > 0) {
-		if (c->owns) {  // the scratch becomes the values array; the old one goes back to the allocator behind the work queued on it
-			void* old = c->d_values;
-			c->d_values = scratch.detach();
-			devFree(old);
-		} else {
-			SMM_HIP_TRY(hipMemcpyAsync(c->d_values, scratch.p, static_cast<size_t>(c->nnz) * sizeof(T), hipMemcpyDeviceToDevice, s));
-		}
-	}
+	SMM_TRY(adoptValues(c, scratch, s));
 	return csrValuesEdited(c, s);
 }
 

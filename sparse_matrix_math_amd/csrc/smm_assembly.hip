@@ -12,12 +12,8 @@
 // A refill writes the matrix's values[] and then takes the path of every other value edit (csrValuesEdited, smm_csr_update.hip).
 #include <algorithm>
 #include <climits>
-#include <memory>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "smm_internal.h"
+#include "smm_csr_build.h"
 
 struct smm_hip_assembly {
 	int rows = 0, cols = 0, nnz = 0;
@@ -35,16 +31,8 @@ struct smm_hip_assembly {
 namespace smm {
 namespace {
 
-constexpr int ATPB = 256;
+constexpr int ATPB = BUILD_TPB;
 constexpr unsigned long long NO_BAD = ~0ULL;
-
-int bitsFor(int count) {  // bits that hold 0 .. count - 1
-	int b = 0;
-	while (b < 31 && (static_cast<long long>(count) - 1) >> b) ++b;
-	return b;
-}
-
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + ATPB - 1) / ATPB)); }
 
 // one lane per triplet: key = row above col in colBits + rowBits bits, seq = list index; the smallest list index of an entry outside
 // [0, rows) x [0, cols) lands in *firstBad (its key is not used: the caller stops there)
@@ -156,9 +144,6 @@ struct PlanDeleter {
 	void operator()(smm_hip_assembly* p) const { planFree(p); }
 };
 
-template <typename T>
-int allocInts(T** p, size_t count) { return devAlloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)); }
-
 // the symbolic pass over index arrays in device memory; synchronises `s` (the range verdict and nnz are needed on the host)
 int planOnDevice(int rows, int cols, long long n, const int* d_rows, const int* d_cols, hipStream_t s, smm_hip_assembly** out) {
 	SetupTrace trace("assembly: symbolic pass");
@@ -169,10 +154,10 @@ int planOnDevice(int rows, int cols, long long n, const int* d_rows, const int* 
 	p->n = n;
 	p->stamp = nextStamp.fetch_add(1, std::memory_order_relaxed);
 	p->firstActiveStart = rows;
-	SMM_TRY(allocInts(&p->d_start, static_cast<size_t>(rows) + 1));
+	SMM_TRY(allocArray(&p->d_start, static_cast<size_t>(rows) + 1));
 	if (n == 0) {
-		SMM_TRY(allocInts(&p->d_positions, 0));
-		SMM_TRY(allocInts(&p->d_perm, 0));
+		SMM_TRY(allocArray(&p->d_positions, 0));
+		SMM_TRY(allocArray(&p->d_perm, 0));
 		SMM_HIP_TRY(hipMemsetAsync(p->d_start, 0, (static_cast<size_t>(rows) + 1) * sizeof(int), s));
 		SMM_HIP_TRY(hipStreamSynchronize(s));
 		*out = p.release();
@@ -196,33 +181,20 @@ int planOnDevice(int rows, int cols, long long n, const int* d_rows, const int* 
 		return SMM_HIP_ERR_INVALID;
 	}
 	SMM_TRY(keyOut.alloc(cnt));
-	SMM_TRY(allocInts(&p->d_perm, cnt));
-	{
-		const unsigned endBit = static_cast<unsigned>(std::max(1, colBits + rowBits));
-		size_t tempBytes = 0;
-		SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keyIn.p, keyOut.p, seqIn.p, p->d_perm, cnt, 0u, endBit, s));
-		DevBuf<unsigned char> temp;
-		SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-		SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keyIn.p, keyOut.p, seqIn.p, p->d_perm, cnt, 0u, endBit, s));
-	}
+	SMM_TRY(allocArray(&p->d_perm, cnt));
+	SMM_TRY(sortPairs(keyIn.p, keyOut.p, seqIn.p, p->d_perm, cnt, static_cast<unsigned>(std::max(1, colBits + rowBits)), s));
 	keyIn.release();  // (stream-ordered: the allocator hands a block out again only behind the work that was using it)
 	seqIn.release();
 	SMM_TRY(runIdx.alloc(cnt));
 	runHeadKernel<<<gridOf(n), ATPB, 0, s>>>(n, keyOut, runIdx);
 	SMM_HIP_TRY(hipGetLastError());
-	{
-		size_t tempBytes = 0;
-		SMM_HIP_TRY(rocprim::inclusive_scan(nullptr, tempBytes, runIdx.p, runIdx.p, cnt, rocprim::plus<int>(), s));
-		DevBuf<unsigned char> temp;
-		SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-		SMM_HIP_TRY(rocprim::inclusive_scan(temp.p, tempBytes, runIdx.p, runIdx.p, cnt, rocprim::plus<int>(), s));
-	}
+	SMM_TRY(scanInclusive(runIdx.p, runIdx.p, cnt, s));
 	int nnz = 0;
 	SMM_HIP_TRY(hipMemcpyAsync(&nnz, runIdx.p + (cnt - 1), sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));
 	p->nnz = nnz;  // (1 .. n, and n <= 2^31 - 1: the library's 32-bit limit holds by construction)
-	SMM_TRY(allocInts(&p->d_positions, static_cast<size_t>(nnz)));
-	if (nnz != n) SMM_TRY(allocInts(&p->d_run_begin, static_cast<size_t>(nnz) + 1));
+	SMM_TRY(allocArray(&p->d_positions, static_cast<size_t>(nnz)));
+	if (nnz != n) SMM_TRY(allocArray(&p->d_run_begin, static_cast<size_t>(nnz) + 1));
 	SMM_TRY(d_info.alloc(2));
 	SMM_HIP_TRY(hipMemsetAsync(d_info, 0, 2 * sizeof(int), s));
 	runScatterKernel<<<gridOf(n), ATPB, 0, s>>>(n, nnz, colBits, keyOut, runIdx, p->d_positions, p->d_run_begin);
@@ -288,36 +260,21 @@ int csrFromPlan(const smm_hip_assembly* p, const T* vals, bool onDevice, hipStre
 		SMM_TRY(hostToDev(staged, vals, sizeof(T) * static_cast<size_t>(p->n), s));
 		vals = staged;
 	}
-	auto* m = new smm_hip_csr();
-	m->rows = p->rows;
-	m->cols = p->cols;
-	m->dtype = dtypeOf<T>();
-	m->owns = true;
-	const size_t nnz = static_cast<size_t>(p->nnz), startBytes = (static_cast<size_t>(p->rows) + 1) * sizeof(int);
-	int st = devAlloc(reinterpret_cast<void**>(&m->d_start), startBytes);
-	if (st == SMM_HIP_OK) st = devAlloc(reinterpret_cast<void**>(&m->d_positions), (nnz ? nnz : 1) * sizeof(int));
-	if (st == SMM_HIP_OK) st = devAlloc(&m->d_values, (nnz ? nnz : 1) * sizeof(T));
-	if (st == SMM_HIP_OK) {
-		hipError_t e = hipMemcpyAsync(m->d_start, p->d_start, startBytes, hipMemcpyDeviceToDevice, s);
-		if (e == hipSuccess && nnz) e = hipMemcpyAsync(m->d_positions, p->d_positions, nnz * sizeof(int), hipMemcpyDeviceToDevice, s);
-		if (e != hipSuccess) st = hipFail(e, "assembly: pattern copy", __FILE__, __LINE__);
-	}
-	if (st == SMM_HIP_OK) st = launchAssemble<T>(p, vals, static_cast<T*>(m->d_values), false, s);
-	if (st == SMM_HIP_OK && !onDevice) {
-		const hipError_t e = hipStreamSynchronize(s);
-		if (e != hipSuccess) st = hipFail(e, "assembly: synchronize", __FILE__, __LINE__);
-	}
-	if (st != SMM_HIP_OK) {
-		smm_hip_csr_destroy(m);
-		return st;
-	}
+	OwnedCsr m;
+	SMM_TRY(newOwnedCsr(p->rows, p->cols, dtypeOf<T>(), &m));
+	SMM_TRY(allocCsrEntries(m.get(), p->nnz, false));
+	const size_t nnz = static_cast<size_t>(p->nnz);
+	SMM_HIP_TRY(hipMemcpyAsync(m->d_start, p->d_start, (static_cast<size_t>(p->rows) + 1) * sizeof(int), hipMemcpyDeviceToDevice, s));
+	if (nnz) SMM_HIP_TRY(hipMemcpyAsync(m->d_positions, p->d_positions, nnz * sizeof(int), hipMemcpyDeviceToDevice, s));
+	SMM_TRY(launchAssemble<T>(p, vals, static_cast<T*>(m->d_values), false, s));
+	if (!onDevice) SMM_HIP_TRY(hipStreamSynchronize(s));
 	m->nnz = p->nnz;
 	m->firstActiveStart = p->firstActiveStart;
 	m->stream_mid_len = p->midLen;
 	m->assemblyStamp = p->stamp;
-	chooseSpmvConfig(m);
+	chooseSpmvConfig(m.get());
 	m->ready = true;
-	*out = m;
+	*out = m.release();
 	return SMM_HIP_OK;
 }
 

@@ -15,45 +15,13 @@
 //     values[map[k]] as raw words.  Keys are distinct, so the result depends on the matrix and the permutation alone.
 //   refresh (smm_hip_csr_permute_refresh_*): values_B[k] = a.values[map[k]], asynchronous, then the path of every value edit.
 #include <algorithm>
-#include <memory>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "smm_internal.h"
+#include "smm_csr_build.h"
 
 namespace smm {
 namespace {
 
-constexpr int CTPB = 256;
-
-int bitsFor(int count) {  // bits that hold 0 .. count - 1
-	int b = 0;
-	while (b < 31 && (static_cast<long long>(count) - 1) >> b) ++b;
-	return b;
-}
-
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + CTPB - 1) / CTPB)); }
-
-template <typename T>
-struct Word;
-template <>
-struct Word<float> {
-	using type = unsigned;
-};
-template <>
-struct Word<double> {
-	using type = unsigned long long;
-};
-
-struct CsrDeleter {
-	void operator()(smm_hip_csr* m) const { smm_hip_csr_destroy(m); }
-};
-
-int readFlag(const int* d_flag, hipStream_t s, int* flag) {
-	SMM_HIP_TRY(hipMemcpyAsync(flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
-	return SMM_HIP_OK;
-}
+constexpr int CTPB = BUILD_TPB;
 
 // one step of the splitmix64 generator from the state x: the golden-ratio increment, then the finalizer
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
@@ -63,12 +31,6 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
 	return z ^ (z >> 31);
 }
 __device__ __forceinline__ unsigned long long colorKey(int i) { return splitmix64(static_cast<unsigned long long>(i) + 1ULL); }
-
-__global__ __launch_bounds__(CTPB) void intsDifferKernel(long long n, const int* __restrict__ a, const int* __restrict__ b, int* differs) {
-	bool d = false;
-	for (long long i = static_cast<long long>(blockIdx.x) * CTPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * CTPB) d |= a[i] != b[i];
-	if (d) *differs = 1;  // (every writer writes the same word)
-}
 
 // is vertex i beaten by an uncoloured neighbour among positions[b .. e)?  (columns were checked against [0, rows) when the transpose was built)
 __device__ __forceinline__ bool beaten(int i, unsigned long long key, const int* __restrict__ positions, int b, int e, const int* __restrict__ colors) {
@@ -145,23 +107,6 @@ __global__ __launch_bounds__(CTPB) void invertPermKernel(int n, const int* __res
 	if (atomicExch(inv + p, static_cast<int>(i)) != -1) *bad = 1;
 }
 
-// the row that holds entry e: the last r in [0, rows) with start[r] <= e (rows >= 1)
-__device__ __forceinline__ int rowOfEntry(int rows, const int* __restrict__ start, int e) {
-	int lo = 0, hi = rows - 1;
-	while (lo < hi) {
-		const int mid = lo + ((hi - lo + 1) >> 1);
-		if (start[mid] <= e) lo = mid;
-		else hi = mid - 1;
-	}
-	return lo;
-}
-
-__global__ __launch_bounds__(CTPB) void startCheckKernel(int rows, const int* __restrict__ start, int* bad) {
-	const long long r = static_cast<long long>(blockIdx.x) * CTPB + threadIdx.x;
-	if (r >= rows) return;
-	if (start[r] > start[r + 1] || (r == 0 && start[0] != 0)) *bad = 1;
-}
-
 __global__ __launch_bounds__(CTPB) void permKeyKernel(int nnz, int n, const int* __restrict__ start, const int* __restrict__ positions, const int* __restrict__ inv,
                                                       unsigned long long* __restrict__ key, int* __restrict__ seq, int* bad) {
 	const long long e = static_cast<long long>(blockIdx.x) * CTPB + threadIdx.x;
@@ -222,16 +167,10 @@ int permuteTyped(const smm_hip_csr* a, const int* d_perm, hipStream_t s, smm_hip
 		setError("csr_permute: start[rows] is negative");
 		return SMM_HIP_ERR_INVALID;
 	}
-	std::unique_ptr<smm_hip_csr, CsrDeleter> b(new smm_hip_csr());
-	b->rows = n;
-	b->cols = n;
-	b->dtype = a->dtype;
-	b->owns = true;
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&b->d_start), (static_cast<size_t>(n) + 1) * sizeof(int)));
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&b->d_positions), static_cast<size_t>(std::max(1, nnz)) * sizeof(int)));
-	SMM_TRY(devAlloc(&b->d_values, static_cast<size_t>(std::max(1, nnz)) * sizeof(T)));
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&b->d_tperm), static_cast<size_t>(std::max(1, nnz)) * sizeof(int)));
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&b->d_pperm), static_cast<size_t>(std::max(1, n)) * sizeof(int)));
+	OwnedCsr b;
+	SMM_TRY(newOwnedCsr(n, n, a->dtype, &b));
+	SMM_TRY(allocCsrEntries(b.get(), nnz, true));
+	SMM_TRY(allocArray(&b->d_pperm, static_cast<size_t>(n)));
 	DevBuf<int> d_bad, inv;
 	SMM_TRY(d_bad.alloc(1));
 	SMM_TRY(inv.alloc(std::max(1, n)));
@@ -263,11 +202,7 @@ int permuteTyped(const smm_hip_csr* a, const int* d_perm, hipStream_t s, smm_hip
 			return SMM_HIP_ERR_INVALID;
 		}
 		const unsigned endBit = 32u + static_cast<unsigned>(std::max(1, bitsFor(n)));
-		size_t tempBytes = 0;
-		SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keyIn.p, keyOut.p, seqIn.p, b->d_tperm, static_cast<size_t>(nnz), 0u, endBit, s));
-		DevBuf<unsigned char> temp;
-		SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-		SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keyIn.p, keyOut.p, seqIn.p, b->d_tperm, static_cast<size_t>(nnz), 0u, endBit, s));
+		SMM_TRY(sortPairs(keyIn.p, keyOut.p, seqIn.p, b->d_tperm, static_cast<size_t>(nnz), endBit, s));
 		permStartKernel<<<gridOf(n + 1LL), CTPB, 0, s>>>(n, nnz, keyOut, b->d_start);
 		permGatherKernel<W><<<gridOf(nnz), CTPB, 0, s>>>(nnz, b->d_tperm, keyOut, static_cast<const W*>(a->d_values), b->d_positions, static_cast<W*>(b->d_values));
 		SMM_HIP_TRY(hipGetLastError());
@@ -291,22 +226,11 @@ int permuteRefreshTyped(smm_hip_csr* b, const smm_hip_csr* a, hipStream_t s) {
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int nnz = b->nnz;
-	int verdict = csrPatternVerdict(a, b->permuteOf);
-	if (verdict < 0) {
-		verdict = 1;
-		if (nnz > 0) {
-			DevBuf<int> d_diff;
-			SMM_TRY(d_diff.alloc(1));
-			SMM_HIP_TRY(hipMemsetAsync(d_diff, 0, sizeof(int), s));
-			permSourceCheckKernel<<<gridOf(nnz), CTPB, 0, s>>>(nnz, b->rows, b->d_start, b->d_positions, b->d_tperm, b->d_pperm, a->d_start, a->d_positions, d_diff);
-			SMM_HIP_TRY(hipGetLastError());
-			int diff = 0;
-			SMM_TRY(readFlag(d_diff, s, &diff));
-			verdict = diff ? 0 : 1;
-		}
-		csrPatternRecord(a, b->permuteOf, verdict == 1);
-	}
-	if (verdict != 1) {
+	bool same = false;
+	SMM_TRY(refreshVerdict(a, b->permuteOf, s, [&](int* d_diff) {
+		permSourceCheckKernel<<<gridOf(nnz), CTPB, 0, s>>>(nnz, b->rows, b->d_start, b->d_positions, b->d_tperm, b->d_pperm, a->d_start, a->d_positions, d_diff);
+	}, &same));
+	if (!same) {
 		setError("csr_permute_refresh: the matrix has another nonzero pattern than the permutation's source");
 		return SMM_HIP_ERR_INVALID;
 	}
@@ -338,7 +262,7 @@ int csrColor(const smm_hip_csr* a, hipStream_t s, int* d_colors, int* ncolors) {
 	// the in-neighbours: the transpose, dropped again when its pattern is A's own (it also checks start[] and the columns)
 	smm_hip_csr* raw = nullptr;
 	SMM_TRY(csrTransposeCreate(a, s, &raw));
-	std::unique_ptr<smm_hip_csr, CsrDeleter> t(raw);
+	OwnedCsr t(raw);
 	DevBuf<int> words;  // [0] the patterns differ, [1] uncoloured vertices left, [2] the largest colour
 	DevBuf<unsigned char> pick;
 	SMM_TRY(words.alloc(4));

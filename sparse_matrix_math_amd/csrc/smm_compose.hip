@@ -26,33 +26,17 @@
 //   scale: one lane per stored entry finds its row by a binary search of start[] (only when there is a row vector) and writes
 //     (r_i v) c_j: two roundings in this order (-ffp-contract=off).  Then the path of every value edit (csrValuesEdited).
 #include <climits>
-#include <memory>
 
-#include <rocprim/device/device_scan.hpp>
-
-#include "smm_internal.h"
+#include "smm_csr_build.h"
 
 namespace smm {
 namespace {
 
-constexpr int CTPB = 256;
+constexpr int CTPB = BUILD_TPB;
 constexpr int MAX_SLOTS = 64;
 constexpr int OWN_CHUNK = 8;         // entries per lane a group of L < 64 lanes copies itself; the rest of the segment goes to the whole wavefront
 constexpr int MAX_LANES_LOG = 16;    // at most 65536 lanes per row
 constexpr int NO_POS = INT_MAX;
-
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + CTPB - 1) / CTPB)); }
-
-template <typename T>
-struct Word;
-template <>
-struct Word<float> {
-	using type = unsigned;
-};
-template <>
-struct Word<double> {
-	using type = unsigned long long;
-};
 
 __device__ __forceinline__ float fromWord(unsigned w) { return __uint_as_float(w); }
 __device__ __forceinline__ double fromWord(unsigned long long w) { return __longlong_as_double(static_cast<long long>(w)); }
@@ -232,11 +216,6 @@ __global__ __launch_bounds__(CTPB) void subKernel(int nr, const int* __restrict_
 	}
 }
 
-__global__ __launch_bounds__(CTPB) void narrowKernel(long long n, const long long* __restrict__ in, int* __restrict__ out) {
-	const long long i = static_cast<long long>(blockIdx.x) * CTPB + threadIdx.x;
-	if (i < n) out[i] = static_cast<int>(in[i]);
-}
-
 // (map[] holds indices below the source's entry count, which the caller has compared with the matrix it passes)
 template <typename W>
 __global__ __launch_bounds__(CTPB) void gatherKernel(int nnz, const int* __restrict__ map, const W* __restrict__ values, W* __restrict__ out) {
@@ -269,17 +248,6 @@ __global__ __launch_bounds__(CTPB) void diagonalKernel(int n, int nnz, const int
 	if (threadIdx.x == 0 && missing && blockMissing) atomicAdd(missing, blockMissing);
 }
 
-// the last r in [0, rows) with start[r] <= e (rows >= 1); reads start[0 .. rows) only
-__device__ __forceinline__ int rowOfEntry(int rows, const int* __restrict__ start, int e) {
-	int lo = 0, hi = rows - 1;
-	while (lo < hi) {
-		const int mid = lo + ((hi - lo + 1) >> 1);
-		if (start[mid] <= e) lo = mid;
-		else hi = mid - 1;
-	}
-	return lo;
-}
-
 template <typename T>
 __global__ __launch_bounds__(CTPB) void scaleKernel(int nnz, int rows, int cols, const int* __restrict__ start, const int* __restrict__ positions,
                                                     const T* __restrict__ r, const T* __restrict__ c, T* __restrict__ values) {
@@ -296,22 +264,6 @@ __global__ __launch_bounds__(CTPB) void scaleKernel(int nnz, int rows, int cols,
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-struct CsrDeleter {
-	void operator()(smm_hip_csr* m) const { smm_hip_csr_destroy(m); }
-};
-
-template <typename T>
-int allocArray(T** p, size_t count) { return devAlloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)); }
-
-int scanInts(int* d, size_t n, hipStream_t s) {
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, d, d, 0, n, rocprim::plus<int>(), s));
-	DevBuf<unsigned char> temp;
-	SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-	SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, d, d, 0, n, rocprim::plus<int>(), s));
-	return SMM_HIP_OK;
-}
-
 int lanesLogFor(long long rows, long long nnz, int cap) {
 	const long long mean = rows > 0 ? nnz / rows : 0;
 	int lg = 0;
@@ -449,20 +401,15 @@ int blockCreate(int p, int q, const smm_hip_csr* const* blocks, const T* coef, c
 	long long rows = 0, cols = 0, nnz = 0, groups = 0;
 	std::vector<int> sizes;
 	SMM_TRY(buildBlockTable<T>(what, p, q, blocks, coef, rowSizes, colSizes, s, tab.get(), &rows, &cols, &nnz, &groups, &sizes));
-	std::unique_ptr<smm_hip_csr, CsrDeleter> c(new smm_hip_csr());
-	c->rows = static_cast<int>(rows);
-	c->cols = static_cast<int>(cols);
-	c->dtype = dtypeOf<T>();
-	c->owns = true;
-	SMM_TRY(allocArray(&c->d_start, static_cast<size_t>(rows) + 1));
-	SMM_TRY(allocArray(&c->d_positions, static_cast<size_t>(nnz)));
-	SMM_TRY(devAlloc(&c->d_values, static_cast<size_t>(nnz ? nnz : 1) * sizeof(T)));
+	OwnedCsr c;
+	SMM_TRY(newOwnedCsr(static_cast<int>(rows), static_cast<int>(cols), dtypeOf<T>(), &c));
+	SMM_TRY(allocCsrEntries(c.get(), nnz, false));
 	DevBuf<BlockTable> d_tab;
 	SMM_TRY(d_tab.alloc(1));
 	SMM_TRY(hostToDev(d_tab.p, tab.get(), sizeof(BlockTable), s));
 	blockCountKernel<<<gridOf(rows + 1), CTPB, 0, s>>>(d_tab.p, c->rows, c->d_start);
 	SMM_HIP_TRY(hipGetLastError());
-	SMM_TRY(scanInts(c->d_start, static_cast<size_t>(rows) + 1, s));
+	SMM_TRY(scanExclusive(c->d_start, c->d_start, static_cast<size_t>(rows) + 1, s));
 	if (groups > 0) blockFillKernel<T><<<static_cast<int>(groups), CTPB, 0, s>>>(d_tab.p, c->d_start, c->d_positions, static_cast<W*>(c->d_values));
 	SMM_HIP_TRY(hipGetLastError());
 	c->blockSlots.assign({p, q});
@@ -555,14 +502,9 @@ int submatrixOnDevice(const char* what, const smm_hip_csr* a, const int* d_rows,
 		}
 	}
 	const int width = d_cols ? nc : c1 - c0;
-	std::unique_ptr<smm_hip_csr, CsrDeleter> c(new smm_hip_csr());
-	c->rows = nr;
-	c->cols = width;
-	c->dtype = a->dtype;
-	c->owns = true;
-	SMM_TRY(allocArray(&c->d_start, static_cast<size_t>(nr) + 1));
+	OwnedCsr c;
+	SMM_TRY(newOwnedCsr(nr, width, a->dtype, &c));
 	DevBuf<int> colMap, counts;
-	DevBuf<long long> start64;
 	if (d_cols) {
 		SMM_TRY(colMap.alloc(static_cast<size_t>(a->cols)));
 		if (a->cols > 0) SMM_HIP_TRY(hipMemsetAsync(colMap.p, 0xFF, static_cast<size_t>(a->cols) * sizeof(int), s));
@@ -572,30 +514,13 @@ int submatrixOnDevice(const char* what, const smm_hip_csr* a, const int* d_rows,
 	const int lanesLog = lanesLogFor(a->rows, a->nnz, 6);
 	const int grid = gridOf(static_cast<long long>(std::max(nr, 1)) << lanesLog);
 	SMM_TRY(counts.alloc(static_cast<size_t>(nr) + 1));
-	SMM_TRY(start64.alloc(static_cast<size_t>(nr) + 1));
 	const bool f32 = a->dtype == SMM_DTYPE_F32;
 	// (the count reads no values: one instantiation serves both element types)
 	subKernel<unsigned, false><<<grid, CTPB, 0, s>>>(nr, d_rows, r0, map, c0, c1, lanesLog, a->d_start, a->d_positions, nullptr, counts.p, nullptr, nullptr, nullptr, nullptr);
 	SMM_HIP_TRY(hipGetLastError());
-	{
-		size_t tempBytes = 0;
-		const size_t n = static_cast<size_t>(nr) + 1;
-		SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, counts.p, start64.p, 0LL, n, rocprim::plus<long long>(), s));
-		DevBuf<unsigned char> temp;
-		SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-		SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, counts.p, start64.p, 0LL, n, rocprim::plus<long long>(), s));
-	}
 	long long nnz = 0;
-	SMM_HIP_TRY(hipMemcpyAsync(&nnz, start64.p + nr, sizeof(long long), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
-	if (nnz > INT_MAX) {
-		setError("%s: the submatrix holds %lld entries, more than 2^31 - 1", what, nnz);
-		return SMM_HIP_ERR_INVALID;
-	}
-	narrowKernel<<<gridOf(nr + 1LL), CTPB, 0, s>>>(nr + 1LL, start64.p, c->d_start);
-	SMM_TRY(allocArray(&c->d_positions, static_cast<size_t>(nnz)));
-	SMM_TRY(devAlloc(&c->d_values, static_cast<size_t>(nnz ? nnz : 1) * (f32 ? 4 : 8)));
-	SMM_TRY(allocArray(&c->d_tperm, static_cast<size_t>(nnz)));
+	SMM_TRY(startsFromCounts(what, "submatrix", counts.p, nr, c.get(), &nnz, s));
+	SMM_TRY(allocCsrEntries(c.get(), nnz, true));
 	if (nnz > 0) {
 		if (f32) {
 			subKernel<unsigned, true><<<grid, CTPB, 0, s>>>(nr, d_rows, r0, map, c0, c1, lanesLog, a->d_start, a->d_positions, static_cast<const unsigned*>(a->d_values), nullptr,

@@ -12,9 +12,8 @@
 //     arrays) or is copied into them (caller-owned), as smm_hip_csr_multiply_into_* installs its result; the other conversions cannot fail
 //     and write dst's values directly.  Then the path of every value edit (csrValuesEdited).
 #include <climits>
-#include <memory>
 
-#include "smm_internal.h"
+#include "smm_csr_build.h"
 #include "smm_solver_host.h"
 
 namespace smm {
@@ -109,7 +108,6 @@ int convertAny(int srcType, int dstType, long long n, const void* src, void* dst
 	return convertLaunch(n, static_cast<const double*>(src), static_cast<double*>(dst), firstBad, s);
 }
 
-size_t elemBytes(int dtype) { return dtype == SMM_DTYPE_F32 ? sizeof(float) : sizeof(double); }
 bool narrowing(int srcType, int dstType) { return srcType == SMM_DTYPE_F64 && dstType == SMM_DTYPE_F32; }
 
 // the range word of a narrowing conversion: preset before the pass, read (the stream synchronised) after it
@@ -130,10 +128,6 @@ struct RangeWord {
 	}
 };
 
-struct CsrDeleter {
-	void operator()(smm_hip_csr* m) const { smm_hip_csr_destroy(m); }
-};
-
 int convertCreate(const smm_hip_csr* a, int dtype, hipStream_t s, smm_hip_csr** out) {
 	const char* what = "csr_convert_create";
 	SetupTrace trace("convert: create");
@@ -143,14 +137,9 @@ int convertCreate(const smm_hip_csr* a, int dtype, hipStream_t s, smm_hip_csr** 
 		setError("%s: start[rows] is negative", what);
 		return SMM_HIP_ERR_INVALID;
 	}
-	std::unique_ptr<smm_hip_csr, CsrDeleter> c(new smm_hip_csr());
-	c->rows = rows;
-	c->cols = a->cols;
-	c->dtype = dtype;
-	c->owns = true;
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&c->d_start), (static_cast<size_t>(rows) + 1) * sizeof(int)));
-	SMM_TRY(devAlloc(reinterpret_cast<void**>(&c->d_positions), static_cast<size_t>(nnz ? nnz : 1) * sizeof(int)));
-	SMM_TRY(devAlloc(&c->d_values, static_cast<size_t>(nnz ? nnz : 1) * elemBytes(dtype)));
+	OwnedCsr c;
+	SMM_TRY(newOwnedCsr(rows, a->cols, dtype, &c));
+	SMM_TRY(allocCsrEntries(c.get(), nnz, false));
 	RangeWord range;
 	SyncOnExit drain{s};  // (an error return must not release the new arrays under the copies queued into them)
 	SMM_HIP_TRY(hipMemcpyAsync(c->d_start, a->d_start, (static_cast<size_t>(rows) + 1) * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -183,13 +172,7 @@ int convertRefresh(smm_hip_csr* dst, const smm_hip_csr* src, hipStream_t s) {
 		SMM_TRY(convertAny(src->dtype, dst->dtype, nnz, src->d_values, scratch.p, range.d.p, s));
 		SMM_TRY(range.read(s, what));
 		drain.armed = false;
-		if (dst->owns) {  // the scratch becomes the values array; the old one goes back to the allocator behind the work queued on it
-			void* old = dst->d_values;
-			dst->d_values = scratch.detach();
-			devFree(old);
-		} else {
-			SMM_HIP_TRY(hipMemcpyAsync(dst->d_values, scratch.p, static_cast<size_t>(nnz) * sizeof(float), hipMemcpyDeviceToDevice, s));
-		}
+		SMM_TRY(adoptValues(dst, scratch, s));
 	} else if (nnz > 0) {
 		SMM_TRY(convertAny(src->dtype, dst->dtype, nnz, src->d_values, dst->d_values, nullptr, s));
 	}

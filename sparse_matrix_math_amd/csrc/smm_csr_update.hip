@@ -14,9 +14,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "smm_internal.h"
+#include "smm_csr_build.h"
 
 namespace smm {
 namespace {
@@ -402,13 +400,9 @@ int updateEntriesOnDevice(smm_hip_csr* m, int n, const int* d_rows, const int* d
 	SMM_TRY(seqOut.alloc(n));
 	findEntriesKernel<<<gridFor(n), UTPB, 0, s>>>(n, m->rows, m->cols, m->nnz, m->d_start, m->d_positions, d_rows, d_cols, keyIn, seqIn, d_found);
 	SMM_HIP_TRY(hipGetLastError());
-	int endBit = 1;  // keys run over [0, nnz]: only their low bits are sorted
+	unsigned endBit = 1;  // keys run over [0, nnz]: only their low bits are sorted
 	while (endBit < 32 && (static_cast<unsigned>(m->nnz) >> endBit) != 0) ++endBit;
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keyIn.p, keyOut.p, seqIn.p, seqOut.p, static_cast<size_t>(n), 0, endBit, s));
-	DevBuf<unsigned char> temp;
-	SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keyIn.p, keyOut.p, seqIn.p, seqOut.p, static_cast<size_t>(n), 0, endBit, s));
+	SMM_TRY(sortPairs(keyIn.p, keyOut.p, seqIn.p, seqOut.p, static_cast<size_t>(n), endBit, s));
 	applyEntriesKernel<T><<<gridFor(n), UTPB, 0, s>>>(n, static_cast<unsigned>(m->nnz), keyOut, seqOut, d_vals, mode == SMM_UPDATE_ADD ? 1 : 0,
 	                                                  static_cast<T*>(m->d_values));
 	SMM_HIP_TRY(hipGetLastError());

@@ -21,10 +21,8 @@
 #include <limits>
 #include <type_traits>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 
 // the state of one FSAI / SPAI handle, behind the public handle (whose d_values are G's / M's values: nnz of them)
 struct smm_precond_ainv {
@@ -357,14 +355,7 @@ int ainvPattern(const smm_hip_csr* pat, int power, smm_precond_ainv* A, size_t* 
 	A->maxRow = h[3];
 	A->tier = h[3] <= 8 ? 8 : h[3] <= 16 ? 16 : h[3] <= 32 ? 32 : 64;
 	*nnz = static_cast<size_t>(sum);
-	{
-		size_t bytes = 0;
-		SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, lens.p, A->d_gstart, 0, static_cast<size_t>(n) + 1, rocprim::plus<int>(), s));
-		DevBuf<unsigned char> temp;
-		SMM_TRY(temp.alloc(std::max<size_t>(bytes, 1)));
-		SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, bytes, lens.p, A->d_gstart, 0, static_cast<size_t>(n) + 1, rocprim::plus<int>(), s));
-		SMM_HIP_TRY(hipStreamSynchronize(s));  // (temp goes back to the allocator)
-	}
+	SMM_TRY(scanExclusive(lens.p, A->d_gstart, static_cast<size_t>(n) + 1, s));
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&A->d_gpos), std::max<size_t>(1, *nnz) * sizeof(int)));
 	if (n) ainvFillKernel<LOWER><<<rowGrid(n), TPB, 0, s>>>(n, pat->d_start, pat->d_positions, A->d_gstart, A->d_gpos);
 	SMM_HIP_TRY(hipGetLastError());

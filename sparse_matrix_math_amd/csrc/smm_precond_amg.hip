@@ -35,11 +35,8 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 #include "smm_solver_host.h"
 #include "smm_solver_scal.h"
 
@@ -422,15 +419,6 @@ __global__ __launch_bounds__(TPB) void amgAddKernel(int n, const T* d, T* x, con
 	streamMap<T, NT, 2, 1>(n, in, out, [&](const T(&v)[2], T(&o)[1]) { o[0] = v[0] + v[1]; });
 }
 
-int scanExclusive(const int* in, int* out, size_t count, hipStream_t s) {
-	size_t bytes = 0;
-	SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int>(), s));
-	DevBuf<unsigned char> temp;
-	SMM_TRY(temp.alloc(std::max<size_t>(bytes, 1)));
-	SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, bytes, in, out, 0, count, rocprim::plus<int>(), s));
-	return SMM_HIP_OK;
-}
-
 int readInt(const int* d, int* h, hipStream_t s) {
 	SMM_HIP_TRY(hipMemcpyAsync(h, d, sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));
@@ -504,7 +492,7 @@ int aggregateGraph(const smm_hip_csr* A, const T* diag, double thetaL, int** out
 	}
 	const int* state = stIn;
 	amgFlagKernel<<<rowGrid(len), TPB, 0, s>>>(n, state, 2, false, flag);
-	SMM_TRY(scanExclusive(flag, number, len, s));
+	SMM_TRY(scanExclusive(flag.p, number.p, len, s));
 	int nRoots = 0;
 	SMM_TRY(readInt(number.p + n, &nRoots, s));
 	amgPhase1Kernel<<<g, TPB, 0, s>>>(n, A->d_start, A->d_positions, strong, state, number, agg);
@@ -521,7 +509,7 @@ int aggregateGraph(const smm_hip_csr* A, const T* diag, double thetaL, int** out
 	}
 	if (aIn != agg) SMM_HIP_TRY(hipMemcpyAsync(agg, aIn, static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToDevice, s));
 	amgFlagKernel<<<rowGrid(len), TPB, 0, s>>>(n, agg, 0, true, flag);
-	SMM_TRY(scanExclusive(flag, number, len, s));
+	SMM_TRY(scanExclusive(flag.p, number.p, len, s));
 	int left = 0;
 	SMM_TRY(readInt(number.p + n, &left, s));
 	if (left) amgLeftKernel<<<g, TPB, 0, s>>>(n, nRoots, number, agg);
@@ -612,7 +600,6 @@ int buildTentative(const smm_precond_amg* G, smm_amg_level& L, void** Bnext, hip
 	const size_t nk = static_cast<size_t>(n) * k, nck = static_cast<size_t>(L.nc) * k;
 	DevBuf<int> iota, sortedAgg, members, aggStart, keptMask, count;
 	DevBuf<T> qd, next;
-	DevBuf<unsigned char> temp;
 	DrainOnExit drain(s);
 	SMM_TRY(iota.alloc(static_cast<size_t>(n)));
 	SMM_TRY(sortedAgg.alloc(static_cast<size_t>(n)));
@@ -624,10 +611,7 @@ int buildTentative(const smm_precond_amg* G, smm_amg_level& L, void** Bnext, hip
 	SMM_TRY(next.alloc(nck));
 	// the member dofs of every aggregate in ascending order: a stable sort of the dof numbers by aggregate number
 	amgIotaKernel<<<rowGrid(n), TPB, 0, s>>>(n, iota);
-	size_t bytes = 0;
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, L.d_agg, sortedAgg.p, iota.p, members.p, static_cast<size_t>(n), 0u, 32u, s));
-	SMM_TRY(temp.alloc(std::max<size_t>(bytes, 1)));
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, bytes, L.d_agg, sortedAgg.p, iota.p, members.p, static_cast<size_t>(n), 0u, 32u, s));
+	SMM_TRY(sortPairs(L.d_agg, sortedAgg.p, iota.p, members.p, static_cast<size_t>(n), 32u, s));
 	amgBoundsKernel<<<rowGrid(nAgg + 1LL), TPB, 0, s>>>(nAgg, n, sortedAgg, aggStart);
 	SMM_HIP_TRY(hipGetLastError());
 	std::vector<int> bounds(static_cast<size_t>(nAgg) + 1);
@@ -645,7 +629,7 @@ int buildTentative(const smm_precond_amg* G, smm_amg_level& L, void** Bnext, hip
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_tstart), (static_cast<size_t>(n) + 1) * sizeof(int)));
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&L.d_tpos), std::max<size_t>(nk, 1) * sizeof(int)));
 	SMM_TRY(devAlloc(&L.d_tval, std::max<size_t>(nk, 1) * sizeof(T)));
-	SMM_TRY(scanExclusive(count, L.d_tstart, static_cast<size_t>(n) + 1, s));
+	SMM_TRY(scanExclusive(count.p, L.d_tstart, static_cast<size_t>(n) + 1, s));
 	amgTentativeFillKernel<T><<<rowGrid(n), TPB, 0, s>>>(n, k, members, sortedAgg, aggStart, keptMask, L.d_tstart, qd, L.d_tpos, static_cast<T*>(L.d_tval));
 	SMM_HIP_TRY(hipGetLastError());
 	std::vector<int> kept(static_cast<size_t>(nAgg));

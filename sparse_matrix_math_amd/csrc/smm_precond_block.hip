@@ -21,11 +21,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 
 struct smm_precond_block {
 	int nBlocks = 0;
@@ -1029,16 +1026,6 @@ static int packKind(const smm_hip_csr* a, smm_hip_precond* M, const unsigned* me
 	}
 }
 
-static int exclusiveScanInPlace(int* d, size_t n, hipStream_t s) {
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, d, d, 0, n, rocprim::plus<int>(), s));
-	DevBuf<char> temp;
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, d, d, 0, n, rocprim::plus<int>(), s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));  // temp goes back to the allocator
-	return SMM_HIP_OK;
-}
-
 // ---- the BRICK partition (r03) ----------------------------------------------------------------------------------------------
 // Contiguous row blocks of a 3-D grid in natural order are a few grid LINES of one plane: every coupling to the planes above and below
 // is dropped from M and BiCGStab needs 150 iterations on the 108^3 problem where the exact ILU0 needs 67.  When the matrix is a grid
@@ -1118,7 +1105,6 @@ static int brickPartition(const smm_hip_csr* a, smm_precond_block* B, hipStream_
 	const int nbx = (nx + bx - 1) / bx, nby = (ny + by - 1) / by;
 	DevBuf<unsigned> keys, keysSorted;
 	DevBuf<int> rows, head;
-	DevBuf<char> temp;
 	SMM_TRY(keys.alloc(static_cast<size_t>(n)));
 	SMM_TRY(keysSorted.alloc(static_cast<size_t>(n)));
 	SMM_TRY(rows.alloc(static_cast<size_t>(n)));
@@ -1127,12 +1113,9 @@ static int brickPartition(const smm_hip_csr* a, smm_precond_block* B, hipStream_
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&B->d_invOrder), static_cast<size_t>(n) * sizeof(int)));
 	const int grid = (n + 1 + 255) / 256;
 	brickKeyKernel<<<grid, 256, 0, s>>>(n, nx, ny, bx, by, bz, nbx, nby, keys, rows);
-	size_t tempBytes = 0;  // (LSD radix sort: stable, so the rows of a block stay in ascending order)
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keys.p, keysSorted.p, rows.p, B->d_rowOrder, static_cast<size_t>(n), 0, 32, s));
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keys.p, keysSorted.p, rows.p, B->d_rowOrder, static_cast<size_t>(n), 0, 32, s));
+	SMM_TRY(sortPairs(keys.p, keysSorted.p, rows.p, B->d_rowOrder, static_cast<size_t>(n), 32u, s));  // (stable: the rows of a block stay in ascending order)
 	brickHeadKernel<<<grid, 256, 0, s>>>(n, keysSorted, B->d_rowOrder, B->d_invOrder, head);
-	SMM_TRY(exclusiveScanInPlace(head, static_cast<size_t>(n) + 1, s));  // head[p] = blocks that start before position p; drains s
+	SMM_TRY(scanExclusive(head.p, head.p, static_cast<size_t>(n) + 1, s));  // head[p] = blocks that start before position p
 	int nBlocks = 0;
 	SMM_HIP_TRY(hipMemcpyAsync(&nBlocks, head.p + n, sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));
@@ -1186,7 +1169,7 @@ int blockCreateTyped(const smm_hip_csr* a, int kind, int blockRows, int levelCap
 	const int nBlocks = B->nBlocks;
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&B->d_chunk0), (static_cast<size_t>(nBlocks) + 1) * sizeof(int)));
 	blkChunkCountKernel<<<(nBlocks + 1 + 255) / 256, 256, 0, s>>>(nBlocks, B->d_bounds, B->d_chunk0);
-	SMM_TRY(exclusiveScanInPlace(B->d_chunk0, static_cast<size_t>(nBlocks) + 1, s));
+	SMM_TRY(scanExclusive(B->d_chunk0, B->d_chunk0, static_cast<size_t>(nBlocks) + 1, s));
 	int nChunks = 0;
 	SMM_HIP_TRY(hipMemcpyAsync(&nChunks, B->d_chunk0 + nBlocks, sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));
@@ -1240,8 +1223,8 @@ int blockCreateTyped(const smm_hip_csr* a, int kind, int blockRows, int levelCap
 		const int grid = static_cast<int>((nRec + 1 + 255) / 256);
 		blkOverflowCountKernel<<<grid, 256, 0, s>>>(static_cast<long long>(nRec), B->kreg, nEntLo, B->d_ovPtrLo);
 		blkOverflowCountKernel<<<grid, 256, 0, s>>>(static_cast<long long>(nRec), B->kreg, nEntUp, B->d_ovPtrUp);
-		SMM_TRY(exclusiveScanInPlace(B->d_ovPtrLo, nRec + 1, s));
-		SMM_TRY(exclusiveScanInPlace(B->d_ovPtrUp, nRec + 1, s));
+		SMM_TRY(scanExclusive(B->d_ovPtrLo, B->d_ovPtrLo, nRec + 1, s));
+		SMM_TRY(scanExclusive(B->d_ovPtrUp, B->d_ovPtrUp, nRec + 1, s));
 		int tot[2] = {0, 0};
 		SMM_HIP_TRY(hipMemcpyAsync(&tot[0], B->d_ovPtrLo + nRec, sizeof(int), hipMemcpyDeviceToHost, s));
 		SMM_HIP_TRY(hipMemcpyAsync(&tot[1], B->d_ovPtrUp + nRec, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -25,8 +25,6 @@
 #include <algorithm>
 #include <map>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "smm_trisweep.h"
 
 struct smm_precond_jsweep {
@@ -183,8 +181,6 @@ __global__ __launch_bounds__(JS_TPB) void jsStartKernel(int n, const T* __restri
 	out[i] = sweepFinish<T, MODE>(sweepStart<T, MODE>(mine), mine, diag[i]);
 }
 
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + JS_TPB - 1) / JS_TPB)); }
-
 void freeScratch(smm_precond_jsweep* J) {
 	for (auto& kv : J->scratch) {
 		devFree(kv.second.s0);
@@ -213,16 +209,6 @@ int scratchFor(const smm_hip_precond* M, size_t elemBytes, hipStream_t s, smm_pr
 		it = J->scratch.emplace(s, sc).first;
 	}
 	*out = it->second;
-	return SMM_HIP_OK;
-}
-
-int scanCounts(int* d_cnt, int* d_start, size_t count, hipStream_t s) {
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, d_cnt, d_start, 0, count, rocprim::plus<int>(), s));
-	DevBuf<char> temp;
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, d_cnt, d_start, 0, count, rocprim::plus<int>(), s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));  // (temp goes back to the allocator when this scope ends)
 	return SMM_HIP_OK;
 }
 
@@ -257,8 +243,8 @@ int buildSplit(smm_hip_precond* M, hipStream_t s) {
 	SMM_HIP_TRY(hipGetLastError());
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&J->d_startL), n1 * sizeof(int)));
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&J->d_startU), n1 * sizeof(int)));
-	SMM_TRY(scanCounts(cntL, J->d_startL, n1, s));
-	SMM_TRY(scanCounts(cntU, J->d_startU, n1, s));
+	SMM_TRY(scanExclusive(cntL.p, J->d_startL, n1, s));
+	SMM_TRY(scanExclusive(cntU.p, J->d_startU, n1, s));
 	SMM_HIP_TRY(hipMemcpyAsync(&J->nnzL, J->d_startL + n, sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipMemcpyAsync(&J->nnzU, J->d_startU + n, sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));

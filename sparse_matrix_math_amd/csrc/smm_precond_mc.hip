@@ -51,8 +51,6 @@ __global__ __launch_bounds__(MTPB) void mcCheckColorsKernel(int n, const int* __
 	if (bad) info[0] = 1;
 }
 
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + MTPB - 1) / MTPB)); }
-
 // B's values from A's present values, the structural checks of the exact kind, and the factor
 template <typename T>
 int mcNumeric(smm_hip_precond* M, bool refreshB, hipStream_t s) {

@@ -20,16 +20,13 @@
 // least (levels x searches) round trips: long thin graphs are slow.
 #include <algorithm>
 #include <climits>
-#include <memory>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "smm_internal.h"
+#include "smm_csr_build.h"
 
 namespace smm {
 namespace {
 
-constexpr int RTPB = 256;
+constexpr int RTPB = BUILD_TPB;
 constexpr int SORT_CAP = 1024;       // the largest level one workgroup sorts in LDS
 constexpr int SORT_TPB = 512;        // one lane per compare-exchange of 1024 keys
 constexpr int WAVE_ROW = 64;         // rows longer than this are walked by the whole wavefront
@@ -42,18 +39,6 @@ struct LevelRec {  // what the host reads per level
 	unsigned long long minKey;  // the smallest (deg << 32 | index) among them
 };
 
-int bitsFor(long long count) {  // bits that hold 0 .. count - 1
-	int b = 0;
-	while (b < 63 && (count - 1) >> b) ++b;
-	return b;
-}
-
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + RTPB - 1) / RTPB)); }
-
-struct CsrDeleter {
-	void operator()(smm_hip_csr* m) const { smm_hip_csr_destroy(m); }
-};
-
 template <typename V>
 int readBack(V* host, const V* dev, hipStream_t s) {
 	SMM_HIP_TRY(hipMemcpyAsync(host, dev, sizeof(V), hipMemcpyDeviceToHost, s));
@@ -63,12 +48,6 @@ int readBack(V* host, const V* dev, hipStream_t s) {
 
 __device__ __forceinline__ unsigned long long keyOf(int deg, int v) {
 	return (static_cast<unsigned long long>(static_cast<unsigned>(deg)) << 32) | static_cast<unsigned long long>(static_cast<unsigned>(v));
-}
-
-__global__ __launch_bounds__(RTPB) void intsDifferKernel(long long n, const int* __restrict__ a, const int* __restrict__ b, int* differs) {
-	bool d = false;
-	for (long long i = static_cast<long long>(blockIdx.x) * RTPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * RTPB) d |= a[i] != b[i];
-	if (d) *differs = 1;  // (every writer writes the same word)
 }
 
 __global__ __launch_bounds__(RTPB) void fillKernel(int n, int value, int* __restrict__ out) {
@@ -357,16 +336,8 @@ struct Rcm {
 	DevBuf<LevelRec> rec;
 	DevBuf<unsigned> idxOut;  // the larger levels' sorts
 	DevBuf<unsigned long long> keyIn, keyOut;
-	DevBuf<unsigned char> temp;
-	size_t tempBytes = 0;
+	PrimScratch temp;  // of every sort of the call
 	int stamp = 0;
-
-	int needTemp(size_t bytes) {
-		if (bytes <= tempBytes) return SMM_HIP_OK;
-		SMM_TRY(temp.alloc(bytes));
-		tempBytes = bytes;
-		return SMM_HIP_OK;
-	}
 
 	// a search from `root`, seeded in bufA: its depth and the smallest key of its last level (of which the vertex, the low word, is used)
 	int search(int root, int* depth, unsigned long long* lastKey) {
@@ -402,17 +373,12 @@ struct Rcm {
 		}
 		const unsigned idxBits = static_cast<unsigned>(std::max(1, bitsFor(n)));
 		const unsigned* levelIn = reinterpret_cast<const unsigned*>(bufA.p);  // (vertex numbers: never negative)
-		size_t bytes = 0;
-		SMM_HIP_TRY(rocprim::radix_sort_keys(nullptr, bytes, levelIn, idxOut.p, static_cast<size_t>(g), 0u, idxBits, s));
-		SMM_TRY(needTemp(bytes));
-		SMM_HIP_TRY(rocprim::radix_sort_keys(temp.p, bytes, levelIn, idxOut.p, static_cast<size_t>(g), 0u, idxBits, s));
+		SMM_TRY(sortKeys(levelIn, idxOut.p, static_cast<size_t>(g), idxBits, s, &temp));
 		const int* sorted = reinterpret_cast<const int*>(idxOut.p);
 		levelKeyKernel<<<gridOf(g), RTPB, 0, s>>>(g, sorted, parent, deg, keyIn);
 		SMM_HIP_TRY(hipGetLastError());
 		// stable: vertices of one (parent, deg) stay in index order
-		SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keyIn.p, keyOut.p, sorted, order.p + base, static_cast<size_t>(g), 0u, 32u + idxBits, s));
-		SMM_TRY(needTemp(bytes));
-		SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, bytes, keyIn.p, keyOut.p, sorted, order.p + base, static_cast<size_t>(g), 0u, 32u + idxBits, s));
+		SMM_TRY(sortPairs(keyIn.p, keyOut.p, sorted, order.p + base, static_cast<size_t>(g), 32u + idxBits, s, &temp));
 		numberLevelKernel<<<gridOf(g), RTPB, 0, s>>>(g, base, order, rank);
 		SMM_HIP_TRY(hipGetLastError());
 		return SMM_HIP_OK;
@@ -466,10 +432,7 @@ struct Rcm {
 			degreeKernel<<<gridOf(n), RTPB, 0, s>>>(n, start, positions, deg, degKey, seq, cursor.p + 1);
 			SMM_HIP_TRY(hipGetLastError());
 			const unsigned endBit = static_cast<unsigned>(std::max(1, bitsFor(n)));  // (deg < n)
-			size_t bytes = 0;
-			SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, degKey.p, degSorted.p, seq.p, byKey.p, static_cast<size_t>(n), 0u, endBit, s));
-			SMM_TRY(needTemp(bytes));
-			SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, bytes, degKey.p, degSorted.p, seq.p, byKey.p, static_cast<size_t>(n), 0u, endBit, s));
+			SMM_TRY(sortPairs(degKey.p, degSorted.p, seq.p, byKey.p, static_cast<size_t>(n), endBit, s, &temp));
 			SMM_HIP_TRY(hipStreamSynchronize(s));  // the three temporaries go back to the allocator when this scope ends
 		}
 		int iso = 0;
@@ -552,7 +515,7 @@ int csrRcm(const smm_hip_csr* a, hipStream_t s, int reverse, int* d_perm, int* c
 		// the in-neighbours: the transpose (it checks start[] and the columns); when its pattern is a's own, a's arrays are the graph
 		smm_hip_csr* raw = nullptr;
 		SMM_TRY(csrTransposeCreate(a, s, &raw));
-		std::unique_ptr<smm_hip_csr, CsrDeleter> t(raw), both;
+		OwnedCsr t(raw), both;
 		DevBuf<int> d_diff;
 		SMM_TRY(d_diff.alloc(1));
 		SMM_HIP_TRY(hipMemsetAsync(d_diff, 0, sizeof(int), s));

@@ -27,18 +27,14 @@
 //   Bytes beside the set-up passes: A once per phase, sum ub_i (s + 4) gathered from B (4 in the symbolic passes), nnz(C) (s + 4) written.
 #include <algorithm>
 #include <climits>
-#include <memory>
 
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 
 namespace smm {
 namespace {
 
-constexpr int GTPB = 256;
+constexpr int GTPB = BUILD_TPB;
 constexpr int MAXBINS = 5;
 // symbolic bins by ub (the last bin: global table) and the LDS slots per row of the first four
 constexpr long long SYM_UP[MAXBINS - 1] = {32, 256, 1024, 4096};
@@ -55,14 +51,6 @@ struct BinCuts {
 	long long upTo[MAXBINS - 1];
 	int bins;
 };
-
-int gridOf(long long work, int per = GTPB) { return static_cast<int>(std::max<long long>(1, (work + per - 1) / per)); }
-
-int bitsFor(int count) {  // bits that hold 0 .. count - 1
-	int b = 0;
-	while (b < 31 && (static_cast<long long>(count) - 1) >> b) ++b;
-	return b;
-}
 
 // the two words of a call: [0] the check word, [1] the smallest row with a product outside the pattern
 __global__ void flagsInitKernel(int* flags) {
@@ -285,12 +273,6 @@ __global__ __launch_bounds__(GTPB) void symbolicGlobalFillKernel(int nList, cons
 	}
 }
 
-// start[i] = start64[i] for i <= m (the caller has checked start64[m] <= INT_MAX)
-__global__ __launch_bounds__(GTPB) void narrowKernel(int m, const long long* __restrict__ start64, int* __restrict__ start) {
-	const long long i = static_cast<long long>(blockIdx.x) * GTPB + threadIdx.x;
-	if (i <= m) start[i] = static_cast<int>(start64[i]);
-}
-
 // the place of col in the ascending cols[0 .. len), -1 when it is not there
 __device__ __forceinline__ int slotOf(const int* cols, int len, int col) {
 	int lo = 0, hi = len;
@@ -383,13 +365,6 @@ __global__ __launch_bounds__(GTPB) void numericGlobalKernel(int nList, const int
 	}
 	if (missed) atomicMin(badRow, row);
 }
-
-struct CsrDeleter {
-	void operator()(smm_hip_csr* m) const { smm_hip_csr_destroy(m); }
-};
-
-template <typename T>
-int allocArray(T** p, size_t count) { return devAlloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)); }
 
 // the rows of a matrix dealt to bins: list[] bin after bin, hostCounts[] once the caller has synchronised
 struct RowBins {
@@ -519,12 +494,8 @@ int multiplyCreateTyped(const smm_hip_csr* a, const smm_hip_csr* b, hipStream_t 
 		setError("csr_multiply_create: start[] of %s does not ascend from 0", a->nnz < 0 || (m == 0 && a->nnz != 0) ? "a" : "b");
 		return SMM_HIP_ERR_INVALID;
 	}
-	std::unique_ptr<smm_hip_csr, CsrDeleter> c(new smm_hip_csr());
-	c->rows = m;
-	c->cols = n;
-	c->dtype = a->dtype;
-	c->owns = true;
-	SMM_TRY(allocArray(&c->d_start, static_cast<size_t>(m) + 1));
+	OwnedCsr c;
+	SMM_TRY(newOwnedCsr(m, n, a->dtype, &c));
 	DevBuf<int> d_bad;  // [0] the check word, [1] the smallest row with a product outside the pattern
 	SMM_TRY(d_bad.alloc(2));
 	flagsInitKernel<<<1, 64, 0, s>>>(d_bad.p);
@@ -532,7 +503,7 @@ int multiplyCreateTyped(const smm_hip_csr* a, const smm_hip_csr* b, hipStream_t 
 	SMM_TRY(enqueueCheck(b, BAD_B_START, BAD_B_COL, d_bad, s));
 	long long nnzC = 0;
 	if (m > 0 && a->nnz > 0 && b->nnz > 0) {
-		DevBuf<long long> ub, tableOff, start64;
+		DevBuf<long long> ub, tableOff;
 		DevBuf<unsigned long long> tableSlots;
 		SMM_TRY(ub.alloc(static_cast<size_t>(m)));
 		SMM_TRY(tableOff.alloc(static_cast<size_t>(m)));
@@ -560,24 +531,8 @@ int multiplyCreateTyped(const smm_hip_csr* a, const smm_hip_csr* b, hipStream_t 
 			symbolicGlobalCountKernel<<<nLong, GTPB, 0, s>>>(nLong, longList, n, ub, tableOff, tables, a->d_start, a->d_positions, b->d_start, b->d_positions, count);
 			SMM_HIP_TRY(hipGetLastError());
 		}
-		SMM_TRY(start64.alloc(static_cast<size_t>(m) + 1));
-		{
-			size_t tempBytes = 0;
-			SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, count.p, start64.p, 0LL, static_cast<size_t>(m) + 1, rocprim::plus<long long>(), s));
-			DevBuf<unsigned char> temp;
-			SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-			SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, count.p, start64.p, 0LL, static_cast<size_t>(m) + 1, rocprim::plus<long long>(), s));
-		}
-		// the rows by their stored length, for the numeric phase: count[] is start's difference, read through a start-shaped view below
-		SMM_HIP_TRY(hipMemcpyAsync(&nnzC, start64.p + m, sizeof(long long), hipMemcpyDeviceToHost, s));
-		SMM_HIP_TRY(hipStreamSynchronize(s));
-		if (nnzC > INT_MAX) {
-			setError("csr_multiply_create: the product holds %lld entries, more than 2^31 - 1", nnzC);
-			return SMM_HIP_ERR_INVALID;
-		}
-		narrowKernel<<<gridOf(m + 1LL), GTPB, 0, s>>>(m, start64, c->d_start);
-		SMM_TRY(allocArray(&c->d_positions, static_cast<size_t>(nnzC)));
-		SMM_TRY(devAlloc(&c->d_values, static_cast<size_t>(nnzC ? nnzC : 1) * sizeof(T)));
+		SMM_TRY(startsFromCounts("csr_multiply_create", "product", count.p, m, c.get(), &nnzC, s));
+		SMM_TRY(allocCsrEntries(c.get(), nnzC, false));
 		if (nnzC > 0) {
 			// ---- symbolic, pass two: the columns in table order, then ascending
 			DevBuf<int> unsorted;
@@ -589,16 +544,8 @@ int multiplyCreateTyped(const smm_hip_csr* a, const smm_hip_csr* b, hipStream_t 
 				symbolicGlobalFillKernel<<<nLong, GTPB, 0, s>>>(nLong, longList, n, ub, tableOff, tables, c->d_start, cursor, unsorted);
 				SMM_HIP_TRY(hipGetLastError());
 			}
-			{
-				const unsigned endBit = static_cast<unsigned>(std::max(1, bitsFor(n)));
-				size_t tempBytes = 0;
-				unsigned* in = reinterpret_cast<unsigned*>(unsorted.p);
-				unsigned* sorted = reinterpret_cast<unsigned*>(c->d_positions);
-				SMM_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tempBytes, in, sorted, static_cast<unsigned>(nnzC), static_cast<unsigned>(m), c->d_start, c->d_start + 1, 0u, endBit, s));
-				DevBuf<unsigned char> temp;
-				SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-				SMM_HIP_TRY(rocprim::segmented_radix_sort_keys(temp.p, tempBytes, in, sorted, static_cast<unsigned>(nnzC), static_cast<unsigned>(m), c->d_start, c->d_start + 1, 0u, endBit, s));
-			}
+			SMM_TRY(sortKeysSegmented(reinterpret_cast<unsigned*>(unsorted.p), reinterpret_cast<unsigned*>(c->d_positions), static_cast<unsigned>(nnzC),
+			                          static_cast<unsigned>(m), c->d_start, c->d_start + 1, static_cast<unsigned>(std::max(1, bitsFor(n))), s));
 			// ---- numeric: the same code as multiply_into
 			RowBins num;
 			SMM_TRY(enqueueBins<true>(num, m, numericCuts(), nullptr, c->d_start, n, nullptr, nullptr, s));
@@ -620,8 +567,7 @@ int multiplyCreateTyped(const smm_hip_csr* a, const smm_hip_csr* b, hipStream_t 
 		if (bad) return describeBad(bad, "csr_multiply_create", a, b);
 		SMM_HIP_TRY(hipMemsetAsync(c->d_start, 0, (static_cast<size_t>(m) + 1) * sizeof(int), s));
 	}
-	if (!c->d_positions) SMM_TRY(allocArray(&c->d_positions, 1));
-	if (!c->d_values) SMM_TRY(devAlloc(&c->d_values, sizeof(T)));
+	if (!c->d_positions) SMM_TRY(allocCsrEntries(c.get(), 0, false));
 	SMM_TRY(ensureCsrReady(c.get(), s, true));  // nnz, the first active row, the typical row and the kernel choice as for caller-owned device arrays
 	*out = c.release();
 	return SMM_HIP_OK;
@@ -684,15 +630,7 @@ int multiplyIntoTyped(smm_hip_csr* c, const smm_hip_csr* a, const smm_hip_csr* b
 		setError("%s: a product of row %d falls on an entry that c does not store", what, badRow);
 		return SMM_HIP_ERR_INVALID;
 	}
-	if (c->nnz > 0) {
-		if (c->owns) {  // the scratch becomes the values array; the old one goes back to the allocator behind the work queued on it
-			void* old = c->d_values;
-			c->d_values = scratch.detach();
-			devFree(old);
-		} else {
-			SMM_HIP_TRY(hipMemcpyAsync(c->d_values, scratch.p, static_cast<size_t>(c->nnz) * sizeof(T), hipMemcpyDeviceToDevice, s));
-		}
-	}
+	SMM_TRY(adoptValues(c, scratch, s));
 	return csrValuesEdited(c, s);
 }
 

@@ -26,10 +26,8 @@
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 
 namespace smm {
 
@@ -784,11 +782,7 @@ int cutRows(const int* d_start, int rows, long long nnz, int capNnz, int maxRows
 	SMM_HIP_TRY(hipMemsetAsync(counts, 0, (static_cast<size_t>(nChunks) + 1) * sizeof(int), s));
 	const int grid = (nChunks + 63) / 64;
 	tileCutKernel<<<grid, 64, 0, s>>>(rows, d_start, capNnz, maxRows, chunkNnz, nChunks, counts, nullptr, nullptr);
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, counts.p, counts.p, 0, static_cast<size_t>(nChunks) + 1, rocprim::plus<int>(), s));
-	DevBuf<char> temp;
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, counts.p, counts.p, 0, static_cast<size_t>(nChunks) + 1, rocprim::plus<int>(), s));
+	SMM_TRY(scanExclusive(counts.p, counts.p, static_cast<size_t>(nChunks) + 1, s));
 	int n = 0;
 	SMM_HIP_TRY(hipMemcpyAsync(&n, counts.p + nChunks, sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipStreamSynchronize(s));  // the caller's stream: the table's size decides the allocation and the grid

@@ -20,10 +20,8 @@
 #include <climits>
 #include <cstring>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 #include "smm_pattern_dev.h"
 
 namespace smm {
@@ -323,15 +321,6 @@ __global__ __launch_bounds__(TPB) void spmvLongRowsKernel(int nTiles, int cap, i
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-static int lrScan(int* d, size_t n, hipStream_t s) {
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::exclusive_scan(nullptr, tempBytes, d, d, 0, n, rocprim::plus<int>(), s));
-	DevBuf<char> temp;
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::exclusive_scan(temp.p, tempBytes, d, d, 0, n, rocprim::plus<int>(), s));
-	return SMM_HIP_OK;
-}
-
 // the analysis, on `s` (caller holds tileMutex); the handle is written last, and only on success.  Reads start[] only.
 static int buildLongRowsLocked(smm_hip_csr* m, hipStream_t s) {
 	SetupTrace trace("LONGROWS analysis");
@@ -353,8 +342,8 @@ static int buildLongRowsLocked(smm_hip_csr* m, hipStream_t s) {
 	const int grid = static_cast<int>((n1 + 255) / 256);
 	lrMarkKernel<<<grid, 256, 0, s>>>(rows, m->d_start, splitLen, segLen, capNnz, isLong, segs, cutLen);
 	SMM_HIP_TRY(hipGetLastError());
-	SMM_TRY(lrScan(isLong, n1, s));
-	SMM_TRY(lrScan(segs, n1, s));
+	SMM_TRY(scanExclusive(isLong.p, isLong.p, n1, s));
+	SMM_TRY(scanExclusive(segs.p, segs.p, n1, s));
 	int nLong = 0, nSegs = 0;
 	SMM_HIP_TRY(hipMemcpyAsync(&nLong, isLong.p + rows, sizeof(int), hipMemcpyDeviceToHost, s));
 	SMM_HIP_TRY(hipMemcpyAsync(&nSegs, segs.p + rows, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -365,7 +354,7 @@ static int buildLongRowsLocked(smm_hip_csr* m, hipStream_t s) {
 		setError("longrows SpMV: %d long rows in a matrix of %d entries overflow the tile cut's 32-bit row starts", nLong, m->nnz);
 		return SMM_HIP_ERR_INVALID;
 	}
-	SMM_TRY(lrScan(cutLen, n1, s));
+	SMM_TRY(scanExclusive(cutLen.p, cutLen.p, n1, s));
 	DevBuf<int2> list;
 	SMM_TRY(list.alloc(static_cast<size_t>(nLong) + 1));
 	lrListKernel<<<grid, 256, 0, s>>>(rows, m->d_start, splitLen, isLong, segs, list);

@@ -28,10 +28,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
-#include "smm_internal.h"
 #include "smm_pattern_dev.h"
 
 namespace smm {
@@ -1310,7 +1308,6 @@ static int tryDict(smm_hip_csr* m, hipStream_t s, const char** why) {
 	};
 	DevBuf<int> d_table, d_sorted, d_state, d_dict;
 	DevBuf<unsigned short> d_codes;
-	DevBuf<char> temp;
 	SMM_TRY(d_table.alloc(DICT_HCAP));
 	SMM_TRY(d_sorted.alloc(DICT_HCAP));
 	SMM_TRY(d_state.alloc(4));
@@ -1326,10 +1323,7 @@ static int tryDict(smm_hip_csr* m, hipStream_t s, const char** why) {
 	const int k = st[0];
 	if (k <= 0) return no("no entries");
 	// PAT_EMPTY is INT_MIN: after an ascending sort of the whole table the dictionary is its last k entries
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::radix_sort_keys(nullptr, tempBytes, d_table.p, d_sorted.p, static_cast<size_t>(DICT_HCAP), 0, 32, s));
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::radix_sort_keys(temp.p, tempBytes, d_table.p, d_sorted.p, static_cast<size_t>(DICT_HCAP), 0, 32, s));
+	SMM_TRY(sortKeys(d_table.p, d_sorted.p, static_cast<size_t>(DICT_HCAP), 32u, s));
 	SMM_TRY(d_dict.alloc(static_cast<size_t>(k)));
 	SMM_HIP_TRY(hipMemcpyAsync(d_dict, d_sorted.p + (DICT_HCAP - k), static_cast<size_t>(k) * sizeof(int), hipMemcpyDeviceToDevice, s));
 	// 16 codes of padding: the kernel's 16-byte loads may start at the last entry

@@ -12,8 +12,7 @@
 // bits.  The L accumulators are independent chains (instruction-level parallelism without any cross-lane step).
 #include <algorithm>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_pattern_dev.h"
 
 namespace smm {
@@ -249,7 +248,6 @@ static int slotsBuild(smm_hip_csr* m, bool forced, hipStream_t s) {
 	const int nWaves = (m->rows + WAVE - 1) / WAVE;
 	DevBuf<long long> counts, base;
 	DevBuf<int> uniform;
-	DevBuf<unsigned char> temp;
 	SMM_TRY(counts.alloc(nWaves));
 	SMM_TRY(base.alloc(static_cast<size_t>(nWaves) + 1));
 	SMM_TRY(uniform.alloc(1));
@@ -258,10 +256,7 @@ static int slotsBuild(smm_hip_csr* m, bool forced, hipStream_t s) {
 	const int grid = std::max(1, std::min(4096, (nWaves + SLOT_WAVES - 1) / SLOT_WAVES));
 	slotsCountKernel<<<grid, TPB, 0, s>>>(m->rows, nWaves, m->d_pat_masks, counts.p, uniform.p);
 	SMM_HIP_TRY(hipGetLastError());
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::inclusive_scan(nullptr, tempBytes, counts.p, base.p + 1, static_cast<size_t>(nWaves), rocprim::plus<long long>(), s));
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::inclusive_scan(temp.p, tempBytes, counts.p, base.p + 1, static_cast<size_t>(nWaves), rocprim::plus<long long>(), s));
+	SMM_TRY(scanInclusive(counts.p, base.p + 1, static_cast<size_t>(nWaves), s));
 	slotsMarkKernel<<<std::max(1, std::min(4096, (nWaves + TPB - 1) / TPB)), TPB, 0, s>>>(nWaves, counts.p, base.p);
 	SMM_HIP_TRY(hipGetLastError());
 	long long total = 0;

@@ -12,54 +12,13 @@
 //     gather (a banded matrix's perm[k] stays within the band's width of k).  Then the path of every value edit (csrValuesEdited).
 //   symmetric (smm_hip_csr_is_symmetric): a temporary transpose, start[] / positions[] compared into a flag, then one pass of IEEE == into a flag.
 #include <algorithm>
-#include <memory>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "smm_internal.h"
+#include "smm_csr_build.h"
 
 namespace smm {
 namespace {
 
-constexpr int XTPB = 256;
-
-int bitsFor(int count) {  // bits that hold 0 .. count - 1
-	int b = 0;
-	while (b < 31 && (static_cast<long long>(count) - 1) >> b) ++b;
-	return b;
-}
-
-int gridOf(long long work) { return static_cast<int>(std::max<long long>(1, (work + XTPB - 1) / XTPB)); }
-
-template <typename T>
-struct Word;
-template <>
-struct Word<float> {
-	using type = unsigned;
-};
-template <>
-struct Word<double> {
-	using type = unsigned long long;
-};
-
-// start[0] == 0 and start[] non-decreasing, or *bad is raised: rowOfEntry below relies on neither for its own safety (it only ever reads
-// start[0 .. rows]), but a matrix that fails here has no transpose
-__global__ __launch_bounds__(XTPB) void startCheckKernel(int rows, const int* __restrict__ start, int* bad) {
-	const long long r = static_cast<long long>(blockIdx.x) * XTPB + threadIdx.x;
-	if (r >= rows) return;
-	if (start[r] > start[r + 1] || (r == 0 && start[0] != 0)) *bad = 1;  // (every writer writes the same word)
-}
-
-// the row that holds entry e: the last r in [0, rows) with start[r] <= e (rows >= 1)
-__device__ __forceinline__ int rowOfEntry(int rows, const int* __restrict__ start, int e) {
-	int lo = 0, hi = rows - 1;
-	while (lo < hi) {
-		const int mid = lo + ((hi - lo + 1) >> 1);
-		if (start[mid] <= e) lo = mid;
-		else hi = mid - 1;
-	}
-	return lo;
-}
+constexpr int XTPB = BUILD_TPB;
 
 // one lane per stored entry: key = its column (0 for a column outside [0, cols): *bad is raised and the caller stops), seq = e, row = its row
 __global__ __launch_bounds__(XTPB) void keyRowKernel(int nnz, int rows, int cols, const int* __restrict__ start, const int* __restrict__ positions,
@@ -112,31 +71,12 @@ __global__ __launch_bounds__(XTPB) void sourceCheckKernel(int nnz, int rowsT, co
 	if (i < 0 || i >= rowsA || positionsA[e] != j || startA[i] > e || startA[i + 1] <= e) *differs = 1;
 }
 
-__global__ __launch_bounds__(XTPB) void intsDifferKernel(long long n, const int* __restrict__ a, const int* __restrict__ b, int* differs) {
-	bool d = false;
-	for (long long i = static_cast<long long>(blockIdx.x) * XTPB + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * XTPB) d |= a[i] != b[i];
-	if (d) *differs = 1;
-}
-
 // IEEE ==: -0.0 equals +0.0, a NaN equals nothing
 template <typename T>
 __global__ __launch_bounds__(XTPB) void valuesDifferKernel(int nnz, const T* __restrict__ a, const T* __restrict__ b, int* differs) {
 	bool d = false;
 	for (long long i = static_cast<long long>(blockIdx.x) * XTPB + threadIdx.x; i < nnz; i += static_cast<long long>(gridDim.x) * XTPB) d |= !(a[i] == b[i]);
 	if (d) *differs = 1;
-}
-
-struct CsrDeleter {
-	void operator()(smm_hip_csr* m) const { smm_hip_csr_destroy(m); }
-};
-
-template <typename T>
-int allocArray(T** p, size_t count) { return devAlloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)); }
-
-int readFlag(const int* d_flag, hipStream_t s, int* flag) {
-	SMM_HIP_TRY(hipMemcpyAsync(flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
-	SMM_HIP_TRY(hipStreamSynchronize(s));
-	return SMM_HIP_OK;
 }
 
 template <typename T>
@@ -148,15 +88,9 @@ int transposeTyped(const smm_hip_csr* a, hipStream_t s, smm_hip_csr** out) {
 		setError("csr_transpose: start[rows] is negative");
 		return SMM_HIP_ERR_INVALID;
 	}
-	std::unique_ptr<smm_hip_csr, CsrDeleter> t(new smm_hip_csr());
-	t->rows = cols;
-	t->cols = rows;
-	t->dtype = a->dtype;
-	t->owns = true;
-	SMM_TRY(allocArray(&t->d_start, static_cast<size_t>(cols) + 1));
-	SMM_TRY(allocArray(&t->d_positions, static_cast<size_t>(nnz)));
-	SMM_TRY(devAlloc(&t->d_values, static_cast<size_t>(nnz ? nnz : 1) * sizeof(T)));
-	SMM_TRY(allocArray(&t->d_tperm, static_cast<size_t>(nnz)));
+	OwnedCsr t;
+	SMM_TRY(newOwnedCsr(cols, rows, a->dtype, &t));
+	SMM_TRY(allocCsrEntries(t.get(), nnz, true));
 	DevBuf<int> d_bad;
 	SMM_TRY(d_bad.alloc(1));
 	SMM_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
@@ -176,14 +110,7 @@ int transposeTyped(const smm_hip_csr* a, hipStream_t s, smm_hip_csr** out) {
 			return SMM_HIP_ERR_INVALID;
 		}
 		SMM_TRY(keyOut.alloc(nnz));
-		{
-			const unsigned endBit = static_cast<unsigned>(std::max(1, bitsFor(cols)));
-			size_t tempBytes = 0;
-			SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keyIn.p, keyOut.p, seqIn.p, t->d_tperm, static_cast<size_t>(nnz), 0u, endBit, s));
-			DevBuf<unsigned char> temp;
-			SMM_TRY(temp.alloc(std::max<size_t>(tempBytes, 1)));
-			SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keyIn.p, keyOut.p, seqIn.p, t->d_tperm, static_cast<size_t>(nnz), 0u, endBit, s));
-		}
+		SMM_TRY(sortPairs(keyIn.p, keyOut.p, seqIn.p, t->d_tperm, static_cast<size_t>(nnz), static_cast<unsigned>(std::max(1, bitsFor(cols))), s));
 		colStartKernel<<<gridOf(cols + 1LL), XTPB, 0, s>>>(cols, nnz, keyOut, t->d_start);
 		gatherKernel<W><<<gridOf(nnz), XTPB, 0, s>>>(nnz, t->d_tperm, rowOf, static_cast<const W*>(a->d_values), t->d_positions, static_cast<W*>(t->d_values));
 		SMM_HIP_TRY(hipGetLastError());
@@ -227,22 +154,11 @@ int refreshTyped(smm_hip_csr* at, const smm_hip_csr* a, hipStream_t s) {
 		return SMM_HIP_ERR_INVALID;
 	}
 	const int nnz = at->nnz;
-	int verdict = csrPatternVerdict(a, at->transposeOf);
-	if (verdict < 0) {
-		verdict = 1;
-		if (nnz > 0) {
-			DevBuf<int> d_diff;
-			SMM_TRY(d_diff.alloc(1));
-			SMM_HIP_TRY(hipMemsetAsync(d_diff, 0, sizeof(int), s));
-			sourceCheckKernel<<<gridOf(nnz), XTPB, 0, s>>>(nnz, at->rows, at->d_start, at->d_positions, at->d_tperm, a->rows, a->d_start, a->d_positions, d_diff);
-			SMM_HIP_TRY(hipGetLastError());
-			int diff = 0;
-			SMM_TRY(readFlag(d_diff, s, &diff));
-			verdict = diff ? 0 : 1;
-		}
-		csrPatternRecord(a, at->transposeOf, verdict == 1);
-	}
-	if (verdict != 1) {
+	bool same = false;
+	SMM_TRY(refreshVerdict(a, at->transposeOf, s, [&](int* d_diff) {
+		sourceCheckKernel<<<gridOf(nnz), XTPB, 0, s>>>(nnz, at->rows, at->d_start, at->d_positions, at->d_tperm, a->rows, a->d_start, a->d_positions, d_diff);
+	}, &same));
+	if (!same) {
 		setError("csr_transpose_refresh: the matrix has another nonzero pattern than the transpose's source");
 		return SMM_HIP_ERR_INVALID;
 	}
@@ -334,7 +250,7 @@ int smm_hip_csr_is_symmetric(const smm_hip_csr* a, int* pattern_symmetric, int* 
 	hipStream_t s = libStream();
 	smm_hip_csr* raw = nullptr;
 	SMM_TRY(csrTransposeCreate(a, s, &raw));
-	std::unique_ptr<smm_hip_csr, CsrDeleter> t(raw);
+	OwnedCsr t(raw);
 	int differ = 0;
 	SMM_TRY(patternsDiffer(a, t.get(), s, &differ));
 	if (differ) return SMM_HIP_OK;

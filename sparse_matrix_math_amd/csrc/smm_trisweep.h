@@ -14,8 +14,7 @@
 #include <type_traits>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "smm_csr_build.h"
 #include "smm_device.h"
 #include "smm_internal.h"
 
@@ -219,11 +218,7 @@ inline int sortRowsByKey(const int* d_keys, int n, int nKeys, hipStream_t s, int
 	iotaKernel<<<sweepGrid(n), SWEEP_TPB, 0, s>>>(n, rowsIn);
 	int bits = 1;
 	while (bits < 31 && (1ll << bits) < nKeys) ++bits;
-	size_t tempBytes = 0;
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, d_keys, sorted.p, rowsIn.p, d_order, static_cast<size_t>(n), 0, bits, s));
-	DevBuf<char> temp;
-	SMM_TRY(temp.alloc(tempBytes ? tempBytes : 1));
-	SMM_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, d_keys, sorted.p, rowsIn.p, d_order, static_cast<size_t>(n), 0, bits, s));
+	SMM_TRY(sortPairs(d_keys, sorted.p, rowsIn.p, d_order, static_cast<size_t>(n), static_cast<unsigned>(bits), s));
 	keyBoundsKernel<<<sweepGrid(nKeys + 1LL), SWEEP_TPB, 0, s>>>(n, nKeys, sorted, d_bounds);
 	SMM_HIP_TRY(hipGetLastError());
 	SMM_HIP_TRY(hipMemcpyAsync(hostBounds.data(), d_bounds, hostBounds.size() * sizeof(int), hipMemcpyDeviceToHost, s));
