@@ -43,7 +43,7 @@
 #include "smm_internal.h"
 #include "smm_solver_host.h"
 #include "smm_p2p.h"
-#include "smm_solver_scal.h"
+#include "smm_krylov_steps.h"
 
 namespace smm {
 
@@ -490,27 +490,6 @@ static int exclusiveScan(int* d_inout, int count, hipStream_t s) {
 	return SMM_HIP_OK;
 }
 
-// recurrence state of the distributed loops
-template <typename T>
-struct DistScal {
-	T rrPing[2];  // BiCGStab: rr0 / CG: ||r||^2, double-buffered by iteration parity (workgroup 0 writes the next while others read)
-	T alpha, omega, res;
-	int done, iters, status, pad;  // pad: `done` as distCgR found it (what the launches behind it test: workgroup 0 of one of them may set `done` while others still start)
-	T alphaRing[LAZY_M];  // CG with the deferred x update (distCgLazyP): alpha of the last LAZY_M iterations
-	int flushIter, pad2;  // CG with the direction formed inside the SpMV: the iteration whose SpMV launch found its predecessor converged (-1: none)
-};
-
-// up to four [lo, hi) runs of rows, passed to the update kernels by value
-struct RowRanges {
-	int n = 0;
-	int lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
-	long long rows() const {
-		long long t = 0;
-		for (int i = 0; i < n; ++i) t += hi[i] - lo[i];
-		return t;
-	}
-};
-
 struct P2PState {
 	int world = 1, rank = 0;
 	bool haloOn = true;      // false: the halo stays with the communicator's grouped send / receive, only the scalars go through the slots (the hybrid)
@@ -622,7 +601,7 @@ static int distWorkspace(smm_hip_dist_csr* D) {
 	SMM_TRY(devAlloc(&D->partsA, PARTS_LEN * sizeof(T)));
 	SMM_TRY(devAlloc(&D->partsB, PARTS_LEN * sizeof(T)));
 	SMM_TRY(devAlloc(&D->partsC, PARTS_LEN * sizeof(T)));
-	SMM_TRY(devAlloc(&D->sc, sizeof(DistScal<T>)));
+	SMM_TRY(devAlloc(&D->sc, sizeof(Scal<T>)));
 	SMM_TRY(devAlloc(reinterpret_cast<void**>(&D->splitSync), (P2P_KINDS + 2) * sizeof(unsigned long long)));
 	preloadSplitUnit();  // (its code object is built for the device now, not inside the first iteration)
 	hipStream_t s = libStream();
@@ -1576,7 +1555,7 @@ struct ThinForm {
 	const T* pOldExt = nullptr;
 	const T* rExt = nullptr;
 	T* pNewExt = nullptr;
-	const DistScal<T>* sc = nullptr;
+	const Scal<T>* sc = nullptr;
 	const T* totalsC = nullptr;
 	int par = 0;
 	HaloSegs segs{};
@@ -1846,7 +1825,7 @@ __global__ __launch_bounds__(TPB) void distDots(int n, const T* a, const T* b, c
 }
 
 template <typename T>
-__global__ void distBicgInit(const T* __restrict__ totals, DistScal<T>* sc) {
+__global__ void distBicgInit(const T* __restrict__ totals, Scal<T>* sc) {
 	sc->rrPing[0] = totals[0];  // rr0 = r.r0, ref:2231
 	sc->res = T(0);
 	sc->iters = 0;
@@ -1854,89 +1833,39 @@ __global__ void distBicgInit(const T* __restrict__ totals, DistScal<T>* sc) {
 	sc->status = SMM_SOLVER_SUCCESS;
 }
 
-// an element-wise map over up to four runs of rows (the boundary rows some peer receives / the rest: halo first)
-template <typename T, int NIN, int NOUT, bool NT = false, typename F>
-__device__ __forceinline__ void rangesMap(const RowRanges& rg, const T* const* in, T* const* out, F&& f) {
-	for (int i = 0; i < rg.n; ++i) {
-		const T* in2[NIN];
-		T* out2[NOUT];
-#pragma unroll
-		for (int k = 0; k < NIN; ++k) in2[k] = in[k] + rg.lo[i];
-#pragma unroll
-		for (int k = 0; k < NOUT; ++k) out2[k] = out[k] + rg.lo[i];
-		streamMap<T, NT, NIN, NOUT>(rg.hi[i] - rg.lo[i], in2, out2, f);
-	}
-}
-
-// alpha = rr0 / (ap.r0) ; s = -alpha ap + r   (ref:2243-2247).  book: this launch records alpha (the other launch of the pair -- boundary
-// rows first, then the bulk -- forms the same alpha from the same operands and only uses it)
+// The steps are those of the single-GPU loop (smm_krylov_steps.h): the kernels here hand them the all-reduced totals and the rows of their
+// launch.  book: this launch records the scalars (the other launch of a pair -- boundary rows first, then the bulk -- forms the same
+// scalars from the same operands and only uses them).
+// alpha = rr0 / (ap.r0) ; s = -alpha ap + r   (ref:2243-2247)
 template <typename T>
-__global__ __launch_bounds__(TPB) void distBicgS(RowRanges rg, int book, DistScal<T>* sc, int par, const T* __restrict__ totalsA, const T* ap, const T* r, T* sv) {
+__global__ __launch_bounds__(TPB) void distBicgS(RowRanges rg, int book, Scal<T>* sc, int par, const T* __restrict__ totalsA, const T* ap, const T* r, T* sv) {
 	if (sc->done) return;
-	const T alpha = sc->rrPing[par] / totalsA[0];
-	if (book && blockIdx.x == 0 && threadIdx.x == 0) sc->alpha = alpha;
-	const T* const in[2] = {ap, r};
-	T* const out[1] = {sv};
-	rangesMap<T, 2, 1>(rg, in, out, [&](const T(&v)[2], T(&o)[1]) { o[0] = smmFma(-alpha, v[0], v[1]); });
+	bicgStepS<T, false>(rg, book, sc, sc->rrPing[par], totalsA[0], ap, r, sv);
 }
 
 // omega = (as.s) / (as.as) ; r = -omega as + s ; local ||r||^2 and r.r0   (ref:2259-2261, 2265)
 template <typename T>
-__global__ __launch_bounds__(TPB) void distBicgR(int n, DistScal<T>* sc, const T* __restrict__ totalsB, const T* sv, const T* as, const T* r0, T* r,
+__global__ __launch_bounds__(TPB) void distBicgR(int n, Scal<T>* sc, const T* __restrict__ totalsB, const T* sv, const T* as, const T* r0, T* r,
                                                  T* partsC) {
 	__shared__ T red[4];
 	if (sc->done) return;
-	const T omega = totalsB[1] / totalsB[0];
-	if (blockIdx.x == 0 && threadIdx.x == 0) sc->omega = omega;
-	T acc0 = T(0), acc1 = T(0);
-	const T* const in[3] = {sv, as, r0};
-	T* const out[1] = {r};
-	streamMap<T, false, 3, 1>(n, in, out, [&](const T(&v)[3], T(&o)[1]) {
-		const T ri = smmFma(-omega, v[1], v[0]);
-		o[0] = ri;
-		acc0 += ri * ri;
-		acc1 += ri * v[2];
-	});
-	const T s0 = blockSum256(acc0, red);
-	const T s1 = blockSum256(acc1, red);
-	if (threadIdx.x == 0) {
-		partsC[blockIdx.x] = s0;
-		partsC[NPART + blockIdx.x] = s1;
-	}
+	bicgStepXR<T, false, false>(n, sc, totalsB[0], totalsB[1], red, nullptr, sv, as, r0, nullptr, r, partsC);
 }
 
-// The same with x = alpha p + (omega s + x) (ref:2264) folded in -- the single-GPU loop's bicgFusedXR: s is read once for both, one launch
-// instead of two.  Taken when the scalars go through the per-rank slots (the reduction behind this kernel is then a single-workgroup launch on
-// the solver's own stream: there is no side-stream collective for a separate x update to run beside).  Same expressions: same bits.
+// The same with x = alpha p + (omega s + x) (ref:2264) folded in: s is read once for both, one launch instead of two.  Taken when the scalars
+// go through the per-rank slots (the reduction behind this kernel is then a single-workgroup launch on the solver's own stream: there is no
+// side-stream collective for a separate x update to run beside).
 template <typename T>
-__global__ __launch_bounds__(TPB) void distBicgRX(int n, DistScal<T>* sc, const T* __restrict__ totalsB, const T* sv, const T* as, const T* r0, const T* p, T* r,
+__global__ __launch_bounds__(TPB) void distBicgRX(int n, Scal<T>* sc, const T* __restrict__ totalsB, const T* sv, const T* as, const T* r0, const T* p, T* r,
                                                   T* x, T* partsC) {
 	__shared__ T red[4];
 	if (sc->done) return;
-	const T omega = totalsB[1] / totalsB[0];
-	const T alpha = sc->alpha;
-	if (blockIdx.x == 0 && threadIdx.x == 0) sc->omega = omega;
-	T acc0 = T(0), acc1 = T(0);
-	const T* const in[5] = {sv, as, r0, p, x};
-	T* const out[2] = {r, x};
-	streamMap<T, false, 5, 2>(n, in, out, [&](const T(&v)[5], T(&o)[2]) {
-		const T ri = smmFma(-omega, v[1], v[0]);
-		o[0] = ri;
-		o[1] = smmFma(alpha, v[3], smmFma(omega, v[0], v[4]));
-		acc0 += ri * ri;
-		acc1 += ri * v[2];
-	});
-	const T s0 = blockSum256(acc0, red);
-	const T s1 = blockSum256(acc1, red);
-	if (threadIdx.x == 0) {
-		partsC[blockIdx.x] = s0;
-		partsC[NPART + blockIdx.x] = s1;
-	}
+	bicgStepXR<T, false, true>(n, sc, totalsB[0], totalsB[1], red, p, sv, as, r0, x, r, partsC);
 }
 
 // x = alpha p + (omega s + x)   (ref:2264) -- independent of the all-reduce of ||r||^2, r.r0 and runs beside it
 template <typename T>
-__global__ __launch_bounds__(TPB) void distBicgX(int n, const DistScal<T>* __restrict__ sc, const T* p, const T* sv, T* x) {
+__global__ __launch_bounds__(TPB) void distBicgX(int n, const Scal<T>* __restrict__ sc, const T* p, const T* sv, T* x) {
 	if (sc->done) return;
 	const T alpha = sc->alpha, omega = sc->omega;
 	const T* const in[3] = {sv, x, p};
@@ -1944,30 +1873,15 @@ __global__ __launch_bounds__(TPB) void distBicgX(int n, const DistScal<T>* __res
 	streamMap<T, false, 3, 1>(n, in, out, [&](const T(&v)[3], T(&o)[1]) { o[0] = smmFma(alpha, v[2], smmFma(omega, v[0], v[1])); });
 }
 
-// resL2Norm, loop test, beta, p = beta (-omega ap + p) + r   (ref:2268-2277).  book: this launch does the scalar bookkeeping (once per pair)
+// resL2Norm, loop test, beta, p = beta (-omega ap + p) + r   (ref:2268-2277)
 template <typename T>
-__global__ __launch_bounds__(TPB) void distBicgP(RowRanges rg, int book, DistScal<T>* sc, int par, const T* __restrict__ totalsC, T eps, const T* ap, const T* r, T* p) {
+__global__ __launch_bounds__(TPB) void distBicgP(RowRanges rg, int book, Scal<T>* sc, int par, const T* __restrict__ totalsC, T eps, const T* ap, const T* r, T* p) {
 	if (sc->done) return;
-	const T rr = totalsC[0];
-	const T newRR0 = totalsC[1];
-	const T res = sizeof(T) == 4 ? static_cast<T>(__fsqrt_rn(static_cast<float>(rr))) : static_cast<T>(__dsqrt_rn(static_cast<double>(rr)));
-	const T alpha = sc->alpha, omega = sc->omega, rr0 = sc->rrPing[par];
-	const bool leave = !(res > eps);
-	if (book && blockIdx.x == 0 && threadIdx.x == 0) {
-		sc->res = res;
-		sc->rrPing[par ^ 1] = newRR0;
-		sc->iters += 1;
-		if (leave) sc->done = 1;
-	}
-	if (leave) return;
-	const T beta = (newRR0 * alpha) / (rr0 * omega);  // ref:2271
-	const T* const in[3] = {ap, p, r};
-	T* const out[1] = {p};
-	rangesMap<T, 3, 1>(rg, in, out, [&](const T(&v)[3], T(&o)[1]) { o[0] = smmFma(beta, smmFma(-omega, v[0], v[1]), v[2]); });
+	bicgStepP<T, false>(rg, book, sc, par, totalsC[0], totalsC[1], eps, ap, r, p);
 }
 
 template <typename T>
-__global__ void distCgInit(const T* __restrict__ totals, DistScal<T>* sc, T eps) {
+__global__ void distCgInit(const T* __restrict__ totals, Scal<T>* sc, T eps) {
 	const T rr = totals[0];  // ref:2341
 	sc->rrPing[0] = rr;
 	sc->res = rr;
@@ -1985,31 +1899,15 @@ __global__ void distCgInit(const T* __restrict__ totals, DistScal<T>* sc, T eps)
 // alpha = rr / (Ap.p) ; r = -alpha Ap + r ; local ||r||^2   (ref:2354-2375)
 // (NT in the CG kernels: non-temporal loads / stores when the vectors cannot stay in the Infinity Cache anyway -- updateNT, as in smm_solvers.hip)
 template <typename T, bool NT>
-__global__ __launch_bounds__(TPB) void distCgR(int n, DistScal<T>* sc, int par, const T* __restrict__ totalsA, const T* Ap, T* r, T* partsC, int alphaSlot) {
+__global__ __launch_bounds__(TPB) void distCgR(int n, Scal<T>* sc, int par, const T* __restrict__ totalsA, const T* Ap, T* r, T* partsC, int alphaSlot) {
 	__shared__ T red[4];
-	const int done = sc->done;
-	if (blockIdx.x == 0 && threadIdx.x == 0) sc->pad = done;
-	if (done) return;
-	const T alpha = sc->rrPing[par] / totalsA[0];
-	if (blockIdx.x == 0 && threadIdx.x == 0) {
-		sc->alpha = alpha;
-		sc->alphaRing[alphaSlot] = alpha;
-	}
-	T acc = T(0);
-	const T* const in[2] = {Ap, r};
-	T* const out[1] = {r};
-	streamMap<T, NT, 2, 1>(n, in, out, [&](const T(&v)[2], T(&o)[1]) {
-		const T ri = smmFma(-alpha, v[0], v[1]);
-		o[0] = ri;
-		acc += ri * ri;
-	});
-	const T s0 = blockSum256(acc, red);
-	if (threadIdx.x == 0) partsC[blockIdx.x] = s0;
+	if (cgSnapshotDone(sc)) return;
+	cgStepR<T, NT>(n, sc, sc->rrPing[par], totalsA[0], red, Ap, r, partsC, alphaSlot);
 }
 
 // x = alpha p + xcur   (ref:2372)
 template <typename T, bool NT>
-__global__ __launch_bounds__(TPB) void distCgX(int n, const DistScal<T>* __restrict__ sc, const T* p, const T* xcur, T* x) {
+__global__ __launch_bounds__(TPB) void distCgX(int n, const Scal<T>* __restrict__ sc, const T* p, const T* xcur, T* x) {
 	if (sc->done) return;
 	const T alpha = sc->alpha;
 	const T* const in[2] = {p, xcur};
@@ -2019,7 +1917,7 @@ __global__ __launch_bounds__(TPB) void distCgX(int n, const DistScal<T>* __restr
 
 // convergence test, beta, p = beta p + r   (ref:2377-2394).  book: as in distBicgP
 template <typename T, bool NT>
-__global__ __launch_bounds__(TPB) void distCgP(RowRanges rg, int book, DistScal<T>* sc, int par, const T* __restrict__ totalsC, T eps, T* p, const T* r) {
+__global__ __launch_bounds__(TPB) void distCgP(RowRanges rg, int book, Scal<T>* sc, int par, const T* __restrict__ totalsC, T eps, T* p, const T* r) {
 	if (sc->done) return;
 	const T rrNew = totalsC[0];
 	const T rrOld = sc->rrPing[par];
@@ -2038,116 +1936,26 @@ __global__ __launch_bounds__(TPB) void distCgP(RowRanges rg, int book, DistScal<
 	const T beta = rrNew / rrOld;
 	const T* const in[2] = {p, r};
 	T* const out[1] = {p};
-	rangesMap<T, 2, 1, NT>(rg, in, out, [&](const T(&v)[2], T(&o)[1]) { o[0] = smmFma(beta, v[0], v[1]); });
+	rg.map<T, 2, 1, NT>(in, out, [&](const T(&v)[2], T(&o)[1]) { o[0] = smmFma(beta, v[0], v[1]); });
 }
 
-// The deferred x update of the single-GPU loop (smm_solvers.hip, cgLazyXP) in the row-partitioned one: nothing inside the loop reads x
-// (ref:2362-2366), so the last LAZY_M directions stay in a ring of halo-extended vectors and x is brought up to date every LAZY_M-th
-// iteration, in the last planned one and by the launch that finds the iteration converged -- x = alpha_k p_k + (... + (alpha_{k-M+1}
-// p_{k-M+1} + x)): the reference's roundings in the reference's order.  11 vector passes per iteration become 9.125.  Range-aware like
-// distCgP (boundary rows first, then the bulk: each launch flushes its own rows).
-template <typename T>
-struct DistRing {
-	T* p[LAZY_M + 1];  // the owned part of every ring vector
-};
-
-template <typename T, bool NT, int PENDING, bool PUPD>
-__device__ __forceinline__ void distLazyFlush(const RowRanges& rg, const DistRing<T>& ring, int cur, const T (&alpha)[LAZY_M], T beta, const T* r, const T* xcur, T* x) {
-	const T* in[PENDING + 2];
-	in[0] = xcur;
-#pragma unroll
-	for (int k = 0; k < PENDING; ++k) in[1 + k] = ring.p[(cur + (LAZY_M + 1) - (PENDING - 1 - k)) % (LAZY_M + 1)];
-	in[PENDING + 1] = PUPD ? r : xcur;  // (without the p update r is not read: any valid vector)
-	T* out[2] = {x, ring.p[(cur + 1) % (LAZY_M + 1)]};
-	rangesMap<T, PENDING + 2, PUPD ? 2 : 1, NT>(rg, in, out, [&](const T(&v)[PENDING + 2], T(&o)[PUPD ? 2 : 1]) {
-		T xv = v[0];
-#pragma unroll
-		for (int k = 0; k < PENDING; ++k) xv = smmFma(alpha[LAZY_M - PENDING + k], v[1 + k], xv);  // oldest direction first, ref:2372
-		o[0] = xv;
-		if constexpr (PUPD) o[1] = smmFma(beta, v[PENDING], v[PENDING + 1]);
-	});
-}
-
-// convergence test, beta, p_next = beta p_cur + r (ref:2377-2394); x completed when `flush` (host: every LAZY_M-th iteration and the last
-// planned one) or when the iteration converged.  pending: directions not yet in x, this iteration's included.  book: as in distCgP
+// The deferred x update of the single-GPU loop (cgLazyStep, smm_krylov_steps.h) in the row-partitioned one: the ring's vectors are
+// halo-extended, 11 vector passes per iteration become 9.125.  Range-aware like distCgP (boundary rows first, then the bulk: each launch
+// flushes its own rows).
 template <typename T, bool NT>
-__global__ __launch_bounds__(TPB) void distCgLazyP(RowRanges rg, int book, DistScal<T>* sc, int par, const T* __restrict__ totalsC, T eps, DistRing<T> ring, int cur,
+__global__ __launch_bounds__(TPB) void distCgLazyP(RowRanges rg, int book, Scal<T>* sc, int par, const T* __restrict__ totalsC, T eps, LazyRing<T> ring, int cur,
                                                    int pending, int flush, int alphaSlot, const T* r, const T* xcur, T* x) {
-	if (sc->pad) return;  // (`done` as distCgR found it: workgroup 0 of THIS launch may be setting it while others start -- and their rows still need the flush)
-	const T rrNew = totalsC[0];
-	const T rrOld = sc->rrPing[par];
-	const bool converged = eps * eps > rrNew;
-	T alpha[LAZY_M];  // alpha[LAZY_M - 1] = this iteration's, alpha[LAZY_M - 2] the one before, ...
-#pragma unroll
-	for (int k = 0; k < LAZY_M; ++k) alpha[LAZY_M - 1 - k] = sc->alphaRing[(alphaSlot + LAZY_M - k) % LAZY_M];
-	if (book && blockIdx.x == 0 && threadIdx.x == 0) {
-		sc->iters += 1;
-		sc->res = rrNew;
-		if (converged) {
-			sc->done = 1;
-			sc->status = SMM_SOLVER_SUCCESS;
-		} else {
-			sc->rrPing[par ^ 1] = rrNew;
-		}
-	}
-	const T beta = rrNew / rrOld;
-	if (!(flush || converged)) {
-		const T* const in[2] = {ring.p[cur], r};
-		T* const out[1] = {ring.p[(cur + 1) % (LAZY_M + 1)]};
-		rangesMap<T, 2, 1, NT>(rg, in, out, [&](const T(&v)[2], T(&o)[1]) { o[0] = smmFma(beta, v[0], v[1]); });
-		return;
-	}
-	static_assert(LAZY_M == 8, "the cases below");
-#define SMM_DIST_LAZY_CASE(P)                                                                  \
-	case P:                                                                                    \
-		if (converged) distLazyFlush<T, NT, P, false>(rg, ring, cur, alpha, beta, r, xcur, x);     \
-		else distLazyFlush<T, NT, P, true>(rg, ring, cur, alpha, beta, r, xcur, x);                \
-		break;
-	switch (pending) {
-		SMM_DIST_LAZY_CASE(1)
-		SMM_DIST_LAZY_CASE(2)
-		SMM_DIST_LAZY_CASE(3)
-		SMM_DIST_LAZY_CASE(4)
-		SMM_DIST_LAZY_CASE(5)
-		SMM_DIST_LAZY_CASE(6)
-		SMM_DIST_LAZY_CASE(7)
-		SMM_DIST_LAZY_CASE(8)
-	default: break;
-	}
-#undef SMM_DIST_LAZY_CASE
+	if (sc->pad) return;
+	cgLazyStep<T, NT>(rg, book, sc, par, totalsC[0], eps, ring, cur, pending, flush, alphaSlot, r, xcur, x);
 }
 
-// what is left of distCgLazyP once the direction is formed in the SpMV: x, brought up to date when scheduled (every LAZY_M-th iteration)
-// or when the SpMV launch in front found its predecessor converged (flushIter == iter) -- cgLazyFlushOnly of smm_solvers.hip
+// what is left of distCgLazyP once the direction is formed in the SpMV
 template <typename T, bool NT>
-__global__ __launch_bounds__(TPB) void distCgFlushOnly(RowRanges rg, const DistScal<T>* __restrict__ sc, DistRing<T> ring, int cur, int pending, int scheduled, int iter,
+__global__ __launch_bounds__(TPB) void distCgFlushOnly(RowRanges rg, const Scal<T>* __restrict__ sc, LazyRing<T> ring, int cur, int pending, int scheduled, int iter,
                                                        int alphaSlot, const T* xcur, T* x) {
-	const bool converged = sc->flushIter == iter;
-	if (!converged && (!scheduled || sc->done)) return;
-	T alpha[LAZY_M];
-#pragma unroll
-	for (int k = 0; k < LAZY_M; ++k) alpha[LAZY_M - 1 - k] = sc->alphaRing[(alphaSlot + LAZY_M - k) % LAZY_M];
-	static_assert(LAZY_M == 8, "the cases below");
-	switch (pending) {
-	case 1: distLazyFlush<T, NT, 1, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 2: distLazyFlush<T, NT, 2, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 3: distLazyFlush<T, NT, 3, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 4: distLazyFlush<T, NT, 4, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 5: distLazyFlush<T, NT, 5, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 6: distLazyFlush<T, NT, 6, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 7: distLazyFlush<T, NT, 7, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 8: distLazyFlush<T, NT, 8, false>(rg, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	default: break;
-	}
+	cgFlushOnlyStep<T, NT>(rg, sc, ring, cur, pending, scheduled, iter, alphaSlot, xcur, x);
 }
 
-#define SMM_DIST_UPDATE(KERNEL, NTFLAG, GRID, STREAM, ...)                       \
-	do {                                                                        \
-		if (NTFLAG) KERNEL<T, true><<<(GRID), TPB, 0, (STREAM)>>>(__VA_ARGS__);  \
-		else KERNEL<T, false><<<(GRID), TPB, 0, (STREAM)>>>(__VA_ARGS__);        \
-	} while (0)
-
-static int gridFor(long long n) { return solverGrid(n); }  // (smm_solver_host.h)
 // Leaving the loop early must be the SAME decision on every rank (a rank that stops issuing iterations while another goes on leaves the
 // other one alone in its next collective).  The `done` flag is formed from all-reduced -- hence identical -- numbers at the same
 // iteration on every rank, so a BLOCKING read of it at fixed iteration numbers is consistent; the asynchronous mailbox of the single-GPU
@@ -2246,7 +2054,7 @@ static int distBicgstab(smm_hip_dist_csr* D, const T* b, T* x, int maxIterations
 	T *pExt = static_cast<T*>(D->pExt), *sExt = static_cast<T*>(D->sExt), *xExt = static_cast<T*>(D->xExt);
 	T *p = pExt + D->ownOffset, *sv = sExt + D->ownOffset;
 	T *partsA = static_cast<T*>(D->partsA), *partsB = static_cast<T*>(D->partsB), *partsC = static_cast<T*>(D->partsC);
-	auto* sc = static_cast<DistScal<T>*>(D->sc);
+	auto* sc = static_cast<Scal<T>*>(D->sc);
 	if (pre && !D->scratch) SMM_TRY(devAlloc(&D->scratch, static_cast<size_t>(std::max(1, n)) * sizeof(T)));
 	T* scratch = static_cast<T*>(D->scratch);
 	hipEvent_t ev = nullptr;
@@ -2293,7 +2101,7 @@ static int distBicgstab(smm_hip_dist_csr* D, const T* b, T* x, int maxIterations
 		SMM_TRY(allreduceTotals<T>(D, partsA, 1, s, &ev, 0, doneFlag));
 		SMM_TRY(join(s, ev));
 		SMM_TRY((updateThenExchange<T>(D, sExt, 1, s, [&](const RowRanges& rg, int book) {
-			distBicgS<T><<<gridFor(rg.rows()), TPB, 0, s>>>(rg, book, sc, par, partsA + PARTS_TOTALS, ap, r, sv);
+			distBicgS<T><<<solverGrid(rg.rows()), TPB, 0, s>>>(rg, book, sc, par, partsA + PARTS_TOTALS, ap, r, sv);
 		})));
 		// as = [M^-1] A s ; as.as, as.s (ref:2249-2261)
 		if (jacobiDiag) {
@@ -2315,23 +2123,23 @@ static int distBicgstab(smm_hip_dist_csr* D, const T* b, T* x, int maxIterations
 			distBicgR<T><<<NPART, TPB, 0, s>>>(n, sc, partsB + PARTS_TOTALS, sv, as, r0, r, partsC);
 			distFinishSums<T><<<1, TPB, 0, s>>>(partsC, 2, partsC + PARTS_TOTALS, doneFlag);
 			SMM_TRY(allreduceTotals<T>(D, partsC, 2, s, &ev, 2, doneFlag));  // (the communicator's collectives: on the side stream ...
-			distBicgX<T><<<gridFor(n), TPB, 0, s>>>(n, sc, p, sv, x);         // ... while x is updated)
+			distBicgX<T><<<solverGrid(n), TPB, 0, s>>>(n, sc, p, sv, x);         // ... while x is updated)
 		}
 		SMM_TRY(join(s, ev));
 		if (i + 1 < planned) {
 			SMM_TRY((updateThenExchange<T>(D, pExt, 0, s, [&](const RowRanges& rg, int book) {
-				distBicgP<T><<<gridFor(rg.rows()), TPB, 0, s>>>(rg, book, sc, par, partsC + PARTS_TOTALS, eps, ap, r, p);
+				distBicgP<T><<<solverGrid(rg.rows()), TPB, 0, s>>>(rg, book, sc, par, partsC + PARTS_TOTALS, eps, ap, r, p);
 			})));
 		} else {
 			RowRanges all{};
 			all.n = 1;
 			all.hi[0] = n;
-			distBicgP<T><<<gridFor(n), TPB, 0, s>>>(all, 1, sc, par, partsC + PARTS_TOTALS, eps, ap, r, p);  // the last pass: no SpMV follows
+			distBicgP<T><<<solverGrid(n), TPB, 0, s>>>(all, 1, sc, par, partsC + PARTS_TOTALS, eps, ap, r, p);  // the last pass: no SpMV follows
 		}
 	}
 	SMM_TRY(distExchangeDrain<T>(D, pExt, s));  // (left early: the exchange posted for the pass that never ran)
 	SMM_HIP_TRY(hipGetLastError());
-	DistScal<T> h;
+	Scal<T> h;
 	unsigned long long p2pErr = 0;
 	SMM_HIP_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, s));
 	SMM_TRY(p2pPostErrRead(D, &p2pErr, s));
@@ -2367,12 +2175,12 @@ static int distCg(smm_hip_dist_csr* D, const T* b, const T* x0, T* x, int maxIte
 	T *pExt = static_cast<T*>(D->pExt), *xExt = static_cast<T*>(D->xExt);
 	T* p = pExt + D->ownOffset;
 	T *partsA = static_cast<T*>(D->partsA), *partsC = static_cast<T*>(D->partsC);
-	auto* sc = static_cast<DistScal<T>*>(D->sc);
+	auto* sc = static_cast<Scal<T>*>(D->sc);
 	hipEvent_t ev = nullptr;
 	// vectors beyond the caches: x deferred through a ring of LAZY_M more direction vectors (distCgLazyP); when they cannot be had, the eager loop
 	bool lazy = n > 0 && static_cast<long long>(n) * static_cast<long long>(sizeof(T)) >= cgLazyMinBytes();
 	T* ringExt[LAZY_M + 1] = {pExt};
-	DistRing<T> ring{};
+	LazyRing<T> ring{};
 	ring.p[0] = p;
 	if (lazy) {
 		const size_t eb = static_cast<size_t>(std::max(1, D->extLen)) * sizeof(T);
@@ -2494,12 +2302,12 @@ static int distCg(smm_hip_dist_csr* D, const T* b, const T* x0, T* x, int maxIte
 					fm.segs = segs;
 					SMM_TRY(launchThinRemote<T>(D, curExt, false, ap, 1, pc, partsA, doneFlag, s, &fm));
 				}
-				SMM_DIST_UPDATE(distCgFlushOnly, updateNT(n, sizeof(T), 5), gridFor(n), s, allRows, sc, ring, prev, (i - 1) % LAZY_M + 1, i % LAZY_M == 0 ? 1 : 0, i,
+				SMM_LAUNCH_UPDATE(distCgFlushOnly, updateNT(n, sizeof(T), 5), solverGrid(n), s, allRows, sc, ring, prev, (i - 1) % LAZY_M + 1, i % LAZY_M == 0 ? 1 : 0, i,
 				                (i - 1) % LAZY_M, i <= LAZY_M ? x0 : x, x);
 			}
 			SMM_TRY(allreduceTotals<T>(D, partsA, 1, s, &ev, 0, doneFlag));
 			SMM_TRY(join(s, ev));
-			SMM_DIST_UPDATE(distCgR, nt3, NPART, s, n, sc, par, partsA + PARTS_TOTALS, ap, r, partsC, i % LAZY_M);
+			SMM_LAUNCH_UPDATE(distCgR, nt3, NPART, s, n, sc, par, partsA + PARTS_TOTALS, ap, r, partsC, i % LAZY_M);
 			if (!D->p2p) distFinishSums<T><<<1, TPB, 0, s>>>(partsC, 1, partsC + PARTS_TOTALS, doneFlag);
 			SMM_TRY(allreduceTotals<T>(D, partsC, 1, s, &ev, 2, doneFlag));
 			const bool lastPass = i + 1 >= maxIterations;
@@ -2509,7 +2317,7 @@ static int distCg(smm_hip_dist_csr* D, const T* b, const T* x0, T* x, int maxIte
 			}
 			SMM_TRY(join(s, ev));
 			if (lastPass) {  // the last planned iteration has no SpMV' behind it: its bookkeeping and the rest of x
-				SMM_DIST_UPDATE(distCgLazyP, nt3, gridFor(n), s, allRows, 1, sc, par, partsC + PARTS_TOTALS, eps, ring, cur, i % LAZY_M + 1, 1, i % LAZY_M, r,
+				SMM_LAUNCH_UPDATE(distCgLazyP, nt3, solverGrid(n), s, allRows, 1, sc, par, partsC + PARTS_TOTALS, eps, ring, cur, i % LAZY_M + 1, 1, i % LAZY_M, r,
 				                i < LAZY_M ? x0 : x, x);
 			}
 			continue;
@@ -2518,10 +2326,10 @@ static int distCg(smm_hip_dist_csr* D, const T* b, const T* x0, T* x, int maxIte
 		SMM_TRY(distMatvecCompute<T>(D, curExt, SMM_OP_ASSIGN, nullptr, ap, 1, pc, partsA, doneFlag, s, nullptr, 0, SPMV_HALF_TILES));  // Ap = A p ; p.Ap, ref:2353-2354
 		SMM_TRY(allreduceTotals<T>(D, partsA, 1, s, &ev, 0, doneFlag));
 		SMM_TRY(join(s, ev));
-		SMM_DIST_UPDATE(distCgR, nt3, NPART, s, n, sc, par, partsA + PARTS_TOTALS, ap, r, partsC, i % LAZY_M);
+		SMM_LAUNCH_UPDATE(distCgR, nt3, NPART, s, n, sc, par, partsA + PARTS_TOTALS, ap, r, partsC, i % LAZY_M);
 		if (!D->p2p) distFinishSums<T><<<1, TPB, 0, s>>>(partsC, 1, partsC + PARTS_TOTALS, doneFlag);
 		SMM_TRY(allreduceTotals<T>(D, partsC, 1, s, &ev, 2, doneFlag));           // (the communicator's collectives: on the side stream ...
-		if (!lazy) SMM_DIST_UPDATE(distCgX, nt3, gridFor(n), s, n, sc, pc, i == 0 ? x0 : x, x);  // ... while x is updated; ref:2351, 2395)
+		if (!lazy) SMM_LAUNCH_UPDATE(distCgX, nt3, solverGrid(n), s, n, sc, pc, i == 0 ? x0 : x, x);  // ... while x is updated; ref:2351, 2395)
 		SMM_TRY(join(s, ev));
 		const bool last = i + 1 >= maxIterations;
 		RowRanges all{};
@@ -2532,7 +2340,7 @@ static int distCg(smm_hip_dist_csr* D, const T* b, const T* x0, T* x, int maxIte
 			const int flush = (pending == LAZY_M || last) ? 1 : 0;
 			const T* xc = i < LAZY_M ? x0 : x;  // (until the first scheduled flush x has not been written: ref:2351, 2395)
 			auto launch = [&](const RowRanges& rg, int book) {
-				SMM_DIST_UPDATE(distCgLazyP, nt3, gridFor(rg.rows()), s, rg, book, sc, par, partsC + PARTS_TOTALS, eps, ring, cur, pending, flush, i % LAZY_M, r, xc, x);
+				SMM_LAUNCH_UPDATE(distCgLazyP, nt3, solverGrid(rg.rows()), s, rg, book, sc, par, partsC + PARTS_TOTALS, eps, ring, cur, pending, flush, i % LAZY_M, r, xc, x);
 			};
 			if (!last) {
 				SMM_TRY((updateThenExchange<T>(D, ringExt[next], 0, s, launch)));
@@ -2542,15 +2350,15 @@ static int distCg(smm_hip_dist_csr* D, const T* b, const T* x0, T* x, int maxIte
 			}
 		} else if (!last) {
 			SMM_TRY((updateThenExchange<T>(D, pExt, 0, s, [&](const RowRanges& rg, int book) {
-				SMM_DIST_UPDATE(distCgP, nt3, gridFor(rg.rows()), s, rg, book, sc, par, partsC + PARTS_TOTALS, eps, p, r);
+				SMM_LAUNCH_UPDATE(distCgP, nt3, solverGrid(rg.rows()), s, rg, book, sc, par, partsC + PARTS_TOTALS, eps, p, r);
 			})));
 		} else {
-			SMM_DIST_UPDATE(distCgP, nt3, gridFor(n), s, all, 1, sc, par, partsC + PARTS_TOTALS, eps, p, r);
+			SMM_LAUNCH_UPDATE(distCgP, nt3, solverGrid(n), s, all, 1, sc, par, partsC + PARTS_TOTALS, eps, p, r);
 		}
 	}
 	SMM_TRY(distExchangeDrain<T>(D, lastExt, s));
 	SMM_HIP_TRY(hipGetLastError());
-	DistScal<T> h;
+	Scal<T> h;
 	unsigned long long p2pErr = 0;
 	SMM_HIP_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, s));
 	SMM_TRY(p2pPostErrRead(D, &p2pErr, s));

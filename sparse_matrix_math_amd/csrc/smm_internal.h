@@ -494,7 +494,7 @@ void preloadSplitUnit();
 // direction written to pNew, p.Ap into `partials`; `sc` is the solver's Scal<T>.  constMarchFusable: the matrix is served by the 2.5-D
 // constant-diagonal kernel in the form this exists for; the launch returns false when it could not be made (the caller must not have
 // relied on it: ask constMarchFusable first).
-// the words of the solver's scalar block the fused launch does its bookkeeping in (Scal<T> on one GPU, DistScal<T> in smm_dist.hip)
+// the words of the solver's scalar block the fused launch does its bookkeeping in (Scal<T>, smm_solver_scal.h: the single-GPU and the row-partitioned loop alike)
 template <typename T>
 struct CgFuseBook {
 	const int* pad = nullptr;  // the done flag as the update before found it

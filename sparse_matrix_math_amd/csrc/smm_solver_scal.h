@@ -1,5 +1,6 @@
 // smm_solver_scal.h -- the recurrence scalars of the device-resident Krylov loops and the fixed-order sums of their partials: shared by the
-// update kernels (smm_solvers.hip) and the SpMV kernel that forms CG's next direction in its own load phase (smm_spmv_march.hip).
+// steps of the CG and BiCGStab loops (smm_krylov_steps.h; their kernels are in smm_solvers.hip and smm_dist.hip), the other solver units and
+// the SpMV kernel that forms CG's next direction in its own load phase (smm_spmv_march.hip).
 #pragma once
 #include "smm_device.h"
 #include "smm_internal.h"
@@ -7,7 +8,7 @@
 namespace smm {
 
 constexpr int SCAL_TPB = 256;
-// ConjugateGradient with the deferred x update (smm_solvers.hip cgLazyXP, smm_dist.hip distCgLazyP): directions kept before x is brought up to date
+// ConjugateGradient with the deferred x update (smm_krylov_steps.h cgLazyStep): directions kept before x is brought up to date
 constexpr int LAZY_M = 8;
 
 template <typename T>
@@ -43,6 +44,12 @@ __device__ __forceinline__ T sumPartsAll(const T* __restrict__ partials, T* red5
 	const T v = red5[4];
 	__syncthreads();
 	return v;
+}
+
+// the correctly rounded square root of the residual norm (ref:2268)
+template <typename T>
+__device__ __forceinline__ T sqrtRn(T v) {
+	return sizeof(T) == 4 ? static_cast<T>(__fsqrt_rn(static_cast<float>(v))) : static_cast<T>(__dsqrt_rn(static_cast<double>(v)));
 }
 
 // the start of BiCGStab (ref:2231) and of ConjugateGradientSquared (ref:2128): rr0 = r.r0 ; iterations = 0 (one workgroup)

@@ -18,8 +18,8 @@
 
 #include "smm_device.h"
 #include "smm_internal.h"
+#include "smm_krylov_steps.h"
 #include "smm_solver_host.h"
-#include "smm_solver_scal.h"
 
 namespace smm {
 
@@ -135,24 +135,9 @@ template <typename T, bool NT>
 __global__ __launch_bounds__(TPB) void cgFusedR(int n, Scal<T>* sc, int par, const T* __restrict__ partsA, const T* Ap, T* r,
                                                 T* __restrict__ partsC, int alphaSlot) {
 	__shared__ T red[5];
-	const int done = sc->done;
-	if (blockIdx.x == 0 && threadIdx.x == 0) sc->pad = done;
-	if (done) return;
-	const T alpha = sc->rrPing[par] / sumPartsAll(partsA, red);
-	if (blockIdx.x == 0 && threadIdx.x == 0) {
-		sc->alpha = alpha;
-		sc->alphaRing[alphaSlot] = alpha;
-	}
-	T acc = T(0);
-	const T* const in[2] = {Ap, r};
-	T* const out[1] = {r};
-	streamMap<T, NT, 2, 1>(n, in, out, [&](const T(&v)[2], T(&o)[1]) {
-		const T ri = smmFma(-alpha, v[0], v[1]);
-		o[0] = ri;
-		acc += ri * ri;
-	});
-	const T s = blockSum256(acc, red);
-	if (threadIdx.x == 0) partsC[blockIdx.x] = s;
+	if (cgSnapshotDone(sc)) return;
+	const T rr = sc->rrPing[par];
+	cgStepR<T, NT>(n, sc, rr, sumPartsAll(partsA, red), red, Ap, r, partsC, alphaSlot);
 }
 
 // x = alpha p + xcur ; convergence test ; beta ; p = beta p + r   (ref:2362-2394: x is updated before the test, p only when the loop goes on)
@@ -191,123 +176,34 @@ __global__ __launch_bounds__(TPB) void cgFusedXP(int n, Scal<T>* sc, int par, co
 }
 
 // ---- the x update deferred (r05) ------------------------------------------------------------------------------------------------
-// For vectors that do not fit the caches an iteration of CG is 10 vector passes, 5 of them in cgFusedXP (read p, x, r; write x, p).  x is
-// only an accumulator: x_{k+1} = alpha_k p_k + x_k (ref:2362-2366).  Keeping the last LAZY_M directions in a ring, x is brought up to date
-// every LAZY_M-th iteration -- x = alpha_k p_k + (... + (alpha_{k-M+1} p_{k-M+1} + x)): the reference's roundings in the reference's order,
-// bit for bit -- in the launch that forms the next p anyway: (3 (M - 1) + M + 4) / M = 4 + 1 / M passes per iteration instead of 5 (M = 8:
-// 4.125; with p formed inside the SpMV the flush is a launch of its own, (M + 2) / M = 1.25), at the price of M more vectors of device memory.  The launch that finds the iteration converged -- or is told it is the last -- flushes
-// whatever is pending, so x is complete whenever the loop ends.
-template <typename T>
-struct LazyRing {
-	T* p[LAZY_M + 1];
-};
-
-// PENDING directions (this iteration's included) are applied to x when FLUSH; p_next = beta p_cur + r unless the iteration converged
-template <typename T, bool NT, int PENDING, bool PUPD>
-__device__ __forceinline__ void cgLazyFlush(int n, const LazyRing<T>& ring, int cur, const T (&alpha)[LAZY_M], T beta, const T* r, const T* xcur, T* x) {
-	// inputs: x, p_cur-PENDING+1 .. p_cur (oldest first) [, r]; outputs: x [, p_next]
-	const T* in[PENDING + 2];
-	in[0] = xcur;
-#pragma unroll
-	for (int k = 0; k < PENDING; ++k) in[1 + k] = ring.p[(cur + (LAZY_M + 1) - (PENDING - 1 - k)) % (LAZY_M + 1)];
-	in[PENDING + 1] = PUPD ? r : xcur;  // (without the p update r is not read: any valid vector)
-	T* out[2] = {x, ring.p[(cur + 1) % (LAZY_M + 1)]};
-	streamMap<T, NT, PENDING + 2, PUPD ? 2 : 1>(n, in, out, [&](const T(&v)[PENDING + 2], T(&o)[PUPD ? 2 : 1]) {
-		T xv = v[0];
-#pragma unroll
-		for (int k = 0; k < PENDING; ++k) xv = smmFma(alpha[LAZY_M - PENDING + k], v[1 + k], xv);  // oldest direction first
-		o[0] = xv;
-		if (PUPD) o[1] = smmFma(beta, v[PENDING], v[PENDING + 1]);
-	});
-}
-
-// convergence test ; beta ; p_next = beta p_cur + r ; x brought up to date when `flush` (host: every LAZY_M-th iteration and the last one)
-// or when the iteration converged.  pending = directions not yet applied to x, this iteration's included (1 .. LAZY_M).
+// For vectors that do not fit the caches an iteration of CG is 10 vector passes, 5 of them in cgFusedXP (read p, x, r; write x, p).  With
+// the last LAZY_M directions kept in a ring (LazyRing, cgLazyStep: smm_krylov_steps.h) x is brought up to date every LAZY_M-th iteration in
+// the launch that forms the next p anyway: (3 (M - 1) + M + 4) / M = 4 + 1 / M passes per iteration instead of 5 (M = 8: 4.125; with p formed
+// inside the SpMV the flush is a launch of its own, (M + 2) / M = 1.25), at the price of M more vectors of device memory.
 template <typename T, bool NT>
 __global__ __launch_bounds__(TPB) void cgLazyXP(int n, Scal<T>* sc, int par, const T* __restrict__ partsC, T eps, LazyRing<T> ring, int cur, int pending, int flush,
                                                 int alphaSlot, const T* r, const T* xcur, T* x) {
 	__shared__ T red[5];
 	if (sc->pad) return;
-	const T rrNew = sumPartsAll(partsC, red);
-	const T rrOld = sc->rrPing[par];
-	const bool converged = eps * eps > rrNew;
-	T alpha[LAZY_M];  // alpha[LAZY_M - 1] = this iteration's, alpha[LAZY_M - 2] the one before, ...
-#pragma unroll
-	for (int k = 0; k < LAZY_M; ++k) alpha[LAZY_M - 1 - k] = sc->alphaRing[(alphaSlot + LAZY_M - k) % LAZY_M];
-	if (blockIdx.x == 0 && threadIdx.x == 0) {
-		sc->iters += 1;
-		sc->res = rrNew;
-		if (converged) {
-			sc->done = 1;
-			sc->status = SMM_SOLVER_SUCCESS;
-		} else {
-			sc->rrPing[par ^ 1] = rrNew;
-		}
-	}
-	const T beta = rrNew / rrOld;
-	if (!(flush || converged)) {
-		const T* const in[2] = {ring.p[cur], r};
-		T* const out[1] = {ring.p[(cur + 1) % (LAZY_M + 1)]};
-		streamMap<T, NT, 2, 1>(n, in, out, [&](const T(&v)[2], T(&o)[1]) { o[0] = smmFma(beta, v[0], v[1]); });
-		return;
-	}
-#define SMM_LAZY_CASE(P)                                                                         \
-	case P:                                                                                      \
-		if (converged) cgLazyFlush<T, NT, P, false>(n, ring, cur, alpha, beta, r, xcur, x);      \
-		else cgLazyFlush<T, NT, P, true>(n, ring, cur, alpha, beta, r, xcur, x);                 \
-		break;
-	switch (pending) {
-		SMM_LAZY_CASE(1)
-		SMM_LAZY_CASE(2)
-		SMM_LAZY_CASE(3)
-		SMM_LAZY_CASE(4)
-		SMM_LAZY_CASE(5)
-		SMM_LAZY_CASE(6)
-		SMM_LAZY_CASE(7)
-		SMM_LAZY_CASE(8)
-	default: break;
-	}
-#undef SMM_LAZY_CASE
+	cgLazyStep<T, NT>(WholeRows{n}, true, sc, par, sumPartsAll(partsC, red), eps, ring, cur, pending, flush, alphaSlot, r, xcur, x);
 }
 
-// With the next direction formed inside the SpMV (launchConstMarchFusedP) nothing is left of cgLazyXP but x: this launch sits behind
-// every such SpMV and completes x when it is scheduled (every LAZY_M-th iteration) or when that SpMV found its predecessor converged
-// (flushIter == iter: one shot -- the launches enqueued behind a finished solve find another number there).  pending directions end at
-// ring slot `cur`; alphaSlot: the ring position of the newest one's alpha.
 template <typename T, bool NT>
 __global__ __launch_bounds__(TPB) void cgLazyFlushOnly(int n, const Scal<T>* __restrict__ sc, LazyRing<T> ring, int cur, int pending, int scheduled, int iter,
                                                        int alphaSlot, const T* xcur, T* x) {
-	const bool converged = sc->flushIter == iter;
-	if (!converged && (!scheduled || sc->done)) return;
-	T alpha[LAZY_M];
-#pragma unroll
-	for (int k = 0; k < LAZY_M; ++k) alpha[LAZY_M - 1 - k] = sc->alphaRing[(alphaSlot + LAZY_M - k) % LAZY_M];
-	switch (pending) {
-	case 1: cgLazyFlush<T, NT, 1, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 2: cgLazyFlush<T, NT, 2, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 3: cgLazyFlush<T, NT, 3, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 4: cgLazyFlush<T, NT, 4, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 5: cgLazyFlush<T, NT, 5, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 6: cgLazyFlush<T, NT, 6, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 7: cgLazyFlush<T, NT, 7, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	case 8: cgLazyFlush<T, NT, 8, false>(n, ring, cur, alpha, T(0), nullptr, xcur, x); break;
-	default: break;
-	}
+	cgFlushOnlyStep<T, NT>(WholeRows{n}, sc, ring, cur, pending, scheduled, iter, alphaSlot, xcur, x);
 }
 
-// alpha = rr0 / (ap.r0) ; s = -alpha ap + r   (ref:2243-2247)
+// the three update kernels of a BiCGStab iteration (bicgStepS / XR / P, smm_krylov_steps.h); partsA = [ap.r0]
 template <typename T, bool NT>
 __global__ __launch_bounds__(TPB) void bicgFusedS(int n, Scal<T>* sc, int par, const T* __restrict__ partsA, const T* ap, const T* r, T* sv) {
 	__shared__ T red[5];
 	if (sc->done) return;
-	const T alpha = sc->rrPing[par] / sumPartsAll(partsA, red);
-	if (blockIdx.x == 0 && threadIdx.x == 0) sc->alpha = alpha;
-	const T* const in[2] = {ap, r};
-	T* const out[1] = {sv};
-	streamMap<T, NT, 2, 1>(n, in, out, [&](const T(&v)[2], T(&o)[1]) { o[0] = smmFma(-alpha, v[0], v[1]); });
+	const T rr0 = sc->rrPing[par];
+	bicgStepS<T, NT>(WholeRows{n}, true, sc, rr0, sumPartsAll(partsA, red), ap, r, sv);
 }
 
-// omega = (as.s)/(as.as) ; x, r update ; partial ||r||^2 and r.r0   (ref:2259-2269); partsB = [as.as | as.s], partsC = [r.r | r.r0]
+// partsB = [as.as | as.s], partsC = [r.r | r.r0]
 template <typename T, bool NT>
 __global__ __launch_bounds__(TPB) void bicgFusedXR(int n, Scal<T>* sc, const T* __restrict__ partsB, const T* p, const T* sv, const T* as,
                                                    const T* r0, T* x, T* r, T* __restrict__ partsC) {
@@ -315,51 +211,16 @@ __global__ __launch_bounds__(TPB) void bicgFusedXR(int n, Scal<T>* sc, const T* 
 	if (sc->done) return;
 	const T asas = sumPartsAll(partsB, red);
 	const T ass = sumPartsAll(partsB + NPART, red);
-	const T omega = ass / asas;
-	const T alpha = sc->alpha;
-	if (blockIdx.x == 0 && threadIdx.x == 0) sc->omega = omega;
-	T acc0 = T(0), acc1 = T(0);
-	const T* const in[5] = {sv, x, p, as, r0};
-	T* const out[2] = {x, r};
-	streamMap<T, NT, 5, 2>(n, in, out, [&](const T(&v)[5], T(&o)[2]) {
-		const T si = v[0];
-		o[0] = smmFma(alpha, v[2], smmFma(omega, si, v[1]));
-		const T ri = smmFma(-omega, v[3], si);
-		o[1] = ri;
-		acc0 += ri * ri;
-		acc1 += ri * v[4];
-	});
-	const T s0 = blockSum256(acc0, red);
-	const T s1 = blockSum256(acc1, red);
-	if (threadIdx.x == 0) {
-		partsC[blockIdx.x] = s0;
-		partsC[NPART + blockIdx.x] = s1;
-	}
+	bicgStepXR<T, NT, true>(n, sc, asas, ass, red, p, sv, as, r0, x, r, partsC);
 }
 
-// resL2Norm, loop test, beta, p = beta (-omega ap + p) + r   (ref:2268-2277)
 template <typename T, bool NT>
 __global__ __launch_bounds__(TPB) void bicgFusedP(int n, Scal<T>* sc, int par, const T* __restrict__ partsC, T eps, const T* ap, const T* r, T* p) {
 	__shared__ T red[5];
 	if (sc->done) return;
 	const T rr = sumPartsAll(partsC, red);
 	const T newRR0 = sumPartsAll(partsC + NPART, red);
-	const T res = sizeof(T) == 4 ? static_cast<T>(__fsqrt_rn(static_cast<float>(rr))) : static_cast<T>(__dsqrt_rn(static_cast<double>(rr)));
-	const T alpha = sc->alpha;
-	const T omega = sc->omega;
-	const T rr0 = sc->rrPing[par];
-	const bool leave = !(res > eps);  // while (resL2Norm > eps ...): NaN leaves the loop too
-	if (blockIdx.x == 0 && threadIdx.x == 0) {
-		sc->res = res;
-		sc->rrPing[par ^ 1] = newRR0;
-		sc->iters += 1;
-		if (leave) sc->done = 1;
-	}
-	if (leave) return;
-	const T beta = (newRR0 * alpha) / (rr0 * omega);  // ref:2271
-	const T* const in[3] = {ap, p, r};
-	T* const out[1] = {p};
-	streamMap<T, NT, 3, 1>(n, in, out, [&](const T(&v)[3], T(&o)[1]) { o[0] = smmFma(beta, smmFma(-omega, v[0], v[1]), v[2]); });
+	bicgStepP<T, NT>(WholeRows{n}, true, sc, par, rr, newRR0, eps, ap, r, p);
 }
 
 // two dot products that share an operand: partials = a.a, partials2 = a.b

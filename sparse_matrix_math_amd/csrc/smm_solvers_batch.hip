@@ -88,11 +88,6 @@ __device__ __forceinline__ unsigned columnMask(const Scal<T>* sc, int Scal<T>::*
 	return m;
 }
 
-template <typename T>
-__device__ __forceinline__ T sqrtRn(T v) {
-	return sizeof(T) == 4 ? static_cast<T>(__fsqrt_rn(static_cast<float>(v))) : static_cast<T>(__dsqrt_rn(static_cast<double>(v)));
-}
-
 // parts[j][0 .. NPART) = per-workgroup sums of a(:, j) . b(:, j)
 template <typename T, int KC>
 __global__ __launch_bounds__(TPB) void batchDot(int n, const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ parts) {
