@@ -1308,7 +1308,7 @@ int smm_hip_svds_dev_f64(const smm_hip_csr* a, const smm_hip_csr* at, int k, int
  *   very directions wanted.
  * The sums run in a fixed order and nothing uses floating-point atomics: two runs of one call give the same bits.
  * Memory: 6k vectors plus the preconditioner's own.
- * WHAT THIS IS NOT: no generalised problem A x = lambda B x, no interior eigenvalues, no hard locking (a converged column stays in the
+ * WHAT THIS IS NOT: the generalised problem A x = lambda B x is smm_hip_lobpcg_gen_*'s (below); no interior eigenvalues, no hard locking (a converged column stays in the
  *   Rayleigh-Ritz basis and only stops producing a residual direction), no column-major SpMM: A W is |active| SpMVs.
  * SMM_HIP_ERR_INVALID (the message starts with "lobpcg:"; checked before the device is touched, the outputs are not written): a null or
  * dtype-mismatched matrix, a matrix that is not square, k < 0 or k > SMM_LOBPCG_MAX_K, 3k > rows (a matrix that small is dense work, or
@@ -1316,6 +1316,7 @@ int smm_hip_svds_dev_f64(const smm_hip_csr* a, const smm_hip_csr* at, int k, int
  * preconditioner of a kind smm_hip_cg_* refuses other than JACOBI and SGS, of the other dtype or of another size. */
 #define SMM_LOBPCG_MAX_K 8
 #define SMM_LOBPCG_MAX_BASIS 24
+#define SMM_LOBPCG_MAX_BASES 3
 int smm_hip_lobpcg_f32(const smm_hip_csr* a, int k, int which, int maxIterations, float tol, const smm_hip_precond* M, const float* X0, long long ldx0,
                        unsigned long long seed, float* eigenvalues, float* eigenvectors, long long ldx, float* residuals, int* nconv, int* iterations, int* matvecs,
                        int* applies, int* solver_status);
@@ -1328,6 +1329,55 @@ int smm_hip_lobpcg_dev_f32(const smm_hip_csr* a, int k, int which, int maxIterat
 int smm_hip_lobpcg_dev_f64(const smm_hip_csr* a, int k, int which, int maxIterations, double tol, const smm_hip_precond* M, const double* d_X0, long long ldx0,
                            unsigned long long seed, double* d_eigenvalues, double* d_eigenvectors, long long ldx, smm_hip_stream stream, double* residuals, int* nconv,
                            int* iterations, int* matvecs, int* applies, int* solver_status);
+
+/* smm_hip_lobpcg_gen_*: the GENERALISED symmetric eigenproblem A x = lambda B x by the loop of smm_hip_lobpcg_* -- the vibration modes
+ * K x = lambda M x of a finite-element model with its consistent mass matrix are what it is for (csrc/smm_solvers_lobpcg.hip; the
+ * definition, line by line, is tests/lobpcg_gen_restatement.py).  LOBPCG needs neither a factorisation of B nor B^-1: only products with B.
+ * `b` is a symmetric positive definite matrix of a's dtype and size; its symmetry and definiteness are the caller's business, like the
+ * symmetry of `a`.  b == NULL forwards to smm_hip_lobpcg_*: the same bits, bmatvecs = 0.  b == a is legal (every eigenvalue is 1).
+ * Every other parameter and output is smm_hip_lobpcg_*'s; bmatvecs (may be NULL) follows matvecs.
+ * The loop.  BS = [BX BP BW] is a third basis beside S and AS, laid out the same way; BX and BP are carried through every rotation and
+ * never recomputed, like AX and AP.  eps = eps(T):
+ *   start: for j = 0 .. k-1:  w = X0_j (or the hash column);  q = B w;  d0 = sqrt(w . q)
+ *            j > 0, twice:  h = BX[:, 0..j-1]^T w;  w = _smm_fma(-h_i, X_i, w), i ascending
+ *            j > 0:  q = B w
+ *            d = sqrt(w . q);  d0 or d not finite, or !(d > sqrt(eps) d0): DIVERGED
+ *            X_j = w / d;  BX_j = q / d                                                        (2k - 1 products with B)
+ *          AX = A X;  T = X^T AX -> host, the Ritz step of smm_hip_lobpcg_*;  X, AX and BX rotated by C
+ *   for it = 0, 1, ...:
+ *     R_j = AX_j - theta_j BX_j;  rn_j = ||R_j||_2;  bn_j = ||BX_j||_2       (one pass over the two blocks; rn and bn come to the host together)
+ *     scale = max(scale, |theta_i|) over every Ritz value of the last Rayleigh-Ritz step
+ *     active = the j with !(rn_j <= tol * scale * bn_j);  none: SUCCESS;  it == maxIterations: MAX_ITERATIONS_REACHED
+ *     W = M^-1 R[:, active] (or R[:, active]);  AW = A W;  BW = B W, column by column
+ *     twice:
+ *       H = BX^T Z;  Z = Z - X H;  AZ = AZ - AX H;  BZ = BZ - BX H           (smm_hip_multi_block_axpy_bases_dev_*: one launch)
+ *       G = Z^T BZ -> host, 1/2 (G + G^T);  d, the live columns, w, kept and Y exactly as in smm_hip_lobpcg_*
+ *       Z = Z Y, AZ = AZ Y, BZ = BZ Y                                          (smm_hip_multi_rotate_bases_dev_*: one launch)
+ *     T = S^T AS -> host -> C;  [X P], [AX AP] and [BX BP] = S, AS, BS times [C | C_P] exactly as in smm_hip_lobpcg_*
+ *   S is B-orthonormal after the two SVQB passes, so the small problem stays the standard one on T: S^T B S is not formed.
+ *   The host reads four things per iteration: rn with bn, the two G and T.
+ * The eigenvectors returned are B-orthonormal: X^T B X = I.  residuals[j] is the last rn_j.  matvecs counts products with `a` only
+ * (k + the sum of |active|); bmatvecs = 2k - 1 + the sum of |active|.
+ * DIVERGED is smm_hip_lobpcg_*'s, and also a bn_j, or a start w . q, that is not finite or not positive: B = -I ends DIVERGED at the start
+ *   with nothing written.  An indefinite B that slips past the start is NOT promised to be detected: the answer is then meaningless.
+ * M approximates A^-1 and must fit `a`: the rule of smm_hip_lobpcg_*, unchanged.
+ * Memory: 9k vectors plus the preconditioner's own.  Fixed-order sums, no floating-point atomics: two runs give the same bits.
+ * WHAT THIS IS NOT: no column-major SpMM (A W and B W are |active| SpMVs each), no indefinite B (buckling problems), no interior
+ *   eigenvalues, no generalised smm_hip_eigsh_*, no hard locking.
+ * SMM_HIP_ERR_INVALID (the message starts with "lobpcg:"; checked before the device is touched, the outputs are not written): everything
+ * smm_hip_lobpcg_* refuses, a `b` of the other dtype, a `b` that is not square, a `b` with other rows than `a`. */
+int smm_hip_lobpcg_gen_f32(const smm_hip_csr* a, const smm_hip_csr* b, int k, int which, int maxIterations, float tol, const smm_hip_precond* M, const float* X0,
+                           long long ldx0, unsigned long long seed, float* eigenvalues, float* eigenvectors, long long ldx, float* residuals, int* nconv, int* iterations,
+                           int* matvecs, int* bmatvecs, int* applies, int* solver_status);
+int smm_hip_lobpcg_gen_f64(const smm_hip_csr* a, const smm_hip_csr* b, int k, int which, int maxIterations, double tol, const smm_hip_precond* M, const double* X0,
+                           long long ldx0, unsigned long long seed, double* eigenvalues, double* eigenvectors, long long ldx, double* residuals, int* nconv, int* iterations,
+                           int* matvecs, int* bmatvecs, int* applies, int* solver_status);
+int smm_hip_lobpcg_gen_dev_f32(const smm_hip_csr* a, const smm_hip_csr* b, int k, int which, int maxIterations, float tol, const smm_hip_precond* M, const float* d_X0,
+                               long long ldx0, unsigned long long seed, float* d_eigenvalues, float* d_eigenvectors, long long ldx, smm_hip_stream stream,
+                               float* residuals, int* nconv, int* iterations, int* matvecs, int* bmatvecs, int* applies, int* solver_status);
+int smm_hip_lobpcg_gen_dev_f64(const smm_hip_csr* a, const smm_hip_csr* b, int k, int which, int maxIterations, double tol, const smm_hip_precond* M, const double* d_X0,
+                               long long ldx0, unsigned long long seed, double* d_eigenvalues, double* d_eigenvectors, long long ldx, smm_hip_stream stream,
+                               double* residuals, int* nconv, int* iterations, int* matvecs, int* bmatvecs, int* applies, int* solver_status);
 
 /* smm_hip_idrs_*: IDR(s) in the biorthogonal form (Sonneveld and van Gijzen 2008; van Gijzen and Sonneveld 2011) with right
  * preconditioning -- an addition, the reference has no IDR(s) (csrc/smm_solvers_idrs.hip; the definition, line by line, is
@@ -1478,6 +1528,23 @@ int smm_hip_multi_block_axpy_dev_f32(int n, int m, int l, const float* d_V, long
                                      smm_hip_stream stream);
 int smm_hip_multi_block_axpy_dev_f64(int n, int m, int l, const double* d_V, long long ldV, const double* d_H, long long ldH, double* d_W, long long ldW,
                                      smm_hip_stream stream);
+
+/* multi_block_axpy and multi_rotate on 1 <= nb <= SMM_LOBPCG_MAX_BASES bases with ONE coefficient matrix in ONE launch (smm_hip_lobpcg_gen_*
+ * updates S, AS and BS by the same small matrix).  d_V and d_W are HOST arrays of nb device pointers, copied into the kernel's arguments:
+ * a grid dimension runs over the bases.  All bases share one ldV and one ldW (one ld for multi_rotate_bases); d_H, h_Y and every other
+ * parameter are the single-basis entry's, and for every i < nb the result on d_V[i] / d_W[i] is bit for bit that of
+ * smm_hip_multi_block_axpy_dev_*(n, m, l, d_V[i], ldV, d_H, ldH, d_W[i], ldW) / smm_hip_multi_rotate_dev_*(n, m, l, d_V[i], ld, h_Y, ldY)
+ * alone: each basis takes the 16-byte path or the element path by its own alignment, and what lies between n and ld is neither read
+ * nor written.  multi_block_axpy_bases is asynchronous on `stream`; multi_rotate_bases stages Y once for all bases and synchronises `stream`.
+ * SMM_HIP_ERR_INVALID (the message starts with "multi_block_axpy_bases:" / "multi_rotate_bases:"; checked before the device is touched):
+ * what the single-basis entry refuses, nb outside 1 .. SMM_LOBPCG_MAX_BASES, a null d_V / d_W, a null entry in either with n > 0, and for
+ * multi_block_axpy_bases any V[i] (m columns) that overlaps any W[j] (l columns). */
+int smm_hip_multi_block_axpy_bases_dev_f32(int n, int m, int l, int nb, const float* const* d_V, long long ldV, const float* d_H, long long ldH, float* const* d_W,
+                                           long long ldW, smm_hip_stream stream);
+int smm_hip_multi_block_axpy_bases_dev_f64(int n, int m, int l, int nb, const double* const* d_V, long long ldV, const double* d_H, long long ldH, double* const* d_W,
+                                           long long ldW, smm_hip_stream stream);
+int smm_hip_multi_rotate_bases_dev_f32(int n, int m, int l, int nb, float* const* d_V, long long ld, const float* h_Y, long long ldY, smm_hip_stream stream);
+int smm_hip_multi_rotate_bases_dev_f64(int n, int m, int l, int nb, double* const* d_V, long long ld, const double* h_Y, long long ldY, smm_hip_stream stream);
 
 /* ---- preconditioners: `int apply(const T* rhs, T* x) const noexcept` (ref:1173-1235) --------------------------
  * create: replaces CSRMatrix<T>::getPreconditioner<kind>() (ref:1643-1651) / IC0Preconditioner::init (ref:1798).

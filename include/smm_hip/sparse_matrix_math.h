@@ -5,7 +5,7 @@
 //     SMM::Vector, SMM::TripletMatrix, SMM::CSRMatrix (init / rMult / rMultAdd / rMultSub / getters / iteration, writable iterators
 //     included / getPreconditioner / operator*= / inplaceAdd / inplaceSubtract / updateEntry / addEntry / zeroValues /
 //     hasSameNonZeroPattern), SMM::SolverStatus, SMM::SolverPreconditioner, SMM::ConjugateGradient (plain and IC0),
-//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::LSQR, SMM::eigsh, SMM::svds, SMM::lobpcg, SMM::IDRs, SMM::loadMatrix
+//     SMM::BiCGStab (plain and preconditioned), SMM::BiCGSymmetric, SMM::ConjugateGradientSquared, SMM::GMRES, SMM::MINRES, SMM::LSQR, SMM::eigsh, SMM::svds, SMM::lobpcg (A x = lambda x and A x = lambda B x), SMM::IDRs, SMM::loadMatrix
 //     (additions: SMM::transpose, SMM::isSymmetric, SMM::BiCG for matrices that are not symmetric; SMM::multiply, SMM::multiplyInto;
 //      SMM::blockMatrix, SMM::blockRefresh, SMM::submatrix, SMM::submatrixRefresh, SMM::diagonal, CSRMatrix::scaleRowsCols;
 //     SMM::add, SMM::addInto; SMM::convert, SMM::IterativeRefinement)
@@ -91,6 +91,10 @@ struct Abi<float> {
 	                  float* x, long long ldx, float* rn, int* nconv, int* iterations, int* matvecs, int* applies, int* st) {
 		return smm_hip_lobpcg_f32(a, k, which, it, tol, M, x0, ldx0, seed, w, x, ldx, rn, nconv, iterations, matvecs, applies, st);
 	}
+	static int lobpcgGen(const smm_hip_csr* a, const smm_hip_csr* b, int k, int which, int it, float tol, const smm_hip_precond* M, const float* x0, long long ldx0,
+	                     unsigned long long seed, float* w, float* x, long long ldx, float* rn, int* nconv, int* iterations, int* matvecs, int* bmatvecs, int* applies, int* st) {
+		return smm_hip_lobpcg_gen_f32(a, b, k, which, it, tol, M, x0, ldx0, seed, w, x, ldx, rn, nconv, iterations, matvecs, bmatvecs, applies, st);
+	}
 	static int idrs(const smm_hip_csr* a, float* b, float* x, int it, float eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f32(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
 	}
@@ -161,6 +165,10 @@ struct Abi<double> {
 	static int lobpcg(const smm_hip_csr* a, int k, int which, int it, double tol, const smm_hip_precond* M, const double* x0, long long ldx0, unsigned long long seed, double* w,
 	                  double* x, long long ldx, double* rn, int* nconv, int* iterations, int* matvecs, int* applies, int* st) {
 		return smm_hip_lobpcg_f64(a, k, which, it, tol, M, x0, ldx0, seed, w, x, ldx, rn, nconv, iterations, matvecs, applies, st);
+	}
+	static int lobpcgGen(const smm_hip_csr* a, const smm_hip_csr* b, int k, int which, int it, double tol, const smm_hip_precond* M, const double* x0, long long ldx0,
+	                     unsigned long long seed, double* w, double* x, long long ldx, double* rn, int* nconv, int* iterations, int* matvecs, int* bmatvecs, int* applies, int* st) {
+		return smm_hip_lobpcg_gen_f64(a, b, k, which, it, tol, M, x0, ldx0, seed, w, x, ldx, rn, nconv, iterations, matvecs, bmatvecs, applies, st);
 	}
 	static int idrs(const smm_hip_csr* a, double* b, double* x, int it, double eps, int s, const smm_hip_precond* M, int* st) {
 		return smm_hip_idrs_f64(a, b, x, it, eps, s, M, 0ull, st, nullptr, nullptr);
@@ -1778,6 +1786,39 @@ template <typename T>
 inline SolverStatus lobpcg(const CSRMatrix<T>& a, int k, int which, T* eigenvalues, T* eigenvectors = nullptr, T tol = T(0), int maxIterations = 1000,
                            const T* X0 = nullptr, unsigned long long seed = 0, T* residuals = nullptr, LobpcgInfo* info = nullptr) {
 	return lobpcg(a, k, which, eigenvalues, eigenvectors, typename CSRMatrix<T>::IDPreconditioner(), tol, maxIterations, X0, seed, residuals, info);
+}
+
+// The GENERALISED problem A x = lambda B x (K x = lambda M x with a mass matrix: the vibration modes), smm_hip_lobpcg_gen_*: `b` is a
+// symmetric positive definite matrix of a's size.  Everything else is lobpcg's above; the eigenvectors come out B-orthonormal, the
+// preconditioner still approximates A^-1 and fits `a`, and info->bmatvecs counts the products with B.  b may be `a` itself.
+struct LobpcgGenInfo : LobpcgInfo {
+	int bmatvecs = 0;
+};
+template <typename Preconditioner, typename T>
+inline SolverStatus lobpcg(const CSRMatrix<T>& a, const CSRMatrix<T>& b, int k, int which, T* eigenvalues, T* eigenvectors, const Preconditioner& preconditioner,
+                           T tol = T(0), int maxIterations = 1000, const T* X0 = nullptr, unsigned long long seed = 0, T* residuals = nullptr,
+                           LobpcgGenInfo* info = nullptr) {
+	static_assert(std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value ||
+	                  std::is_base_of<typename CSRMatrix<T>::PreconditionerBase, Preconditioner>::value,
+	              "lobpcg runs the library's own preconditioners only");
+	int st = 0;
+	LobpcgGenInfo local;
+	LobpcgGenInfo* o = info ? info : &local;
+	const smm_hip_csr* d = a.device();
+	const smm_hip_csr* db = &b == &a ? d : b.device();
+	const smm_hip_precond* h = preconditioner.handle();
+	constexpr bool precondition = !std::is_same<Preconditioner, typename CSRMatrix<T>::IDPreconditioner>::value;
+	if (d && db && precondition && !h) return SolverStatus::DIVERGED;  // (the preconditioner could not be built: lastHipStatus() says why)
+	const long long rows = static_cast<long long>(a.getDenseRowCount());
+	const int rc = d && db ? detail::Abi<T>::lobpcgGen(d, db, k, which, maxIterations, tol, h, X0, rows, seed, eigenvalues, eigenvectors, rows, residuals, &o->nconv,
+	                                                   &o->iterations, &o->matvecs, &o->bmatvecs, &o->applies, &st)
+	                       : SMM_HIP_ERR_NO_DEVICE;
+	return detail::toStatus(rc, st);
+}
+template <typename T>
+inline SolverStatus lobpcg(const CSRMatrix<T>& a, const CSRMatrix<T>& b, int k, int which, T* eigenvalues, T* eigenvectors = nullptr, T tol = T(0),
+                           int maxIterations = 1000, const T* X0 = nullptr, unsigned long long seed = 0, T* residuals = nullptr, LobpcgGenInfo* info = nullptr) {
+	return lobpcg(a, b, k, which, eigenvalues, eigenvectors, typename CSRMatrix<T>::IDPreconditioner(), tol, maxIterations, X0, seed, residuals, info);
 }
 
 // ---- an addition with no counterpart in the reference: IDR(s), biorthogonal form, with right preconditioning (smm_hip.h states the loop) ----

@@ -85,6 +85,12 @@ _TYPED = {
                                    POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "smm_hip_multi_gram_dev": (c_int, [c_int, c_int, c_int, _P, c_longlong, _P, c_longlong, _P, c_longlong, _P]),
     "smm_hip_multi_block_axpy_dev": (c_int, [c_int, c_int, c_int, _P, c_longlong, _P, c_longlong, _P, c_longlong, _P]),
+    "smm_hip_lobpcg_gen": (c_int, [_P, _P, c_int, c_int, c_int, "T", _P, _P, c_longlong, c_ulonglong, _P, _P, c_longlong, _P, POINTER(c_int), POINTER(c_int),
+                                   POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "smm_hip_lobpcg_gen_dev": (c_int, [_P, _P, c_int, c_int, c_int, "T", _P, _P, c_longlong, c_ulonglong, _P, _P, c_longlong, _P, _P, POINTER(c_int), POINTER(c_int),
+                                       POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "smm_hip_multi_block_axpy_bases_dev": (c_int, [c_int, c_int, c_int, c_int, POINTER(_P), c_longlong, _P, c_longlong, POINTER(_P), c_longlong, _P]),
+    "smm_hip_multi_rotate_bases_dev": (c_int, [c_int, c_int, c_int, c_int, POINTER(_P), c_longlong, _P, c_longlong, _P]),
     "smm_hip_bicg": (c_int, [_P, _P, _P, _P, c_int, "T", POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_bicg_dev": (c_int, [_P, _P, _P, _P, c_int, "T", _P, POINTER(c_int), POINTER(c_int), "PT"]),
     "smm_hip_lsqr": (c_int, [_P, _P, _P, _P, c_int, "T", "T", POINTER(c_int), POINTER(c_int), POINTER(c_int), "PT", "PT"]),

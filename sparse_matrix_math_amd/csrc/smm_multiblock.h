@@ -232,16 +232,9 @@ __device__ __forceinline__ void multiBlockAxpyRows(const T* vrow, long long ldV,
 	}
 }
 
-// R > 1 needs V and W 16-byte aligned and both leading dimensions multiples of R (the launcher checks); the last n % R rows take one lane each.
+// The rows of one workgroup.  R > 1 needs V and W 16-byte aligned and both leading dimensions multiples of R; the last n % R rows take one lane each.
 template <typename T, int MP, int R>
-__global__ __launch_bounds__(MV_TPB) void multiBlockAxpyKernel(long long n, int m, int l, const T* __restrict__ V, long long ldV, const T* __restrict__ H, long long ldH,
-                                                               T* __restrict__ W, long long ldW) {
-	__shared__ T Hs[MP * MB_MAX];
-	for (int i = threadIdx.x; i < MP * l; i += MV_TPB) {
-		const int j = i % MP, c = i / MP;
-		Hs[i] = j < m ? H[j + c * ldH] : T(0);
-	}
-	__syncthreads();
+__device__ __forceinline__ void multiBlockAxpyBody(long long n, int m, int l, const T* V, long long ldV, T* W, long long ldW, const T* Hs) {
 	const long long packs = n / R;
 	for (long long i = static_cast<long long>(blockIdx.x) * MV_TPB + threadIdx.x; i < packs; i += static_cast<long long>(gridDim.x) * MV_TPB) {
 		multiBlockAxpyRows<T, MP, R>(V + i * R, ldV, W + i * R, ldW, m, l, Hs);
@@ -253,13 +246,61 @@ __global__ __launch_bounds__(MV_TPB) void multiBlockAxpyKernel(long long n, int 
 }
 
 template <typename T, int MP>
+__device__ __forceinline__ void multiBlockAxpyStage(int m, int l, const T* __restrict__ H, long long ldH, T* Hs) {
+	for (int i = threadIdx.x; i < MP * l; i += MV_TPB) {
+		const int j = i % MP, c = i / MP;
+		Hs[i] = j < m ? H[j + c * ldH] : T(0);
+	}
+	__syncthreads();
+}
+
+// R as multiBlockAxpyBody's: the launcher checks.
+template <typename T, int MP, int R>
+__global__ __launch_bounds__(MV_TPB) void multiBlockAxpyKernel(long long n, int m, int l, const T* __restrict__ V, long long ldV, const T* __restrict__ H, long long ldH,
+                                                               T* __restrict__ W, long long ldW) {
+	__shared__ T Hs[MP * MB_MAX];
+	multiBlockAxpyStage<T, MP>(m, l, H, ldH, Hs);
+	multiBlockAxpyBody<T, MP, R>(n, m, l, V, ldV, W, ldW, Hs);
+}
+
+// The same update of up to MV_MAX_BASES pairs (V_b, W_b) with ONE H in one launch: blockIdx.y is the pair, the pointers travel by value in
+// the kernel arguments.  Every pair takes the 16-byte path or the element path by its OWN alignment (uniform over the workgroup), so each
+// gets the bits of multiBlockAxpyKernel on it alone.
+template <typename T, int MP>
+__global__ __launch_bounds__(MV_TPB) void multiBlockAxpyBasesKernel(long long n, int m, int l, BasePtrs<const T> Vs, long long ldV, const T* __restrict__ H, long long ldH,
+                                                                    BasePtrs<T> Ws, long long ldW) {
+	constexpr int N = Pack16<T>::N;
+	__shared__ T Hs[MP * MB_MAX];
+	multiBlockAxpyStage<T, MP>(m, l, H, ldH, Hs);
+	const T* V = Vs.at(blockIdx.y);
+	T* W = Ws.at(blockIdx.y);
+	if (aligned16(V) && aligned16(W) && ldV % N == 0 && ldW % N == 0) multiBlockAxpyBody<T, MP, N>(n, m, l, V, ldV, W, ldW, Hs);
+	else multiBlockAxpyBody<T, MP, 1>(n, m, l, V, ldV, W, ldW, Hs);
+}
+
+template <typename T, int MP>
 inline void multiBlockAxpyLaunchMP(long long n, int m, int l, const T* V, long long ldV, const T* H, long long ldH, T* W, long long ldW, hipStream_t s) {
 	constexpr int N = Pack16<T>::N;
 	const bool vec = ((reinterpret_cast<unsigned long long>(V) | reinterpret_cast<unsigned long long>(W)) & 15ull) == 0 && ldV % N == 0 && ldW % N == 0;
-	const long long lanes = vec ? (n / N > 0 ? n / N : 1) : n;
-	const int g = static_cast<int>(std::max<long long>(1, std::min<long long>((lanes + MV_TPB - 1) / MV_TPB, 4 * NPART)));
+	const int g = rowLanesGrid<T>(n, vec);
 	if (vec) multiBlockAxpyKernel<T, MP, N><<<g, MV_TPB, 0, s>>>(n, m, l, V, ldV, H, ldH, W, ldW);
 	else multiBlockAxpyKernel<T, MP, 1><<<g, MV_TPB, 0, s>>>(n, m, l, V, ldV, H, ldH, W, ldW);
+}
+
+template <typename T, int MP>
+inline void multiBlockAxpyBasesLaunchMP(long long n, int m, int l, int nb, const T* const* V, long long ldV, const T* H, long long ldH, T* const* W, long long ldW,
+                                        hipStream_t s) {
+	constexpr int N = Pack16<T>::N;
+	BasePtrs<const T> vs;
+	BasePtrs<T> ws;
+	int g = 1;  // the widest any pair needs: the rows are walked by a grid-stride loop
+	for (int b = 0; b < MV_MAX_BASES; ++b) {
+		vs.p[b] = V[b < nb ? b : 0];
+		ws.p[b] = W[b < nb ? b : 0];
+		const bool vec = ((reinterpret_cast<unsigned long long>(vs.p[b]) | reinterpret_cast<unsigned long long>(ws.p[b])) & 15ull) == 0 && ldV % N == 0 && ldW % N == 0;
+		g = std::max(g, rowLanesGrid<T>(n, vec));
+	}
+	multiBlockAxpyBasesKernel<T, MP><<<dim3(g, nb), MV_TPB, 0, s>>>(n, m, l, vs, ldV, H, ldH, ws, ldW);
 }
 
 // 1 <= m, l <= MB_MAX, n >= 1, V and W do not overlap (the caller checks).
@@ -268,6 +309,16 @@ inline void multiBlockAxpyLaunch(long long n, int m, int l, const T* V, long lon
 	if (m <= 8) multiBlockAxpyLaunchMP<T, 8>(n, m, l, V, ldV, H, ldH, W, ldW, s);
 	else if (m <= 16) multiBlockAxpyLaunchMP<T, 16>(n, m, l, V, ldV, H, ldH, W, ldW, s);
 	else multiBlockAxpyLaunchMP<T, 24>(n, m, l, V, ldV, H, ldH, W, ldW, s);
+}
+
+// W_b -= V_b H for the pairs b < nb in ONE launch.  1 <= nb <= MV_MAX_BASES, otherwise as multiBlockAxpyLaunch; no V_b overlaps any W_c (the
+// caller checks).
+template <typename T>
+inline void multiBlockAxpyBasesLaunch(long long n, int m, int l, int nb, const T* const* V, long long ldV, const T* H, long long ldH, T* const* W, long long ldW,
+                                      hipStream_t s) {
+	if (m <= 8) multiBlockAxpyBasesLaunchMP<T, 8>(n, m, l, nb, V, ldV, H, ldH, W, ldW, s);
+	else if (m <= 16) multiBlockAxpyBasesLaunchMP<T, 16>(n, m, l, nb, V, ldV, H, ldH, W, ldW, s);
+	else multiBlockAxpyBasesLaunchMP<T, 24>(n, m, l, nb, V, ldV, H, ldH, W, ldW, s);
 }
 
 }  // namespace smm

@@ -307,12 +307,9 @@ __device__ __forceinline__ void multiRotateRows(T* row, long long ld, int m, int
 	}
 }
 
-// R > 1 needs V 16-byte aligned and ld a multiple of R (the launcher checks); the last n % R rows take one lane each.
+// The rows of one workgroup.  R > 1 needs V 16-byte aligned and ld a multiple of R; the last n % R rows take one lane each.
 template <typename T, int MP, int R>
-__global__ __launch_bounds__(MV_TPB) void multiRotateKernel(long long n, int m, int l, T* V, long long ld, const T* __restrict__ Y) {
-	__shared__ T Ys[MP * MP];
-	for (int i = threadIdx.x; i < MP * l; i += MV_TPB) Ys[i] = Y[i];
-	__syncthreads();
+__device__ __forceinline__ void multiRotateBody(long long n, int m, int l, T* V, long long ld, const T* Ys) {
 	const long long packs = n / R;
 	for (long long i = static_cast<long long>(blockIdx.x) * MV_TPB + threadIdx.x; i < packs; i += static_cast<long long>(gridDim.x) * MV_TPB) {
 		multiRotateRows<T, MP, R>(V + i * R, ld, m, l, Ys);
@@ -323,13 +320,62 @@ __global__ __launch_bounds__(MV_TPB) void multiRotateKernel(long long n, int m, 
 	}
 }
 
+// R as multiRotateBody's: the launcher checks.
+template <typename T, int MP, int R>
+__global__ __launch_bounds__(MV_TPB) void multiRotateKernel(long long n, int m, int l, T* V, long long ld, const T* __restrict__ Y) {
+	__shared__ T Ys[MP * MP];
+	for (int i = threadIdx.x; i < MP * l; i += MV_TPB) Ys[i] = Y[i];
+	__syncthreads();
+	multiRotateBody<T, MP, R>(n, m, l, V, ld, Ys);
+}
+
+// Up to MV_MAX_BASES bases that one launch of a row-per-lane kernel works on (smm_solvers_lobpcg.hip: S, AS and BS take the same small
+// matrix).  The pointers travel BY VALUE in the kernel arguments; blockIdx.y picks one by comparisons, so the array is never indexed by
+// a run-time value and stays in scalar registers.
+constexpr int MV_MAX_BASES = SMM_LOBPCG_MAX_BASES;
+static_assert(MV_MAX_BASES == 3, "BasePtrs::at picks among three");
+template <typename T>
+struct BasePtrs {
+	T* p[MV_MAX_BASES];
+	__device__ __forceinline__ T* at(unsigned b) const { return b == 0 ? p[0] : b == 1 ? p[1] : p[2]; }
+};
+
+// a pack of rows per lane only where its values fit the budget
+template <typename T, int MP>
+constexpr bool multiRotateFits = MP * Pack16<T>::N * static_cast<int>(sizeof(T) / 4) <= MR_MAX_HELD;
+
+// multiRotateKernel on the bases b < gridDim.y with ONE Y in one launch.  Every basis takes the 16-byte path or the element path by its
+// OWN alignment (uniform over the workgroup), so each gets the bits of multiRotateKernel on it alone.
+template <typename T, int MP>
+__global__ __launch_bounds__(MV_TPB) void multiRotateBasesKernel(long long n, int m, int l, BasePtrs<T> Vs, long long ld, const T* __restrict__ Y) {
+	constexpr int N = Pack16<T>::N;
+	__shared__ T Ys[MP * MP];
+	for (int i = threadIdx.x; i < MP * l; i += MV_TPB) Ys[i] = Y[i];
+	__syncthreads();
+	T* V = Vs.at(blockIdx.y);
+	if constexpr (multiRotateFits<T, MP>) {
+		if (aligned16(V) && ld % N == 0) {
+			multiRotateBody<T, MP, N>(n, m, l, V, ld, Ys);
+			return;
+		}
+	}
+	multiRotateBody<T, MP, 1>(n, m, l, V, ld, Ys);
+}
+
+// workgroups of a row-per-lane launch over n rows: a lane owns one row, or one 16-byte pack of rows
+template <typename T>
+inline int rowLanesGrid(long long n, bool vec) {
+	constexpr int N = Pack16<T>::N;
+	const long long lanes = vec ? (n / N > 0 ? n / N : 1) : n;
+	return static_cast<int>(std::max<long long>(1, std::min<long long>((lanes + MV_TPB - 1) / MV_TPB, 4 * NPART)));
+}
+
 template <typename T, int MP>
 inline void multiRotateLaunchMP(long long n, int m, int l, T* V, long long ld, const T* dY, hipStream_t s) {
 	constexpr int N = Pack16<T>::N;
-	constexpr bool fits = MP * N * static_cast<int>(sizeof(T) / 4) <= MR_MAX_HELD;  // a pack of rows per lane only where its values fit the budget
+	constexpr bool fits = multiRotateFits<T, MP>;
 	const bool vec = fits && (reinterpret_cast<unsigned long long>(V) & 15ull) == 0 && ld % N == 0;
-	const long long lanes = vec ? (n / N > 0 ? n / N : 1) : n;
-	const int g = static_cast<int>(std::max<long long>(1, std::min<long long>((lanes + MV_TPB - 1) / MV_TPB, 4 * NPART)));
+	const int g = rowLanesGrid<T>(n, vec);
 	if constexpr (fits) {
 		if (vec) {
 			multiRotateKernel<T, MP, N><<<g, MV_TPB, 0, s>>>(n, m, l, V, ld, dY);
@@ -337,6 +383,19 @@ inline void multiRotateLaunchMP(long long n, int m, int l, T* V, long long ld, c
 		}
 	}
 	multiRotateKernel<T, MP, 1><<<g, MV_TPB, 0, s>>>(n, m, l, V, ld, dY);
+}
+
+template <typename T, int MP>
+inline void multiRotateBasesLaunchMP(long long n, int m, int l, int nb, T* const* V, long long ld, const T* dY, hipStream_t s) {
+	constexpr int N = Pack16<T>::N;
+	BasePtrs<T> vs;
+	int g = 1;  // the widest any basis needs: the rows are walked by a grid-stride loop
+	for (int b = 0; b < MV_MAX_BASES; ++b) {
+		vs.p[b] = V[b < nb ? b : 0];
+		const bool vec = multiRotateFits<T, MP> && (reinterpret_cast<unsigned long long>(vs.p[b]) & 15ull) == 0 && ld % N == 0;
+		g = std::max(g, rowLanesGrid<T>(n, vec));
+	}
+	multiRotateBasesKernel<T, MP><<<dim3(g, nb), MV_TPB, 0, s>>>(n, m, l, vs, ld, dY);
 }
 
 inline int multiRotatePad(int m) { return m <= 16 ? 16 : m <= 32 ? 32 : MR_MAX; }
@@ -361,6 +420,16 @@ inline void multiRotateLaunch(long long n, int m, int l, T* V, long long ld, con
 		case 16: multiRotateLaunchMP<T, 16>(n, m, l, V, ld, dY, s); break;
 		case 32: multiRotateLaunchMP<T, 32>(n, m, l, V, ld, dY, s); break;
 		default: multiRotateLaunchMP<T, 64>(n, m, l, V, ld, dY, s); break;
+	}
+}
+
+// V_b[:, 0..l-1] = V_b[:, 0..m-1] Y for the bases b < nb in ONE launch.  1 <= nb <= MV_MAX_BASES, otherwise as multiRotateLaunch.
+template <typename T>
+inline void multiRotateBasesLaunch(long long n, int m, int l, int nb, T* const* V, long long ld, const T* dY, hipStream_t s) {
+	switch (multiRotatePad(m)) {
+		case 16: multiRotateBasesLaunchMP<T, 16>(n, m, l, nb, V, ld, dY, s); break;
+		case 32: multiRotateBasesLaunchMP<T, 32>(n, m, l, nb, V, ld, dY, s); break;
+		default: multiRotateBasesLaunchMP<T, 64>(n, m, l, nb, V, ld, dY, s); break;
 	}
 }
 

@@ -348,11 +348,23 @@ def _q1_stiffness(dim, nu):
 _CLAMP = {"left": (0, 0), "right": (0, -1), "bottom": (1, 0), "top": (1, -1), "front": (2, 0), "back": (2, -1)}
 
 
-def _elasticity(cells, nu, clamp, dtype):
+def _q1_mass(dim, rho):
+    """the consistent element mass matrix of the unit Q1 square or cube of density rho, exact: the tensor product of the 1-D linear
+    element's [[1/3, 1/6], [1/6, 1/3]]; dofs ordered as _q1_stiffness orders them, the components of a corner not coupled"""
+    one = np.array([[2.0, 1.0], [1.0, 2.0]])
+    nodal = np.ones((1, 1))
+    for _ in range(dim):
+        nodal = np.kron(one, nodal)  # the last factor is the slowest axis: corner c has bit a for axis a
+    return np.kron(nodal * (rho / 6.0 ** dim), np.eye(dim))
+
+
+def _q1_assemble(who, cells, element, clamp, dtype, stored=None):
+    """the element matrix `element` (dim 2^dim square: corner by corner, component inside the corner) summed over the cells of the grid,
+    the nodes of the clamped side removed; `stored` (None: all): the entries of the element matrix that enter the pattern"""
     dim = len(cells)
     dtype = np.dtype(dtype).type
     if any(c < 1 for c in cells) or clamp not in _CLAMP or _CLAMP[clamp][0] >= dim:
-        raise ValueError(f"elasticity: {cells} cells clamped at {clamp!r}")
+        raise ValueError(f"{who}: {cells} cells clamped at {clamp!r}")
     nodes = [c + 1 for c in cells]
     grid = np.stack(np.meshgrid(*[np.arange(m) for m in nodes[::-1]], indexing="ij")[::-1], axis=-1).reshape(-1, dim)  # x fastest
     axis, side = _CLAMP[clamp]
@@ -365,9 +377,11 @@ def _elasticity(cells, nu, clamp, dtype):
     free = kept[node]
     dof = (number[node][:, :, None] * dim + np.arange(dim)).reshape(len(cell), -1)
     free = np.repeat(free, dim, axis=1)
-    K = _q1_stiffness(dim, nu)
+    K = element
     n = int(kept.sum()) * dim
     pair = free[:, :, None] & free[:, None, :]
+    if stored is not None:
+        pair = pair & stored
     keys = (dof[:, :, None] * n + dof[:, None, :])[pair]
     vals = np.broadcast_to(K, pair.shape)[pair]
     uniq, slot = np.unique(keys, return_inverse=True)
@@ -375,6 +389,10 @@ def _elasticity(cells, nu, clamp, dtype):
     start = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(np.bincount(uniq // n, minlength=n), out=start[1:])
     return start.astype(np.int32), (uniq % n).astype(np.int32), values.astype(dtype), grid[kept].astype(np.float64)
+
+
+def _elasticity(cells, nu, clamp, dtype):
+    return _q1_assemble("elasticity", cells, _q1_stiffness(len(cells), nu), clamp, dtype)
 
 
 def elasticity2d(nx, ny, nu=0.3, clamp="left", dtype=np.float64):
@@ -389,6 +407,22 @@ def elasticity3d(nx, ny, nz, nu=0.3, clamp="left", dtype=np.float64):
     face ("left", "right", "bottom", "top", "front", "back") clamped and removed.  Three dofs per kept node.  Returns (start, positions,
     values, coords) as elasticity2d does, coords (nodes, 3)."""
     return _elasticity([int(nx), int(ny), int(nz)], float(nu), clamp, dtype)
+
+
+def mass2d(nx, ny, clamp="left", rho=1.0, dtype=np.float64):
+    """The consistent Q1 mass matrix (density rho) on the mesh, the node numbering and the clamping of elasticity2d(nx, ny, clamp=clamp):
+    two dofs per kept node, u_x and u_y not coupled (no entry is stored between them).  Returns (start, positions, values): CSR with ascending columns, symmetric positive
+    definite -- the M of the vibration problem K x = lambda M x (lobpcg(K, ..., B=M))."""
+    cells = [int(nx), int(ny)]
+    element = _q1_mass(2, float(rho))
+    return _q1_assemble("mass", cells, element, clamp, dtype, stored=element != 0)[:3]
+
+
+def mass3d(nx, ny, nz, clamp="left", rho=1.0, dtype=np.float64):
+    """mass2d on the mesh of elasticity3d(nx, ny, nz, clamp=clamp): three dofs per kept node."""
+    cells = [int(nx), int(ny), int(nz)]
+    element = _q1_mass(3, float(rho))
+    return _q1_assemble("mass", cells, element, clamp, dtype, stored=element != 0)[:3]
 
 
 def rigid_body_modes(coords, dtype=np.float64):

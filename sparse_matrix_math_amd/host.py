@@ -1536,10 +1536,12 @@ def svds_dev(a, k, d_s, d_U, ldu, d_V, ldv, ncv=0, tol=0.0, max_restarts=300, d_
 
 
 LOBPCG_MAX_K, LOBPCG_MAX_BASIS = 8, 24  # SMM_LOBPCG_MAX_K, SMM_LOBPCG_MAX_BASIS
+LOBPCG_MAX_BASES = 3  # SMM_LOBPCG_MAX_BASES
 LobpcgInfo = collections.namedtuple("LobpcgInfo", "residuals nconv iterations matvecs applies status")
+LobpcgGenInfo = collections.namedtuple("LobpcgGenInfo", LobpcgInfo._fields + ("bmatvecs",))
 
 
-def lobpcg(a, k=4, which="SA", M=None, X0=None, tol=0.0, max_iterations=1000, seed=0, return_eigenvectors=True):
+def lobpcg(a, k=4, which="SA", M=None, X0=None, tol=0.0, max_iterations=1000, seed=0, return_eigenvectors=True, B=None):
     """The k algebraically smallest ("SA") or largest ("LA") eigenvalues of the symmetric CSRMatrix `a`, with their eigenvectors, by
     LOBPCG on the device -- the preconditioned block method, an addition (include/smm_hip.h states the loop).  1 <= k <= LOBPCG_MAX_K
     with 3k <= rows.  M: None or a symmetric positive definite preconditioner (any kind ConjugateGradient takes, or JACOBI or SGS) of a matrix of the same
@@ -1547,7 +1549,11 @@ def lobpcg(a, k=4, which="SA", M=None, X0=None, tol=0.0, max_iterations=1000, se
     None for the hash columns of `seed`, or a (rows, k) start block.  tol <= 0 means the machine epsilon of the dtype; column j has
     converged when ||A x_j - theta_j x_j|| <= tol * max|theta|.  Returns (w, X, info), or (w, info) with return_eigenvectors=False: w in
     the order of `which`, X of shape (rows, k), info a LobpcgInfo(residuals, nconv, iterations, matvecs, applies, status).  When status
-    is MAX_ITERATIONS_REACHED the pairs are the best available; when it is DIVERGED they are not written."""
+    is MAX_ITERATIONS_REACHED the pairs are the best available; when it is DIVERGED they are not written.
+    B: None, or a symmetric positive definite CSRMatrix of the same size and dtype: the GENERALISED problem A x = lambda B x (K x =
+    lambda M x with a mass matrix: the vibration modes).  Column j has then converged when ||A x_j - theta_j B x_j|| <= tol *
+    max|theta| * ||B x_j||, X is B-orthonormal (X^T B X = I), M still approximates A^-1, and info is a LobpcgGenInfo: LobpcgInfo's
+    fields and bmatvecs, the products with B."""
     suf = a._suf
     k = int(k)
     w = np.zeros(max(k, 0), dtype=a.dtype)
@@ -1559,12 +1565,16 @@ def lobpcg(a, k=4, which="SA", M=None, X0=None, tol=0.0, max_iterations=1000, se
         if X0.dtype != a.dtype or X0.shape != (a.rows, k):
             raise TypeError(f"X0 must be a ({a.rows}, {k}) array of {a.dtype}")
         start = np.ascontiguousarray(X0.T)  # row j: start column j
-    nconv, its, matvecs, applies, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    check(_fn("smm_hip_lobpcg", suf)(a._h, k, _eigsh_which(which), int(max_iterations), a.dtype.type(tol), _mh(M),
-                                     None if start is None else start.ctypes.data_as(ctypes.c_void_p), a.rows, int(seed), w.ctypes.data_as(ctypes.c_void_p),
-                                     None if X is None else X.ctypes.data_as(ctypes.c_void_p), a.rows, res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
-                                     ctypes.byref(its), ctypes.byref(matvecs), ctypes.byref(applies), ctypes.byref(st)))
-    info = LobpcgInfo(res, nconv.value, its.value, matvecs.value, applies.value, SolverStatus(st.value))
+    nconv, its, matvecs, bmatvecs, applies, st = (ctypes.c_int() for _ in range(6))
+    head = (k, _eigsh_which(which), int(max_iterations), a.dtype.type(tol), _mh(M), None if start is None else start.ctypes.data_as(ctypes.c_void_p), a.rows, int(seed),
+            w.ctypes.data_as(ctypes.c_void_p), None if X is None else X.ctypes.data_as(ctypes.c_void_p), a.rows, res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
+            ctypes.byref(its), ctypes.byref(matvecs))
+    if B is None:
+        check(_fn("smm_hip_lobpcg", suf)(a._h, *head, ctypes.byref(applies), ctypes.byref(st)))
+        info = LobpcgInfo(res, nconv.value, its.value, matvecs.value, applies.value, SolverStatus(st.value))
+    else:
+        check(_fn("smm_hip_lobpcg_gen", suf)(a._h, B._h, *head, ctypes.byref(bmatvecs), ctypes.byref(applies), ctypes.byref(st)))
+        info = LobpcgGenInfo(res, nconv.value, its.value, matvecs.value, applies.value, SolverStatus(st.value), bmatvecs.value)
     return (w, X.T, info) if return_eigenvectors else (w, info)
 
 
@@ -1579,6 +1589,44 @@ def lobpcg_dev(a, k, which, d_w, d_X, ldx, M=None, d_X0=None, ldx0=0, tol=0.0, m
                                          _dptr(d_X), int(ldx), _dptr(stream), res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv), ctypes.byref(its),
                                          ctypes.byref(matvecs), ctypes.byref(applies), ctypes.byref(st)))
     return LobpcgInfo(res, nconv.value, its.value, matvecs.value, applies.value, SolverStatus(st.value))
+
+
+def lobpcg_gen_dev(a, B, k, which, d_w, d_X, ldx, M=None, d_X0=None, ldx0=0, tol=0.0, max_iterations=1000, seed=0, stream=None):
+    """device-pointer lobpcg for A x = lambda B x: lobpcg_dev's arguments with the CSRMatrix B after `a` (None: the standard problem, the
+    bits of lobpcg_dev, bmatvecs 0).  Returns a LobpcgGenInfo (residuals: a host array).  Synchronises `stream`."""
+    suf = a._suf
+    k = int(k)
+    res = np.zeros(max(k, 0), dtype=a.dtype)
+    nconv, its, matvecs, bmatvecs, applies, st = (ctypes.c_int() for _ in range(6))
+    check(_fn("smm_hip_lobpcg_gen_dev", suf)(a._h, _mh(B), k, _eigsh_which(which), int(max_iterations), a.dtype.type(tol), _mh(M), _dptr(d_X0), int(ldx0), int(seed),
+                                             _dptr(d_w), _dptr(d_X), int(ldx), _dptr(stream), res.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nconv),
+                                             ctypes.byref(its), ctypes.byref(matvecs), ctypes.byref(bmatvecs), ctypes.byref(applies), ctypes.byref(st)))
+    return LobpcgGenInfo(res, nconv.value, its.value, matvecs.value, applies.value, SolverStatus(st.value), bmatvecs.value)
+
+
+def _dptr_array(items):
+    """a host array of device pointers (None entries are null pointers)"""
+    return (ctypes.c_void_p * len(items))(*[_dptr(t) for t in items])
+
+
+def multi_block_axpy_bases_dev(n, m, l, d_V, ldV, d_H, ldH, d_W, ldW, dtype, stream=None):
+    """multi_block_axpy_dev on the pairs (d_V[i], d_W[i]) of two equally long sequences of 1 .. LOBPCG_MAX_BASES device pointers with one
+    d_H, in ONE launch; every pair gets the bits of multi_block_axpy_dev alone.  No V may overlap any W.  Asynchronous."""
+    if len(d_V) != len(d_W):
+        raise ValueError("d_V and d_W must hold as many bases")
+    check(_fn("smm_hip_multi_block_axpy_bases_dev", _suffix(dtype))(int(n), int(m), int(l), len(d_V), _dptr_array(d_V), int(ldV), _dptr(d_H), int(ldH), _dptr_array(d_W),
+                                                                    int(ldW), _dptr(stream)))
+
+
+def multi_rotate_bases_dev(n, m, l, d_V, ld, Y, dtype, stream=None):
+    """multi_rotate_dev on every basis of the sequence d_V (1 .. LOBPCG_MAX_BASES device pointers) with one (m, l) HOST array Y, staged
+    once, in ONE launch; every basis gets the bits of multi_rotate_dev alone.  Synchronises `stream`."""
+    Y = np.asarray(Y)
+    if Y.dtype != np.dtype(dtype) or Y.shape != (int(m), int(l)):
+        raise TypeError(f"Y must be an ({m}, {l}) array of {np.dtype(dtype)}")
+    Yf = np.asfortranarray(Y)  # element (i, c) at i + c * m
+    check(_fn("smm_hip_multi_rotate_bases_dev", _suffix(dtype))(int(n), int(m), int(l), len(d_V), _dptr_array(d_V), int(ld), Yf.ctypes.data_as(ctypes.c_void_p), int(m),
+                                                                _dptr(stream)))
 
 
 def multi_gram_dev(n, m, l, d_V, ldV, d_W, ldW, d_G, ldG, dtype, stream=None):
