@@ -1,7 +1,7 @@
 // smm_csr_build.h -- the kit of the device operations that build a new smm_hip_csr or rewrite the values of one they made earlier
 // (transpose, permutation, assembly, product, sum, block matrix / submatrix, conversion) and of the set-up code that scans and sorts.
 //   device primitives: the rocprim scans and radix sorts, each behind ONE two-phase call (size query, scratch, run) -- no other file of the
-//     library names rocprim (smm_dist.hip keeps a scan of its own);
+//     library names rocprim (smm_dist_create.hip keeps a scan of its own);
 //   small host helpers: bitsFor, gridOf, Word<T>, readFlag;
 //   handle construction: OwnedCsr, newOwnedCsr, allocCsrEntries (every array holds at least one element);
 //   shared tails: startsFromCounts (row counts -> start[] with the 2^31 - 1 refusal), adoptValues (a scratch array becomes the values),

@@ -40,6 +40,12 @@ struct RowRanges {
 		}
 	}
 };
+inline RowRanges wholeRange(int n) {  // rows [0, n) as one run
+	RowRanges all{};
+	all.n = 1;
+	all.hi[0] = n;
+	return all;
+}
 
 // `book` in the steps below: this launch records the scalars.  Of a boundary / bulk pair of launches both form them from the same
 // operands, one writes them; a launch over the whole vector passes true.

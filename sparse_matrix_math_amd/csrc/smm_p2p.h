@@ -7,7 +7,7 @@
 //   * every rank owns a SYMMETRIC BLOCK of fine-grained device memory (coherent without kernel boundaries: remote writes are seen by
 //     system-scope loads), exported once with hipIpcGetMemHandle and mapped by every peer (ranks must be separate PROCESSES: between threads
 //     of one process the set-up votes for the collectives -- HIP may put two streams of a process on one hardware queue, and a kernel that
-//     waits for a peer's kernel would then sit in front of it; smm_dist.hip, p2pSetup): flags, reduction slots, a LANDING area per
+//     waits for a peer's kernel would then sit in front of it; smm_dist_p2p.hip, p2pSetup): flags, reduction slots, a LANDING area per
 //     halo-extended vector and a STAGING area for data this rank relays;
 //   * halo: a push kernel on the communicator's side stream copies the boundary slices of the freshly updated vector into the
 //     neighbours' landing areas, one share DIRECTLY and the other shares through RELAY ranks (rank g -> r -> g + 1 uses the links
@@ -25,7 +25,7 @@
 // r06: the DEFAULT between processes (SMM_HIP_P2P=0 on any rank turns it off): taken when every rank succeeds in mapping every peer and in
 // the create-time self-test -- every reduction point through the slots, five halo exchanges through every path --; the halo part failing
 // leaves the scalars in the slots and the halo with the communicator (the hybrid), the scalar part failing leaves everything with the
-// communicator's collectives (smm_dist.hip, p2pSetup).
+// communicator's collectives (smm_dist_p2p.hip, p2pSetup).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1156,7 +1156,7 @@ static bool launchMarchKN(const smm_hip_csr* m, int op, const T* lhs, const T* d
 	static MarchLaunchState state;
 	int perCU = 0;
 	if (!marchPrepare(state, spmvPatternConstMarchKernel<T, R, KN, NT, HP, FUSE>, lds, 128 /* red[], redF[] */, &perCU)) return false;
-	const int cus = (op & SPMV_LEAVE_ROOM) ? std::max(8, numCUs() - 8) : numCUs();  // room for the RCCL kernel beside A_loc (smm_dist.hip)
+	const int cus = (op & SPMV_LEAVE_ROOM) ? std::max(8, numCUs() - 8) : numCUs();  // room for the RCCL kernel beside A_loc (smm_dist_matvec.hip)
 	op &= ~SPMV_LEAVE_ROOM;
 	const int resident = cus * perCU;
 	// planes per unit: enough units for ~1.5 x the chip's workgroup slots -- on mid-size grids THAT is what matters, not the two extra

@@ -1497,7 +1497,7 @@ template <typename T>
 static void launchPatConst(const smm_hip_csr* m, int op, const T* lhs, const T* divisor, const T* x, T* out, int dotMode, const T* w1, T* partials,
                            const int* doneFlag, hipStream_t s) {
 	if (launchPatConstMarch<T>(m, op, lhs, divisor, x, out, dotMode, w1, partials, doneFlag, s)) return;  // grid-shaped: the 2.5-D form
-	const int cus = (op & SPMV_LEAVE_ROOM) ? std::max(8, numCUs() - 8) : numCUs();  // room for the RCCL kernel beside A_loc (smm_dist.hip)
+	const int cus = (op & SPMV_LEAVE_ROOM) ? std::max(8, numCUs() - 8) : numCUs();  // room for the RCCL kernel beside A_loc (smm_dist_matvec.hip)
 	op &= ~SPMV_LEAVE_ROOM;
 	const int nTiles = (m->rows + TPB - 1) / TPB;
 	const int perCU = std::max(1, env::intOr(env::CONST_WGS_PER_CU, 8));

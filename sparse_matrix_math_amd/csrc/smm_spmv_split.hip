@@ -1,6 +1,6 @@
 // smm_spmv_split.hip -- the row-partitioned SpMV in ONE launch (round 6; the loop it serves: ref:2232-2277).
 //
-// A rank's rows are split into A_loc (owned columns) and A_rem (halo columns), smm_dist.hip.  r01-r05 ran them as two launches: A_loc while
+// A rank's rows are split into A_loc (owned columns) and A_rem (halo columns), smm_dist_create.hip.  r01-r05 ran them as two launches: A_loc while
 // the halo is in flight, then -- behind an event of the communicator's stream -- A_rem, which re-reads and re-writes out[].  The second
 // launch costs a second ramp and tail of a persistent grid, a pass over out[] and a dependent kernel boundary behind the exchange: ~10 us
 // per SpMV of a rank's 1.25 M-row share, two SpMVs per BiCGStab iteration, where the whole iteration has ~190 us at 8 GPUs.

@@ -184,7 +184,7 @@ def test_native_bicgstab_matches_oracle(smm, oracle, world, dtype):
 @pytest.mark.parametrize("world,chunks", [(2, 2), (3, 4), (4, 3)])
 def test_halo_in_pieces(smm, oracle, world, chunks, monkeypatch):
     """SMM_HIP_HALO_CHUNKS: the halo of every SpMV travels in `chunks` exchanges and A_rem is cut by columns into as many parts, part k
-    starting when piece k has landed (csrc/smm_dist.hip, distMatvec).  Row sums are then ((loc + rem_0) + rem_1) + ...: within the bound
+    starting when piece k has landed (csrc/smm_dist_matvec.hip, distMatvec).  Row sums are then ((loc + rem_0) + rem_1) + ...: within the bound
     the one-piece form is held to.  Both kernel families (the banded matrix's blocks stay on the CSR kernels at 6 iterations; the
     converged solves adopt PATTERN), BiCGStab with and without Jacobi (the division rides in the LAST part's epilogue), CG."""
     monkeypatch.setenv("SMM_HIP_HALO_CHUNKS", str(chunks))
@@ -642,7 +642,7 @@ def test_one_launch_spmv_fuzz(smm, oracle, seed):
 @pytest.mark.parametrize("world,dtype,matrix", [(2, np.float64, "band"), (3, np.float32, "band"), (3, np.float64, "grid"), (2, np.float32, "grid"), (2, np.float32, "ragged"),
                                                 (4, np.float64, "ragged"), (3, np.float64, "ragged7"), (2, np.float64, "ragged9"), (4, np.float32, "ragged11")])
 def test_thin_remote_block(smm, oracle, world, dtype, matrix):
-    """csrc/smm_dist.hip thinRemoteKernel (r06): when at most an eighth of a rank's rows hold a remote entry (a narrow band, the slabs of a
+    """csrc/smm_dist_matvec.hip thinRemoteKernel (r06): when at most an eighth of a rank's rows hold a remote entry (a narrow band, the slabs of a
     grid) the second half of the row-partitioned SpMV runs over the listed rows only and the dot products ride in the local launch --
     against the general second launch (SMM_HIP_THIN_REMOTE=0): every SpMV op the same bytes; BiCGStab and CG the same iteration counts, x
     and residual to the solvers' tolerance (the dot products add the same terms in another order); and against the oracle."""

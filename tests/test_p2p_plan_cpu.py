@@ -1,4 +1,4 @@
-"""The peer-to-peer halo plan (csrc/smm_dist.hip, p2pMakePlan; csrc/smm_p2p.h) replayed on the CPU for worlds the one-GPU boxes cannot
+"""The peer-to-peer halo plan (csrc/smm_dist_p2p.hip, p2pMakePlan; csrc/smm_p2p.h) replayed on the CPU for worlds the one-GPU boxes cannot
 run: every rank derives ITS push / forward / land jobs from the globally known column ranges and row bounds alone; here all ranks' jobs are
 executed on numpy arrays -- direct parts into the destinations' landing areas, staged shares into the relays' staging areas and on from
 there, landing areas into the halos -- and every halo element of every rank must hold its owner's value, exactly once, for 2-8 ranks,
